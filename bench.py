@@ -2,7 +2,7 @@
 """Headline benchmark of the render path: rays/s of ImplicitGenerator3d.forward at 128x128x64 spp on synthetic
 ShapeNetCar-shaped inputs (BASELINE.json metric).
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
 
 N > 1 runs one rank per GPU: either the driver starts the ranks itself (`python -m torch.distributed.run ... bench.py
 --gpus N`, WORLD_SIZE in the environment) or this process does -- with WORLD_SIZE unset it only launches N children
@@ -10,10 +10,15 @@ through torch.distributed.run BEFORE anything touches the GPU, relays rank 0's J
 
 A step = one generator forward over this rank's B images (the four random draws, FiLM mapping, channel-last copy of the
 feature volume, weight packing, coarse pass, resampling, fine pass, merge + composite).  Inputs are resident in HBM
-before the timed region.  Rank 0 prints ONE JSON line with the whole-job rays/s, the roofline of the dominant kernel
-(timed with HIP events recorded inside the timed region) and, at N=1, the CPU oracle timed on image 0 of the SAME inputs
-and draws -- whose output is also the checker of the timed run (`check`): the run fails if the image the GPU produced in
-its last timed step does not match it.
+before the timed region.  Rank 0 prints ONE JSON line with the whole-job rays/s and the roofline of the dominant kernel
+(timed with HIP events recorded inside the timed region).  `--dump-outputs DIR` writes what rank 0's last timed step
+returned (pixels, depth) as DIR/<name>.npy; the inputs, parameters and that step's draws are seeded, so two builds can be
+compared output for output.
+
+Everything else is measured only with `--full`: the unfused sample + composite roofline, the fp16x3 / fp16 / in-kernel
+Philox paths, render forward + backward, the GAN step legs and, at N=1, the CPU oracle timed on image 0 of the SAME
+inputs and draws -- whose output is also the checker of the timed run (`check`): the run fails if the image the GPU
+produced in its last timed step does not match it.
 """
 import argparse
 import ctypes
@@ -124,6 +129,23 @@ def synthetic_inputs(B, V, Z, dev, seed):
 def zin(gen, fvol, glob):
     """The generator's `z`: (feature volume, global feature) for the globally conditioned families, the volume alone otherwise."""
     return (fvol, glob) if gen.siren.spec.has_global else fvol
+
+
+DUMP_CAP_BYTES = 60 * 10 ** 6      # the .npy files of one dump stay under 64 MB, headers included
+
+
+def dump_outputs(directory, arrays, cap_bytes=DUMP_CAP_BYTES):
+    """Writes every array as <directory>/<name>.npy in float32.  When they hold more than cap_bytes together, each is
+    replaced by a fixed sample of its flattened elements (seed 0, sorted indices, its share of the cap), so that two
+    runs with the same arguments write the same elements."""
+    os.makedirs(directory, exist_ok=True)
+    arrays = {k: np.ascontiguousarray(v, dtype=np.float32) for k, v in arrays.items()}
+    total = 4 * sum(a.size for a in arrays.values())
+    for name, a in arrays.items():
+        if total > cap_bytes:
+            idx = np.random.default_rng(0).choice(a.size, a.size * cap_bytes // total, replace=False)
+            a = a.reshape(-1)[np.sort(idx)]
+        np.save(os.path.join(directory, name + ".npy"), a)
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -600,14 +622,16 @@ def stub_main(args, rank, world):
     os.environ.setdefault("MASTER_PORT", str(_free_port()))
     dist.init_process_group("gloo", rank=rank, world_size=world)
     elapsed = timed_region(lambda i: time.sleep(0.005 * (1 + rank)), args.steps, args.warmup, dist if world > 1 else None)
-    args.img_size_full, args.img_size, args.num_steps, args.hidden = args.img_size, 16, 4, 64
-    ddp, _ = train_step_ddp(args, torch.device("cpu"), rank, world, dist, stub=True)
+    res = {"metric": "rays/sec at 128x128x64spp ShapeNetCar", "unit": "rays/s", "n_gpus": world, "steps": args.steps,
+           "warmup": args.warmup, "value": whole_job_rays_per_s(world, args.batch, args.img_size, args.steps, elapsed),
+           "ms_per_step": elapsed / args.steps * 1e3, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+           "dtype": "none", "data": "stub: stand-in step on the CPU (launcher test), NOT a measurement",
+           "config": {"workload": "stub"}}
+    if args.full:
+        args.img_size, args.num_steps, args.hidden = 16, 4, 64
+        res["train_step_ddp"], _ = train_step_ddp(args, torch.device("cpu"), rank, world, dist, stub=True)
     if rank == 0:
-        emit_result({"metric": "rays/sec at 128x128x64spp ShapeNetCar", "unit": "rays/s", "n_gpus": world, "steps": args.steps,
-                          "warmup": args.warmup, "value": whole_job_rays_per_s(world, args.batch, args.img_size_full, args.steps, elapsed),
-                          "ms_per_step": elapsed / args.steps * 1e3, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-                          "dtype": "none", "data": "stub: stand-in step on the CPU (launcher test), NOT a measurement",
-                          "config": {"workload": "stub"}, "train_step_ddp": ddp})
+        emit_result(res)
     dist.barrier()
     dist.destroy_process_group()
     return 0
@@ -648,6 +672,10 @@ def main():
     ap.add_argument("--no-miopen-db", action="store_true", help="GAN step legs: MIOpen immediate mode instead of find mode over the shipped find results")
     ap.add_argument("--cpu-reps", type=int, default=2)
     ap.add_argument("--device", default="cuda", choices=["cuda", "cpu"], help="cpu: launcher test with a stand-in step (no measurement)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the pixels and depth that rank 0's last timed step returned as DIR/<name>.npy (float32)")
+    ap.add_argument("--full", action="store_true",
+                    help="also the secondary measurements (sample + composite roofline, fp16x3 / fp16 / Philox paths, forward + backward, "
+                         "GAN step legs) and, at N=1, the CPU oracle baseline and the check of the timed image; the --no-* options select among them")
     args = ap.parse_args()
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
@@ -666,13 +694,16 @@ def main():
         return stub_main(args, rank, world)
     torch.cuda.set_device(local_rank)
     dev = torch.device("cuda", local_rank)
-    # RCCL process group, also for a single rank (the training leg wraps the networks in DDP at every N).  The forward metric has
-    # no data-path collective: there the group only carries the barrier and the max-over-ranks of the elapsed time.
+    # RCCL process group: for N > 1, and with --full also for a single rank (the training leg wraps the networks in DDP at every
+    # N).  The forward metric has no data-path collective: there the group only carries the barrier and the max-over-ranks of the
+    # elapsed time.
     import datetime
     import torch.distributed as dist
-    os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
-    os.environ.setdefault("MASTER_PORT", str(_free_port()))
-    dist.init_process_group("nccl", rank=rank, world_size=world, device_id=dev, timeout=datetime.timedelta(minutes=30))
+    use_dist = world > 1 or args.full
+    if use_dist:
+        os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
+        os.environ.setdefault("MASTER_PORT", str(_free_port()))
+        dist.init_process_group("nccl", rank=rank, world_size=world, device_id=dev, timeout=datetime.timedelta(minutes=30))
 
     import __graft_entry__ as ge
     import cnerf_amd                                   # (the package loads libcnerf_hip.so lazily: importable before the build)
@@ -694,7 +725,7 @@ def main():
 
     # The draws of the LAST timed step are known in advance (torch.cuda seed CHECK_SEED): the CPU oracle renders the expected image
     # of that step from them AFTER all GPU legs (the GPU work of a run is contiguous; the oracle's ~20 s of host time come last).
-    do_check = world == 1 and not args.no_cpu_baseline
+    do_check = args.full and world == 1 and not args.no_cpu_baseline
     base = ref = draws = None
     if do_check:
         torch.cuda.manual_seed(CHECK_SEED)
@@ -715,6 +746,8 @@ def main():
     elapsed = timed_region(step, args.steps, args.warmup, dist if world > 1 else None, torch.cuda.synchronize, dev)
     out = last["out"]
     assert torch.isfinite(out[0]).all() and torch.isfinite(out[1]).all()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"pixels": out[0].cpu().numpy(), "depth": out[1].cpu().numpy()})
 
     # dominant kernel: the field kernel, two launches per step (coarse, fine), same work each
     kern_ms = []
@@ -762,12 +795,12 @@ def main():
                        "parallelism": f"image-batch data parallel x{world}, no data-path collective"},
             "roofline": roof,
         }
-        if world == 1:
+        if args.full and world == 1:
             res["roofline_sample_composite"] = sample_composite_pass(args, gen, fvol, glob, cam, meta, evs)
-        if world == 1 and args.precision == "fp32" and not args.no_fast_path:
+        if args.full and world == 1 and args.precision == "fp32" and not args.no_fast_path:
             res["fp16x3_split_path"] = fast_path(args, gen, fvol, glob, cam, meta, evs)
             res["fp16_single_pass_path"] = fast_path(args, gen, fvol, glob, cam, meta, evs, precision="fp16")
-        if world == 1 and args.precision == "fp32" and not args.no_fast_path:
+        if args.full and world == 1 and args.precision == "fp32" and not args.no_fast_path:
             # the same fp32 step with the four draws generated inside the kernels (no torch RNG kernels, no random tensors)
             gen.rng_mode = "philox"
             try:
@@ -784,9 +817,9 @@ def main():
                 gen.rng_mode = "torch"
             res["philox_rng_path"] = {"value": B * R * R / dtp, "unit": "rays/s", "ms_per_step": dtp * 1e3, "dtype": "f32",
                                       "note": "in-kernel Philox4x32-10 draws (cnerf_cfg.philox) instead of torch.rand / randn tensors"}
-        if world == 1 and not args.no_train_step:
+        if args.full and world == 1 and not args.no_train_step:
             res["train_step"] = train_step_timing(args, gen, fvol, glob, cam, evs)
-    if not args.no_gan_step:          # every rank: the networks are wrapped in DDP over the job's process group
+    if args.full and not args.no_gan_step:          # every rank: the networks are wrapped in DDP over the job's process group
         ddp, legs = train_step_ddp(args, dev, rank, world, dist)
         if rank == 0:
             res["train_step_ddp"] = ddp
@@ -802,8 +835,9 @@ def main():
         emit_result(res)
         if rc:
             sys.stderr.write("bench.py: the timed image FAILED the oracle check: " + json.dumps(res["check"]) + "\n")
-    dist.barrier()
-    dist.destroy_process_group()
+    if use_dist:
+        dist.barrier()
+        dist.destroy_process_group()
     return rc
 
 

@@ -4,7 +4,7 @@ for T in _r02_tree .; do
   ( cd $T
     python -c "import __graft_entry__ as g; g.build()" > /dev/null 2>&1
     echo "== tree $T"
-    timeout -k 10 300 python bench.py --no-train-step --no-cpu-baseline $( [ $T = . ] && echo --no-gan-step ) 2>/dev/null | python -c "
+    timeout -k 10 300 python bench.py --no-train-step --no-cpu-baseline $( [ $T = . ] && echo --full --no-gan-step ) 2>/dev/null | python -c "
 import json,sys
 d=json.loads([l for l in sys.stdin if l.startswith('{')][-1])
 print('  fp32 %.2f ms/launch (%.3f of peak) | fp16x3 %.2f (%.3f) | fp16 %.2f (%.3f) | step %.2f ms' % (d['roofline']['avg_launch_ms'], d['roofline']['frac'], d['fp16x3_split_path']['avg_launch_ms'], d['fp16x3_split_path']['frac_of_fp16_mfma_peak'], d['fp16_single_pass_path']['avg_launch_ms'], d['fp16_single_pass_path']['frac_of_fp16_mfma_peak'], d['ms_per_step']))"

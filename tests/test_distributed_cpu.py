@@ -73,8 +73,8 @@ def test_bench_launches_its_own_ranks():
     import numpy as np
     from conftest import ROOT
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "4", "--warmup", "1", "--device", "cpu"],
-                       capture_output=True, text=True, env=env, timeout=170)
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "4", "--warmup", "1", "--device", "cpu",
+                        "--full"], capture_output=True, text=True, env=env, timeout=170)
     assert p.returncode == 0, p.stderr[-2000:]
     lines = [l for l in p.stdout.splitlines() if l.strip()]
     assert len(lines) == 1, p.stdout
@@ -95,6 +95,43 @@ def test_bench_launches_its_own_ranks():
     assert set(ddp["allreduce_standalone"]) == set(ar) and all(v["ms"] > 0 for v in ddp["allreduce_standalone"].values())
     assert {"d_render", "d_disc_r1_opt", "g_render_fwd", "g_backward", "g_clip_opt", "encoder_fwd"} <= set(ddp["phases_ms_rank0"])
     assert all(np.isfinite(v) for v in ddp["losses"].values())
+
+
+@pytest.mark.timeout(120)
+def test_bench_plain_run_times_only_the_steps():
+    """Without --full the line carries the headline figure and nothing that takes runs of its own (the DDP training leg here)."""
+    import json
+    import subprocess
+    import sys
+    from conftest import ROOT
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--device", "cpu"],
+                       capture_output=True, text=True, env=env, timeout=110)
+    assert p.returncode == 0, p.stderr[-2000:]
+    lines = [l for l in p.stdout.splitlines() if l.strip()]
+    assert len(lines) == 1, p.stdout
+    res = json.loads(lines[0])
+    assert res["steps"] == 3 and res["warmup"] == 1 and res["ms_per_step"] >= 5.0 * 0.9
+    assert {"metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"} <= set(res)
+    assert "train_step_ddp" not in res
+
+
+def test_dump_outputs(tmp_path):
+    """--dump-outputs: float32 .npy per array; above the size cap the same seeded sample of every array, inside the cap."""
+    import numpy as np
+    import bench
+    px = np.random.default_rng(1).standard_normal((2, 3, 8, 8))
+    bench.dump_outputs(str(tmp_path / "a"), {"pixels": px, "depth": px[:, 0]})
+    got = np.load(tmp_path / "a" / "pixels.npy")
+    assert got.dtype == np.float32 and got.shape == px.shape and np.array_equal(got, px.astype(np.float32))
+    assert np.load(tmp_path / "a" / "depth.npy").shape == (2, 8, 8)
+    cap = 4 * 200
+    for d in ("b", "c"):
+        bench.dump_outputs(str(tmp_path / d), {"pixels": px, "depth": px[:, 0]}, cap_bytes=cap)
+    s1, s2 = np.load(tmp_path / "b" / "pixels.npy"), np.load(tmp_path / "c" / "pixels.npy")
+    assert s1.dtype == np.float32 and np.array_equal(s1, s2)
+    assert 4 * (s1.size + np.load(tmp_path / "b" / "depth.npy").size) <= cap
+    assert np.isin(s1, px.astype(np.float32)).all()
 
 
 def test_bench_launcher_propagates_failure():
