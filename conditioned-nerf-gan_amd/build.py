@@ -25,7 +25,7 @@ def build_library(force=False, verbose=False, extra_flags=()):
     hdrs = [os.path.join(CSRC, h) for h in HEADERS]
     objs, jobs = [], []
     # (source, object, extra defines): field_h3.hip and field_pw16.hip are compiled twice -- fp16x3 split kernels and the single-pass fp16 kernels
-    h1_defs = ("-DCNERF_H3_PARTS=1",) + tuple(os.environ.get("CNERF_H1_FLAGS", "").split())      # (experiments: e.g. -DCNERF_H3_OCC=2)
+    h1_defs = ("-DCNERF_H3_PARTS=1",)
     units = [(src, src.replace(".hip", ".o"), ()) for src in SOURCES] + [("field_h3.hip", "field_h1.o", h1_defs), ("field_pw16.hip", "field_pw1.o", h1_defs)]
     for src, obj, defs in units:
         s = os.path.join(CSRC, src)

@@ -238,6 +238,42 @@ void set_points(FieldArgs& a, int B, long long n_per_image) {
     a.total_tiles = a.tiles_per_image * B;
 }
 
+// FieldArgs of one field pass over images [image0, image0 + n_images) of the call: pass 0 = coarse samples (u_strat or NULL),
+// 1 = fine samples (fine_z), 2 = explicit points (B, R*R*S, 3) carried in u_strat.  The per-image inputs are the call's full tensors.
+int pass_args(FieldArgs& a, const cnerf_cfg* c, int pass, int image0, int n_images, const cnerf_volumes* vols, const cnerf_grad_volumes* gvols,
+              const float* packed, const float* freq, const float* phase, const float* cam2world, const float* u_strat, const float* fine_z) {
+    if (int rc = fill_field_args(a, c, vols, gvols, packed, freq, phase, image0)) return rc;
+    const long long npi = (long long)c->R * c->R * c->S;
+    set_points(a, n_images, npi);
+    a.cam2world = cam2world + (size_t)image0 * 16;
+    if (pass == 0) {
+        a.mode = FIELD_MODE_COARSE;
+        a.u_strat = u_strat ? u_strat + (size_t)image0 * npi : nullptr;
+    } else if (pass == 1) {
+        a.mode = FIELD_MODE_FINE;
+        a.fine_z = fine_z + (size_t)image0 * npi;
+    } else {
+        if (!u_strat) return fail(CNERF_EINVAL, "field_backward: pass 2 takes the points (B,R*R*S,3) in the u_strat argument");
+        a.mode = FIELD_MODE_POINTS;
+        a.points = u_strat + (size_t)image0 * npi * 3;
+    }
+    return CNERF_OK;
+}
+
+// the activation-storing re-run of a half-precision backward: the pass `a` again, storing fp16 TB16 activations (amax: per-point FiLM
+// family only); its head output goes to `scratch`, (n,4) floats nobody reads -- the chain overwrites that buffer entirely
+FieldArgs storing_args(const FieldArgs& a, long long n_points, void* feat, void* h, void* c, float* amax, void* scratch) {
+    FieldArgs s = a;
+    s.rgb_sigma = (float*)scratch;
+    s.act_points = n_points;
+    s.act_feat = (float*)feat;
+    s.act_h = (float*)h;
+    s.act_c = (float*)c;
+    s.act_amax = amax;
+    s.act_tb16 = 1;
+    return s;
+}
+
 }  // namespace
 
 extern "C" {
@@ -581,9 +617,6 @@ int cnerf_render_forward(const cnerf_cfg* cfg, const cnerf_volumes* vols, const 
     fa.rgb_sigma = c_rs;
     fa.z_out = c_z;
     fa.points_out = aux ? aux->coarse_points : nullptr;
-#ifdef CNERF_STAMPS
-    fa.stamps = aux ? (unsigned long long*)aux->cdf : nullptr;   // diagnostic build, non-hierarchical call: cdf slot is never written
-#endif
     auto mark = [&](int i) {
         if (aux && aux->field_events[i]) (void)hipEventRecord((hipEvent_t)aux->field_events[i], stream);
     };
@@ -720,22 +753,8 @@ int cnerf_field_backward(const cnerf_cfg* cfg, int32_t pass, int32_t image0, int
     const long long npi = (long long)cfg->R * cfg->R * cfg->S;
 
     FieldArgs fa;
-    if (int rc = fill_field_args(fa, cfg, vols, grad_vols, packed, freq, phase, image0)) return rc;
-    set_points(fa, n_images, npi);
-    fa.cam2world = cam2world + (size_t)image0 * 16;
-    if (pass == 0) {
-        fa.mode = FIELD_MODE_COARSE;
-        fa.u_strat = u_strat ? u_strat + (size_t)image0 * npi : nullptr;
-    } else if (pass == 1) {
-        fa.mode = FIELD_MODE_FINE;
-        fa.fine_z = fine_z + (size_t)image0 * npi;
-    } else {
-        if (!u_strat) return fail(CNERF_EINVAL, "field_backward: pass 2 takes the points (B,R*R*S,3) in the u_strat argument");
-        fa.mode = FIELD_MODE_POINTS;
-        fa.points = u_strat + (size_t)image0 * npi * 3;
-    }
+    if (int rc = pass_args(fa, cfg, pass, image0, n_images, vols, grad_vols, packed, freq, phase, cam2world, u_strat, fine_z)) return rc;
     fa.rgb_sigma = act_go;          // the re-run forward needs somewhere to put its head output: overwritten below by go'
-    fa.z_out = nullptr;
     fa.act_points = (long long)n_images * npi;
     fa.act_feat = act_feat;
     fa.act_h = act_h;
@@ -875,101 +894,6 @@ int cnerf_pack_field_chain16(const cnerf_cfg* cfg, const cnerf_field_params* p, 
     return CNERF_OK;
 }
 
-namespace {
-int field_backward16_impl(const cnerf_cfg* cfg, uint32_t mode, int32_t group_step, int32_t pass, int32_t image0, int32_t n_images,
-                          const cnerf_volumes* vols, const float* packed, const void* packed16, const float* freq,
-                          const float* phase, const float* cam2world, const float* u_strat, const float* fine_z,
-                          const float* grad_rgb_sigma, const float* saved_rgb_sigma, void* act_feat16, void* act_h16, void* act_c16,
-                          void* act_g16, void* act_go16, const float* scales, uint32_t* gmax, const cnerf_grad_volumes* grad_vols,
-                          uint32_t* sat, float* gin, void* stream_) {
-    g_err[0] = 0;
-    if (int rc = check_cfg(cfg, true)) return rc;
-    Chain16Layout l;
-    if (int rc = chain16_layout(cfg, l)) return rc;
-    if (cfg->precision != CNERF_PREC_FP16X3) return fail(CNERF_EINVAL, "field_backward16: cfg->precision must be CNERF_PREC_FP16X3 (the re-run forward is that kernel)");
-    if (image0 < 0 || n_images < 1 || image0 + n_images > cfg->B) return fail(CNERF_EINVAL, "field_backward16: image range out of [0,B)");
-    if (pass < 0 || pass > 2) return fail(CNERF_EINVAL, "field_backward16: pass must be 0 (coarse), 1 (fine) or 2 (explicit points)");
-    if (!(mode & (CNERF_B16_STORE | CNERF_B16_DRY | CNERF_B16_CHAIN))) return fail(CNERF_EINVAL, "field_backward16: empty mode");
-    if (!vols || !packed || !packed16 || !cam2world || !act_feat16 || !act_h16 || !act_c16 || !scales)
-        return fail(CNERF_EINVAL, "field_backward16: NULL argument");
-    if ((mode & (CNERF_B16_DRY | CNERF_B16_CHAIN)) && (!grad_rgb_sigma || !saved_rgb_sigma)) return fail(CNERF_EINVAL, "field_backward16: the chain needs grad / saved rgb_sigma");
-    if ((mode & CNERF_B16_DRY) && !gmax) return fail(CNERF_EINVAL, "field_backward16: the dry run needs gmax");
-    if ((mode & CNERF_B16_CHAIN) && (!act_g16 || !act_go16 || !grad_vols)) return fail(CNERF_EINVAL, "field_backward16: the chain needs act_g16, act_go16, grad_vols");
-    if (mode & CNERF_B16_CHAIN)
-        for (int i = 0; i < n_levels_of(cfg); ++i)
-            if (!grad_vols->level[i]) return fail(CNERF_EINVAL, "field_backward16: gradient volume %d is NULL", i);
-    if (pass == 1 && !fine_z) return fail(CNERF_EINVAL, "field_backward16: the fine pass needs fine_z");
-    const PackedLayout pl = packed_layout(cfg);
-    if (pl.n_film && (!freq || !phase)) return fail(CNERF_EINVAL, "field_backward16: FiLM layers need freq and phase");
-    hipStream_t stream = (hipStream_t)stream_;
-    const long long npi = (long long)cfg->R * cfg->R * cfg->S;
-
-    FieldArgs fa;
-    if (int rc = fill_field_args(fa, cfg, vols, (mode & CNERF_B16_CHAIN) ? grad_vols : nullptr, packed, freq, phase, image0)) return rc;
-    set_points(fa, n_images, npi);
-    fa.cam2world = cam2world + (size_t)image0 * 16;
-    if (pass == 0) {
-        fa.mode = FIELD_MODE_COARSE;
-        fa.u_strat = u_strat ? u_strat + (size_t)image0 * npi : nullptr;
-    } else if (pass == 1) {
-        fa.mode = FIELD_MODE_FINE;
-        fa.fine_z = fine_z + (size_t)image0 * npi;
-    } else {
-        if (!u_strat) return fail(CNERF_EINVAL, "field_backward16: pass 2 takes the points (B,R*R*S,3) in the u_strat argument");
-        fa.mode = FIELD_MODE_POINTS;
-        fa.points = u_strat + (size_t)image0 * npi * 3;
-    }
-    const char* base16 = (const char*)packed16;
-    if (mode & CNERF_B16_STORE) {
-        if (!act_g16) return fail(CNERF_EINVAL, "field_backward16: the storing re-run uses act_g16 as scratch for its head output");
-        FieldArgs fs = fa;
-        fs.rgb_sigma = (float*)act_g16;      // (n,4) floats of head output nobody reads; the chain overwrites act_g16 entirely
-        fs.z_out = nullptr;
-        fs.act_points = (long long)n_images * npi;
-        fs.act_feat = (float*)act_feat16;
-        fs.act_h = (float*)act_h16;
-        fs.act_c = (float*)act_c16;
-        fs.act_tb16 = 1;
-        if (hipError_t e = launch_field_h3(fs, cfg->H, stream)) return hip_fail(e, "field kernel (fp16 activation store)");
-    }
-    fa.grad_out = grad_rgb_sigma ? grad_rgb_sigma + (size_t)image0 * npi * 4 : nullptr;
-    fa.saved_out = saved_rgb_sigma ? saved_rgb_sigma + (size_t)image0 * npi * 4 : nullptr;
-    const float* winv = (const float*)(base16 + l.winv_off);
-    if (mode & CNERF_B16_DRY) {
-        if (hipError_t e = launch_chain16(fa, cfg->H, base16, base16 + l.head_off, winv, scales, act_c16, nullptr, nullptr, gmax, nullptr, l.n_mats, 1,
-                                          group_step < 1 ? 1 : group_step, stream))
-            return hip_fail(e, "chain16 (dry run)");
-    }
-    if (mode & CNERF_B16_CHAIN) {
-        // Ray passes: the chain stores its input-tile gradients (fp32, 128 B per point) and scatter_sorted_kernel adds them to the volume
-        // pre-reduced per pixel patch (scatter_patch.hip); explicit points are added by the chain itself.  CNERF_SCATTER=chain makes the
-        // chain add the ray passes' too, CNERF_SCATTER=coarse sends only the coarse pass through the patch kernel (A/B runs and
-        // tests/test_gpu_parity.py::test_sorted_patch_scatter_matches_the_chain_scatter; DESIGN.md 3.7 has the three timings).
-        const char* sc_env = getenv("CNERF_SCATTER");
-        const bool force_chain = sc_env && !strcmp(sc_env, "chain"), coarse_only = sc_env && !strcmp(sc_env, "coarse");
-        const bool patch = gin && pass != 2 && !force_chain && (pass == 0 || !coarse_only);
-        fa.gin = patch ? gin : nullptr;
-        if (hipError_t e = launch_chain16(fa, cfg->H, base16, base16 + l.head_off, winv, scales, act_c16, act_g16, act_go16, nullptr, sat, l.n_mats, 0, 1,
-                                          stream))
-            return hip_fail(e, "chain16");
-        if (patch)
-            if (hipError_t e = launch_scatter_patch(fa, gin, stream)) return hip_fail(e, "scatter_patch");
-    }
-    return CNERF_OK;
-}
-}  // namespace
-
-int cnerf_field_backward16(const cnerf_cfg* cfg, uint32_t mode, int32_t group_step, int32_t pass, int32_t image0, int32_t n_images,
-                           const cnerf_volumes* vols, const float* packed, const void* packed16, const float* freq,
-                           const float* phase, const float* cam2world, const float* u_strat, const float* fine_z,
-                           const float* grad_rgb_sigma, const float* saved_rgb_sigma, void* act_feat16, void* act_h16, void* act_c16,
-                           void* act_g16, void* act_go16, const float* scales, uint32_t* gmax, const cnerf_grad_volumes* grad_vols,
-                           void* stream_) {
-    return field_backward16_impl(cfg, mode, group_step, pass, image0, n_images, vols, packed, packed16, freq, phase, cam2world, u_strat, fine_z,
-                                 grad_rgb_sigma, saved_rgb_sigma, act_feat16, act_h16, act_c16, act_g16, act_go16, scales, gmax, grad_vols, nullptr,
-                                 nullptr, stream_);
-}
-
 // ---------------------------------------------------------------------------------------------------------------------
 // the whole backward in one call
 // ---------------------------------------------------------------------------------------------------------------------
@@ -1064,6 +988,39 @@ int backward_layout(const cnerf_cfg* c, int bprec, int cnt, bool have_act16, Bac
     L.total = off;
     return CNERF_OK;
 }
+
+// Scales of a half-precision chunk before its dry run: {1, 1} for slots 0 .. head - 1, slot `head` {S, 1 / S} from the largest
+// |d loss / d rgb_sigma| of the chunk (g_out, n floats), whose bit pattern lands in *gmax_head; the gmax_words maxima are zeroed first
+int head_scales(const float* g_out, long long n, uint32_t* gmax, size_t gmax_words, uint32_t* gmax_head, float* scales, int head, hipStream_t stream) {
+    if (hipError_t e = hipMemsetAsync(gmax, 0, gmax_words * sizeof(uint32_t), stream)) return hip_fail(e, "memset");
+    if (hipError_t e = launch_absmax_bits(g_out, n, gmax_head, stream)) return hip_fail(e, "absmax");
+    if (hipError_t e = launch_pow2_scales(gmax_head, 1, scales + 2 * head, stream)) return hip_fail(e, "pow2_scales");
+    for (int m = 0; m < head; ++m)
+        if (hipError_t e = launch_fill(scales + 2 * m, 1.0f, 2, stream)) return hip_fail(e, "fill");
+    return CNERF_OK;
+}
+
+// One weight reduction of a half-precision chunk (cnt images of tpi tiles): dw (cnt, n_rows, 32 x_ct) = G^T X and cs (cnt, n_rows) =
+// column sums of G per image (G: TB16, g_ct channel tiles, stored times 1 / *inv_scale), then param_reduce adds columns [k0, k0 + k_real)
+// to dW, db -- and, for a FiLM matrix, dfreq / dphase of the chunk's images
+int reduce16(int cnt, long long tpi, int n_rows, int g_ct, int x_ct, const void* G, const void* X, const float* inv_scale, float* dw, float* cs,
+             int k0, int k_real, const float* freq, int film_stride, const float* W, const float* b, float* dW, float* db, float* dfreq,
+             float* dphase, hipStream_t stream) {
+    if (hipError_t e = hipMemsetAsync(dw, 0, (size_t)cnt * n_rows * 32 * x_ct * sizeof(float), stream)) return hip_fail(e, "memset");
+    if (hipError_t e = hipMemsetAsync(cs, 0, (size_t)cnt * n_rows * sizeof(float), stream)) return hip_fail(e, "memset");
+    if (hipError_t e = launch_weight_grad16(cnt, tpi, n_rows, g_ct, x_ct, G, X, dw, cs, inv_scale, stream)) return hip_fail(e, "weight_grad16");
+    if (hipError_t e = launch_param_reduce(cnt, n_rows, 32 * x_ct, k_real, dw + k0, cs, freq, film_stride, W, b, dW, db, dfreq, dphase, stream))
+        return hip_fail(e, "param_reduce");
+    return CNERF_OK;
+}
+
+// Environment CNERF_SCATTER=chain: the half-precision chain adds the ray passes' feature-volume gradients with its own atomics instead of
+// scatter_sorted_kernel (A/B runs and tests/test_gpu_parity.py::test_sorted_patch_scatter_matches_the_chain_scatter, which switches it
+// within one process: read per call)
+bool scatter_by_chain() {
+    const char* s = getenv("CNERF_SCATTER");
+    return s && !strcmp(s, "chain");
+}
 }  // namespace
 
 int cnerf_backward_workspace_bytes(const cnerf_cfg* cfg, int32_t backward_precision, int32_t images_per_chunk, int32_t have_act16, size_t* bytes) {
@@ -1087,6 +1044,8 @@ int cnerf_render_backward(const cnerf_cfg* cfg, int32_t bprec, int32_t cnt_max, 
     if (int rc = backward_layout(cfg, bprec, cnt_max, have_act16, L)) return rc;
     if (!vols || !P || !packed || !packed_bwd || !cam2world || !saved || !grad_pixels || !G || !grad_vols || !workspace)
         return fail(CNERF_EINVAL, "render_backward: NULL argument");
+    for (int i = 0; i < n_levels_of(cfg); ++i)
+        if (!grad_vols->level[i]) return fail(CNERF_EINVAL, "render_backward: gradient volume %d is NULL", i);
     const bool hier = cfg->flags & CNERF_F_HIERARCHICAL;
     if (!saved->coarse_rgb_sigma || !saved->coarse_z || (hier && (!saved->fine_rgb_sigma || !saved->fine_z)))
         return fail(CNERF_EINVAL, "render_backward: saved rgb_sigma / z of the forward are incomplete");
@@ -1100,6 +1059,14 @@ int cnerf_render_backward(const cnerf_cfg* cfg, int32_t bprec, int32_t cnt_max, 
     char* ws = (char*)workspace;
     float* gc = (float*)(ws + L.gc);
     float* gf = hier ? (float*)(ws + L.gf) : nullptr;
+    float* dwarg = (float*)(ws + L.dwarg);
+    float* cs = (float*)(ws + L.cs);
+    float* dwh = (float*)(ws + L.dwh);
+    float* csh = (float*)(ws + L.csh);
+    uint32_t* gmax = (uint32_t*)(ws + L.gmax);
+    float* scales = (float*)(ws + L.scales);
+    char* a_g = ws + L.a_g;
+    char* a_go = ws + L.a_go;
 
     // 1. d(pixels, depth) -> d(rgb_sigma) of every coarse / fine sample
     if (int rc = cnerf_merge_composite_backward(cfg, saved->coarse_rgb_sigma, saved->coarse_z, saved->fine_rgb_sigma, saved->fine_z,
@@ -1117,14 +1084,6 @@ int cnerf_render_backward(const cnerf_cfg* cfg, int32_t bprec, int32_t cnt_max, 
             if (!G->w[l] || !G->b[l]) return fail(CNERF_EINVAL, "render_backward: gradient buffers of layer %d are NULL", l);
         const PwChainLayout cl = pw_chain_layout(cfg);
         const char* base16 = (const char*)packed_bwd;
-        float* dwarg = (float*)(ws + L.dwarg);
-        float* cs = (float*)(ws + L.cs);
-        float* dwh = (float*)(ws + L.dwh);
-        float* csh = (float*)(ws + L.csh);
-        uint32_t* gmax = (uint32_t*)(ws + L.gmax);
-        float* scales = (float*)(ws + L.scales);
-        char* a_g = ws + L.a_g;
-        char* a_go = ws + L.a_go;
         if (hipError_t e = hipMemsetAsync(a_go, 0, (size_t)cnt_max * tpi * 2048, stream)) return hip_fail(e, "memset");
         for (int pass = 0; pass < (hier ? 2 : 1); ++pass) {
             const float* g_out = pass ? gf : gc;
@@ -1139,36 +1098,13 @@ int cnerf_render_backward(const cnerf_cfg* cfg, int32_t bprec, int32_t cnt_max, 
                 float* a_amax = have_act16 ? (float*)kept->act16[pass].amax : (float*)(ws + L.a_amax);
                 if (have_act16 && (!a_feat || !a_h || !a_c || !a_amax)) return fail(CNERF_EINVAL, "render_backward: act16 of pass %d is incomplete", pass);
                 FieldArgs fa;
-                if (int rc = fill_field_args(fa, cfg, vols, grad_vols, packed, nullptr, nullptr, b0)) return rc;
-                if (!fa.lvl_grad[0]) return fail(CNERF_EINVAL, "render_backward: gradient volume is NULL");
-                set_points(fa, cnt, npi);
-                fa.cam2world = cam2world + (size_t)b0 * 16;
-                if (pass == 0) {
-                    fa.mode = FIELD_MODE_COARSE;
-                    fa.u_strat = rng->u_strat ? rng->u_strat + (size_t)b0 * npi : nullptr;
-                } else {
-                    fa.mode = FIELD_MODE_FINE;
-                    fa.fine_z = saved->fine_z + (size_t)b0 * npi;
-                }
-                if (!have_act16) {
-                    FieldArgs fs = fa;
-                    fs.rgb_sigma = (float*)a_g;      // (n,4) floats of head output nobody reads; the chain overwrites a_g entirely
-                    fs.z_out = nullptr;
-                    fs.act_points = (long long)cnt * npi;
-                    fs.act_feat = (float*)a_feat;
-                    fs.act_h = (float*)a_h;
-                    fs.act_c = (float*)a_c;
-                    fs.act_amax = a_amax;
-                    fs.act_tb16 = 1;
-                    if (hipError_t e = launch_field_pw3(fs, H, stream)) return hip_fail(e, "field kernel (fp16 activation store)");
-                }
+                if (int rc = pass_args(fa, cfg, pass, b0, cnt, vols, grad_vols, packed, nullptr, nullptr, cam2world, rng->u_strat, saved->fine_z)) return rc;
+                if (!have_act16)
+                    if (hipError_t e = launch_field_pw3(storing_args(fa, (long long)cnt * npi, a_feat, a_h, a_c, a_amax, a_g), H, stream))
+                        return hip_fail(e, "field kernel (fp16 activation store)");
                 fa.grad_out = g_out + (size_t)b0 * npi * 4;
                 fa.saved_out = s_out + (size_t)b0 * npi * 4;
-                if (hipError_t e = hipMemsetAsync(gmax, 0, (size_t)(5 * Lc + 2) * sizeof(uint32_t), stream)) return hip_fail(e, "memset");
-                if (hipError_t e = launch_absmax_bits(fa.grad_out, (long long)cnt * npi * 4, gmax + n_slots - 1, stream)) return hip_fail(e, "absmax");
-                if (hipError_t e = launch_pow2_scales(gmax + n_slots - 1, 1, scales + 2 * (n_slots - 1), stream)) return hip_fail(e, "pow2_scales");
-                for (int m = 0; m < n_slots - 1; ++m)
-                    if (hipError_t e = launch_fill(scales + 2 * m, 1.0f, 2, stream)) return hip_fail(e, "fill");
+                if (int rc = head_scales(fa.grad_out, (long long)cnt * npi * 4, gmax, 5 * Lc + 2, gmax + n_slots - 1, scales, n_slots - 1, stream)) return rc;
                 const size_t slabH = (size_t)T * NT * 2048;            // bytes per (tiles, NT, 32, 32) slab
                 float* lay = scales + 2 * (4 * Lc + 2);
                 PwChainBuffers cb{base16, base16 + cl.m_off, base16 + cl.head_off, (const float*)(base16 + cl.winv_off), (const float*)(base16 + cl.anorm_off),
@@ -1191,14 +1127,10 @@ int cnerf_render_backward(const cnerf_cfg* cfg, int32_t bprec, int32_t cnt_max, 
                 if (hipError_t e = launch_pow2_scales(gmax + 3 * Lc, 1, scales + 2 * (3 * Lc), stream)) return hip_fail(e, "pow2_scales");
                 cb.sat = saturated;
                 if (hipError_t e = launch_pw_gm(fa, H, cb, 0, 1, stream)) return hip_fail(e, "pw_gm");
-                // one reduction: G (n_rows of slab `slot`) against X (x_ct channel tiles), take k_real columns from column k0 on
-                auto reduce = [&](const void* Gs, int g_ct, int n_rows, int slot, const void* X, int x_ct, int k0, int k_real, float* dW, float* db) -> int {
-                    if (hipError_t e = hipMemsetAsync(dwarg, 0, (size_t)cnt * n_rows * 32 * x_ct * sizeof(float), stream)) return hip_fail(e, "memset");
-                    if (hipError_t e = hipMemsetAsync(cs, 0, (size_t)cnt * n_rows * sizeof(float), stream)) return hip_fail(e, "memset");
-                    if (int rc = cnerf_weight_grad16(cnt, tpi, n_rows, g_ct, x_ct, Gs, X, dwarg, cs, scales + 2 * slot + 1, stream_)) return rc;
-                    if (hipError_t e = launch_param_reduce(cnt, n_rows, 32 * x_ct, k_real, dwarg + k0, cs, nullptr, 0, nullptr, nullptr, dW, db, nullptr, nullptr, stream))
-                        return hip_fail(e, "param_reduce");
-                    return CNERF_OK;
+                // one reduction per matrix: G (n_rows of slab `slot`) against X (x_ct channel tiles), k_real columns from column k0 on
+                auto reduce = [&](const void* Gs, int g_ct, int n_rows, int slot, const void* X, int x_ct, int k0, int k_real, float* dW, float* db) {
+                    return reduce16(cnt, tpi, n_rows, g_ct, x_ct, Gs, X, scales + 2 * slot + 1, dwarg, cs, k0, k_real, nullptr, 0, nullptr, nullptr, dW, db,
+                                    nullptr, nullptr, stream);
                 };
                 const char* m16 = a_h + (size_t)Lc * slabH;
                 const size_t LH = (size_t)Lc * H;
@@ -1214,11 +1146,9 @@ int cnerf_render_backward(const cnerf_cfg* cfg, int32_t bprec, int32_t cnt_max, 
                         return rc;
                 }
                 if (int rc = reduce(a_g + (size_t)(3 * Lc) * slabH, 8, 256, 3 * Lc, a_feat, 2, 0, 32, G->map_w1, G->map_b1)) return rc;
-                if (hipError_t e = hipMemsetAsync(dwh, 0, (size_t)cnt * 4 * H * sizeof(float), stream)) return hip_fail(e, "memset");
-                if (hipError_t e = hipMemsetAsync(csh, 0, (size_t)cnt * 4 * sizeof(float), stream)) return hip_fail(e, "memset");
-                if (int rc = cnerf_weight_grad16(cnt, tpi, 4, 1, NT, a_go, a_h + (size_t)(Lc - 1) * slabH, dwh, csh, scales + 2 * (n_slots - 1) + 1, stream_)) return rc;
-                if (hipError_t e = launch_param_reduce(cnt, 4, H, H, dwh, csh, nullptr, 0, nullptr, nullptr, G->w_final, G->b_final, nullptr, nullptr, stream))
-                    return hip_fail(e, "param_reduce (head)");
+                if (int rc = reduce16(cnt, tpi, 4, 1, NT, a_go, a_h + (size_t)(Lc - 1) * slabH, scales + 2 * (n_slots - 1) + 1, dwh, csh, 0, H, nullptr, 0,
+                                      nullptr, nullptr, G->w_final, G->b_final, nullptr, nullptr, stream))
+                    return rc;
             }
         }
         return CNERF_OK;
@@ -1242,92 +1172,99 @@ int cnerf_render_backward(const cnerf_cfg* cfg, int32_t bprec, int32_t cnt_max, 
         }
     }
     const int film_stride = pl.n_film * H;
-    float* dwarg = (float*)(ws + L.dwarg);
-    float* cs = (float*)(ws + L.cs);
-    float* dwh = (float*)(ws + L.dwh);
-    float* csh = (float*)(ws + L.csh);
-    uint32_t* gmax = (uint32_t*)(ws + L.gmax);
-    float* scales = (float*)(ws + L.scales);
-    void* a_g = ws + L.a_g;
-    void* a_go = ws + L.a_go;
-    if (bprec == CNERF_PREC_FP16)        // only channels 0..3 of a row are ever written: the rest must read as zero
+    // matrix m's slice of freq / grad_freq / grad_phase for the chunk from image b0 (NULL unless m is a FiLM matrix)
+    auto film = [&](auto* t, int m, int b0) { return film_of[m] >= 0 ? t + (size_t)b0 * film_stride + (size_t)film_of[m] * H : nullptr; };
+
+    if (bprec == CNERF_PREC_FP16) {
+        // ---- FiLM / plain-sine / residual networks, half-precision backward (bwd16.hip): per chunk the storing re-run (fp16x3 kernel), the
+        // chain's dry run for the per-matrix scales, the chain, the patch scatter of the input-tile gradients, one weight_grad16 per matrix
+        Chain16Layout cl;
+        if (int rc = chain16_layout(cfg, cl)) return rc;
+        const char* base16 = (const char*)packed_bwd;
+        const float* winv = (const float*)(base16 + cl.winv_off);
+        float* gin = (float*)(ws + L.a_gin);
+        const bool patch = !scatter_by_chain();
+        // only channels 0..3 of a row are ever written: the rest must read as zero
         if (hipError_t e = hipMemsetAsync(a_go, 0, (size_t)cnt_max * tpi * 2048, stream)) return hip_fail(e, "memset");
-
-    // reduce one matrix' per-image sums into the parameter gradients (and dfreq / dphase of the chunk's images)
-    auto reduce_matrix = [&](int m, int cnt, int b0, int ld) -> int {
-        const int k_real = m == 0 ? L.k0 : H;
-        const bool film = film_of[m] >= 0;
-        const size_t foff = film ? (size_t)b0 * film_stride + (size_t)film_of[m] * H : 0;
-        if (hipError_t e = launch_param_reduce(cnt, H, ld, k_real, dwarg, cs, film ? freq + foff : nullptr, film_stride, Wm[m], bm[m], dWm[m], dbm[m],
-                                               film ? grad_freq + foff : nullptr, film ? grad_phase + foff : nullptr, stream))
-            return hip_fail(e, "param_reduce");
+        for (int pass = 0; pass < (hier ? 2 : 1); ++pass) {
+            const float* g_out = pass ? gf : gc;
+            const float* s_out = pass ? saved->fine_rgb_sigma : saved->coarse_rgb_sigma;
+            for (int b0 = 0; b0 < B; b0 += cnt_max) {
+                const int cnt = b0 + cnt_max <= B ? cnt_max : B - b0;
+                const long long T = (long long)cnt * tpi;
+                void* a_feat = have_act16 ? kept->act16[pass].feat : (void*)(ws + L.a_feat);
+                void* a_h = have_act16 ? kept->act16[pass].h : (void*)(ws + L.a_h);
+                void* a_c = have_act16 ? kept->act16[pass].c : (void*)(ws + L.a_c);
+                if (have_act16 && (!a_feat || !a_h || !a_c)) return fail(CNERF_EINVAL, "render_backward: act16 of pass %d is incomplete", pass);
+                if (int rc = head_scales(g_out + (size_t)b0 * npi * 4, (long long)cnt * npi * 4, gmax, L.n_mats + 2, gmax + L.n_mats + 1, scales, L.n_mats,
+                                         stream))
+                    return rc;
+                const long long groups = (long long)cnt * ((tpi + 3) / 4);
+                long long step = groups / 2048;                       // dry-run sampling: every 16th tile group once there are plenty
+                step = step < 1 ? 1 : (step > 16 ? 16 : step);
+                // the storing re-run and the dry run leave the gradient volumes alone; the chain (fc) adds to them
+                FieldArgs fa, fc;
+                if (int rc = pass_args(fa, cfg, pass, b0, cnt, vols, nullptr, packed, freq, phase, cam2world, rng->u_strat, saved->fine_z)) return rc;
+                if (int rc = pass_args(fc, cfg, pass, b0, cnt, vols, grad_vols, packed, freq, phase, cam2world, rng->u_strat, saved->fine_z)) return rc;
+                if (!have_act16)
+                    if (hipError_t e = launch_field_h3(storing_args(fa, (long long)cnt * npi, a_feat, a_h, a_c, nullptr, a_g), H, stream))
+                        return hip_fail(e, "field kernel (fp16 activation store)");
+                fa.grad_out = fc.grad_out = g_out + (size_t)b0 * npi * 4;
+                fa.saved_out = fc.saved_out = s_out + (size_t)b0 * npi * 4;
+                if (hipError_t e = launch_chain16(fa, H, base16, base16 + cl.head_off, winv, scales, a_c, nullptr, nullptr, gmax, nullptr, cl.n_mats, 1, (int)step,
+                                                  stream))
+                    return hip_fail(e, "chain16 (dry run)");
+                if (hipError_t e = launch_pow2_scales(gmax, L.n_mats, scales, stream)) return hip_fail(e, "pow2_scales");
+                // the chain stores its input-tile gradients (fp32, 128 B per point) and scatter_sorted_kernel adds them to the volume pre-reduced
+                // per pixel patch (scatter_patch.hip), or the chain adds them itself (CNERF_SCATTER=chain)
+                fc.gin = patch ? gin : nullptr;
+                if (hipError_t e = launch_chain16(fc, H, base16, base16 + cl.head_off, winv, scales, a_c, a_g, a_go, nullptr, saturated, cl.n_mats, 0, 1, stream))
+                    return hip_fail(e, "chain16");
+                if (patch)
+                    if (hipError_t e = launch_scatter_patch(fc, gin, stream)) return hip_fail(e, "scatter_patch");
+                const size_t slab = (size_t)T * NT * 2048;             // bytes per matrix in a_h / a_g
+                for (int m = 0; m < L.n_mats; ++m) {
+                    const int x_ct = m == 0 ? L.n_in : NT;
+                    const void* X = m == 0 ? a_feat : (const void*)((const char*)a_h + (size_t)(m - 1) * slab);
+                    if (int rc = reduce16(cnt, tpi, H, NT, x_ct, a_g + (size_t)m * slab, X, scales + 2 * m + 1, dwarg, cs, 0, m == 0 ? L.k0 : H, film(freq, m, b0),
+                                          film_stride, Wm[m], bm[m], dWm[m], dbm[m], film(grad_freq, m, b0), film(grad_phase, m, b0), stream))
+                        return rc;
+                }
+                if (int rc = reduce16(cnt, tpi, 4, 1, NT, a_go, (const char*)a_h + (size_t)(L.n_mats - 1) * slab, scales + 2 * L.n_mats + 1, dwh, csh, 0, H,
+                                      nullptr, 0, nullptr, nullptr, G->w_final, G->b_final, nullptr, nullptr, stream))
+                    return rc;
+            }
+        }
         return CNERF_OK;
-    };
+    }
 
+    // ---- exact fp32 backward: per chunk cnerf_field_backward (re-run in cfg->precision, fp32 chain, scatter), one weight_grad per matrix
     for (int pass = 0; pass < (hier ? 2 : 1); ++pass) {
         const float* g_out = pass ? gf : gc;
         const float* s_out = pass ? saved->fine_rgb_sigma : saved->coarse_rgb_sigma;
         const uint8_t* drop = pass ? rng->drop_fine : rng->drop_coarse;
         for (int b0 = 0; b0 < B; b0 += cnt_max) {
             const int cnt = b0 + cnt_max <= B ? cnt_max : B - b0;
-            if (bprec == CNERF_PREC_FP16) {
-                const long long T = (long long)cnt * tpi;
-                void* a_feat = have_act16 ? kept->act16[pass].feat : (void*)(ws + L.a_feat);
-                void* a_h = have_act16 ? kept->act16[pass].h : (void*)(ws + L.a_h);
-                void* a_c = have_act16 ? kept->act16[pass].c : (void*)(ws + L.a_c);
-                if (have_act16 && (!a_feat || !a_h || !a_c)) return fail(CNERF_EINVAL, "render_backward: act16 of pass %d is incomplete", pass);
-                // scales: ones for the matrices during the dry run, the head gradient's from max |d loss / d rgb_sigma| of the chunk
-                if (hipError_t e = hipMemsetAsync(gmax, 0, (size_t)(L.n_mats + 2) * sizeof(uint32_t), stream)) return hip_fail(e, "memset");
-                if (hipError_t e = launch_absmax_bits(g_out + (size_t)b0 * npi * 4, (long long)cnt * npi * 4, gmax + L.n_mats + 1, stream)) return hip_fail(e, "absmax");
-                if (hipError_t e = launch_pow2_scales(gmax + L.n_mats + 1, 1, scales + 2 * L.n_mats, stream)) return hip_fail(e, "pow2_scales");
-                for (int m = 0; m < L.n_mats; ++m)
-                    if (hipError_t e = launch_fill(scales + 2 * m, 1.0f, 2, stream)) return hip_fail(e, "fill");
-                const long long groups = (long long)cnt * ((tpi + 3) / 4);
-                long long step = groups / 2048;                       // dry-run sampling: every 16th tile group once there are plenty
-                step = step < 1 ? 1 : (step > 16 ? 16 : step);
-                if (int rc = field_backward16_impl(cfg, (have_act16 ? 0u : CNERF_B16_STORE) | CNERF_B16_DRY, (int)step, pass, b0, cnt, vols, packed, packed_bwd,
-                                                   freq, phase, cam2world, rng->u_strat, saved->fine_z, g_out, s_out, a_feat, a_h, a_c, a_g, a_go, scales, gmax,
-                                                   grad_vols, nullptr, nullptr, stream_))
-                    return rc;
-                if (hipError_t e = launch_pow2_scales(gmax, L.n_mats, scales, stream)) return hip_fail(e, "pow2_scales");
-                if (int rc = field_backward16_impl(cfg, CNERF_B16_CHAIN, 1, pass, b0, cnt, vols, packed, packed_bwd, freq, phase, cam2world, rng->u_strat,
-                                                   saved->fine_z, g_out, s_out, a_feat, a_h, a_c, a_g, a_go, scales, gmax, grad_vols, saturated, (float*)(ws + L.a_gin), stream_))
-                    return rc;
-                const size_t slab = (size_t)T * NT * 2048;             // bytes per matrix in a_h / a_g
-                for (int m = 0; m < L.n_mats; ++m) {
-                    const int x_ct = m == 0 ? L.n_in : NT;
-                    const void* X = m == 0 ? a_feat : (const void*)((const char*)a_h + (size_t)(m - 1) * slab);
-                    if (hipError_t e = hipMemsetAsync(dwarg, 0, (size_t)cnt * H * 32 * x_ct * sizeof(float), stream)) return hip_fail(e, "memset");
-                    if (hipError_t e = hipMemsetAsync(cs, 0, (size_t)cnt * H * sizeof(float), stream)) return hip_fail(e, "memset");
-                    if (int rc = cnerf_weight_grad16(cnt, tpi, H, NT, x_ct, (const char*)a_g + (size_t)m * slab, X, dwarg, cs, scales + 2 * m + 1, stream_)) return rc;
-                    if (int rc = reduce_matrix(m, cnt, b0, 32 * x_ct)) return rc;
-                }
-                if (hipError_t e = hipMemsetAsync(dwh, 0, (size_t)cnt * 4 * H * sizeof(float), stream)) return hip_fail(e, "memset");
-                if (hipError_t e = hipMemsetAsync(csh, 0, (size_t)cnt * 4 * sizeof(float), stream)) return hip_fail(e, "memset");
-                if (int rc = cnerf_weight_grad16(cnt, tpi, 4, 1, NT, a_go, (const char*)a_h + (size_t)(L.n_mats - 1) * slab, dwh, csh, scales + 2 * L.n_mats + 1, stream_))
-                    return rc;
-                if (hipError_t e = launch_param_reduce(cnt, 4, H, H, dwh, csh, nullptr, 0, nullptr, nullptr, G->w_final, G->b_final, nullptr, nullptr, stream))
-                    return hip_fail(e, "param_reduce (head)");
-            } else {
-                const size_t n = (size_t)cnt * npi;
-                float* a_feat = (float*)(ws + L.a_feat);
-                float* a_h = (float*)(ws + L.a_h);
-                float* a_c = (float*)(ws + L.a_c);
-                if (int rc = cnerf_field_backward(cfg, pass, b0, cnt, vols, packed, (const float*)packed_bwd, freq, phase, cam2world, rng->u_strat, saved->fine_z,
-                                                  g_out, s_out, a_feat, a_h, a_c, (float*)a_g, (float*)a_go, grad_vols, drop, stream_))
-                    return rc;
-                for (int m = 0; m < L.n_mats; ++m) {
-                    const int K = m == 0 ? 32 * L.n_in : H;
-                    const float* X = m == 0 ? a_feat : a_h + (size_t)(m - 1) * n * H;
-                    if (hipError_t e = hipMemsetAsync(dwarg, 0, (size_t)cnt * H * K * sizeof(float), stream)) return hip_fail(e, "memset");
-                    if (hipError_t e = hipMemsetAsync(cs, 0, (size_t)cnt * H * sizeof(float), stream)) return hip_fail(e, "memset");
-                    if (int rc = cnerf_weight_grad(cnt, npi, H, K, (const float*)a_g + (size_t)m * n * H, X, dwarg, cs, stream_)) return rc;
-                    if (int rc = reduce_matrix(m, cnt, b0, K)) return rc;
-                }
-                if (G->w_final && G->b_final)
-                    if (hipError_t e = launch_head_grad32((const float*)a_go, a_h + (size_t)(L.n_mats - 1) * n * H, (long long)n, H, G->w_final, G->b_final, stream))
-                        return hip_fail(e, "head_grad32");
+            const size_t n = (size_t)cnt * npi;
+            float* a_feat = (float*)(ws + L.a_feat);
+            float* a_h = (float*)(ws + L.a_h);
+            float* a_c = (float*)(ws + L.a_c);
+            if (int rc = cnerf_field_backward(cfg, pass, b0, cnt, vols, packed, (const float*)packed_bwd, freq, phase, cam2world, rng->u_strat, saved->fine_z,
+                                              g_out, s_out, a_feat, a_h, a_c, (float*)a_g, (float*)a_go, grad_vols, drop, stream_))
+                return rc;
+            for (int m = 0; m < L.n_mats; ++m) {
+                const int K = m == 0 ? 32 * L.n_in : H;
+                const float* X = m == 0 ? a_feat : a_h + (size_t)(m - 1) * n * H;
+                if (hipError_t e = hipMemsetAsync(dwarg, 0, (size_t)cnt * H * K * sizeof(float), stream)) return hip_fail(e, "memset");
+                if (hipError_t e = hipMemsetAsync(cs, 0, (size_t)cnt * H * sizeof(float), stream)) return hip_fail(e, "memset");
+                if (int rc = cnerf_weight_grad(cnt, npi, H, K, (const float*)a_g + (size_t)m * n * H, X, dwarg, cs, stream_)) return rc;
+                if (hipError_t e = launch_param_reduce(cnt, H, K, m == 0 ? L.k0 : H, dwarg, cs, film(freq, m, b0), film_stride, Wm[m], bm[m], dWm[m], dbm[m],
+                                                       film(grad_freq, m, b0), film(grad_phase, m, b0), stream))
+                    return hip_fail(e, "param_reduce");
             }
+            if (G->w_final && G->b_final)
+                if (hipError_t e = launch_head_grad32((const float*)a_go, a_h + (size_t)(L.n_mats - 1) * n * H, (long long)n, H, G->w_final, G->b_final, stream))
+                    return hip_fail(e, "head_grad32");
         }
     }
     return CNERF_OK;

@@ -32,7 +32,9 @@ struct FieldArgs {
     float* rgb_sigma;        // (B,n,4)
     float* z_out;            // mode COARSE: (B,n)
     float* points_out;       // optional (B,n,3)
-    unsigned long long* stamps;  // diagnostic builds (-DCNERF_STAMPS) only: 8 cycle totals; else unused
+    void* unused;            // never read: keeps the argument layout the kernels were tuned in (dropping these 8 bytes moves every later
+                             // field off its 16-byte alignment; the compiler then groups the argument loads differently and 18 of the
+                             // field kernels change their spills, e.g. the fp32 activation-storing re-run at H = 256 from 0 to 68 bytes)
     // activation store of the backward pass (all null in a plain forward): row-major [point][channel]
     long long act_points;    // rows of every activation buffer (= B * n_per_image of the chunk)
     float* act_feat;         // (n,32*n_in) layer-0 input tiles (looked-up features, xyz)

@@ -487,20 +487,6 @@ __device__ __forceinline__ void h3_layer0_from_lds(const f16x8* lds_unit, const 
     }
 }
 
-#ifdef CNERF_STAMPS
-// Diagnostic build only: per-phase s_memtime totals summed over all tiles of all waves into a.stamps[0..7].
-#define BSTAMP(i)                                                                                    \
-    do {                                                                                             \
-        __builtin_amdgcn_sched_barrier(0);                                                           \
-        const unsigned long long now_ = __builtin_readcyclecounter();                                \
-        __builtin_amdgcn_sched_barrier(0);                                                           \
-        st_[i] += now_ - last_;                                                                      \
-        last_ = now_;                                                                                \
-    } while (0)
-#else
-#define BSTAMP(i)
-#endif
-
 template <int N>
 struct Younger { static constexpr int value = N; };            // compile-time tag of unit_begin() in the kernel
 struct ResidNo { static constexpr bool value = false; };      // compile-time tags for the `matrix` lambda of the kernel
@@ -526,10 +512,6 @@ __device__ __forceinline__ TilePoint tile_of_group(const FieldArgs& a, long long
 // two-waves-per-tile variant of this kernel -- 11.7 vs 10.9 ms)
 template <int NT, int STORE, bool HAS_RES, int WF>
 __global__ __launch_bounds__(256) void field_h3_kernel(FieldArgs a) {
-#ifdef CNERF_STAMPS
-    unsigned long long st_[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    unsigned long long last_ = __builtin_readcyclecounter();
-#endif
     extern __shared__ __attribute__((aligned(16))) char smem[];
     constexpr int UNIT_FR = H3Lds<NT>::FRAGS;
     constexpr int H = NT * 32;
@@ -626,7 +608,6 @@ __global__ __launch_bounds__(256) void field_h3_kernel(FieldArgs a) {
         const int b = tp.b;
         const long long nn = tp.nn;
         const bool valid = tp.valid;
-        BSTAMP(0);
         if (WF && b != staged_b) {                            // block-uniform: this image's accumulator starts K' S' and its 1 / S' per matrix
             __syncthreads();                                        // nobody still reads the previous image's constants
             const float* fsrc = a.fold + (size_t)(b + a.image0) * (a.n_mats * (H + 1));
@@ -667,7 +648,6 @@ __global__ __launch_bounds__(256) void field_h3_kernel(FieldArgs a) {
         const TilePoint tn = tile_of_group(a, has_next ? g + blk_per_cls : g, G, wave, j);
         const TileRaw raw_next = tile_point_fetch(a, tn.b, tn.nn);
         if (WF) next_base = img_units + (size_t)(tn.b + a.image0) * img_stride;
-        BSTAMP(1);
 
         const float* bias = lds_bias;
         const float* lfr = lds_freq;
@@ -724,7 +704,6 @@ __global__ __launch_bounds__(256) void field_h3_kernel(FieldArgs a) {
                 f2[1] = split8_clamped(fv + 8);
                 h3_layer0_from_lds<NT>(unit, f2, acc0, lane);
             }
-            BSTAMP(2);
             const bool film = a.layer_kind[0] == CNERF_LAYER_FILM;
             const float inv_s = WF ? lds_mh[0] : lds_inv_s[0];
 #pragma unroll
@@ -745,7 +724,6 @@ __global__ __launch_bounds__(256) void field_h3_kernel(FieldArgs a) {
                 lph += H;
             }
         }
-        BSTAMP(3);
         // ---- hidden layers: NT weight units per matrix -------------------------------------------------------------------
         // One matrix: out[t] = epilogue(W[t] in) for the NT output tiles, the epilogue of tile t-1 pipelined under the MFMAs
         // of tile t.  RESID: `out` is the residual block's input x and is updated in place.
@@ -819,7 +797,6 @@ __global__ __launch_bounds__(256) void field_h3_kernel(FieldArgs a) {
                 }
             }
         }
-        BSTAMP(4);
         // ---- head (last unit of the sequence).  Behind its barrier: layer-0 unit 0 streams in for the next group, the
         // next tile's position is finished and its 32 lookups are issued -- they fly under the head's MFMAs.
         {
@@ -849,14 +826,9 @@ __global__ __launch_bounds__(256) void field_h3_kernel(FieldArgs a) {
             pz = nz;
             tp = tn;
         }
-        BSTAMP(5);
     }
     wait_vmcnt<0>();                                                 // drain the copies issued for tiles this block does not have: an LDS-DMA
     __syncthreads();                                                 // write must not land after the block has given its LDS back
-#ifdef CNERF_STAMPS
-    if (a.stamps && lane == 0)
-        for (int i = 0; i < 8; ++i) atomicAdd(a.stamps + i, st_[i]);
-#endif
 }
 
 constexpr size_t LDS_LIMIT = 160 * 1024;

@@ -71,10 +71,7 @@ struct Act {
 // that consumes them, across output-tile boundaries and epilogues, so the L2 latency is hidden behind the matrix pipe.
 // Everything is unrolled: register indices of the ring, the B operands and the accumulators are compile-time.
 // ---------------------------------------------------------------------------------------------------------------
-#ifndef CNERF_RING
-#define CNERF_RING 6
-#endif
-constexpr int RING = CNERF_RING;
+constexpr int RING = 6;
 
 // Forward epilogue sine.  v_sin_f32 behind an exact reduction by 2 pi (max abs error 3.8e-7, scripts/ubench/vsin_accuracy.hip)
 // instead of the 12-op polynomial (1.2e-7) is +1.7 % throughput, but on this exact path it pushes one random-input parity
@@ -296,20 +293,6 @@ __device__ __forceinline__ void film_all(const f32x16* y, f32x16* x, const float
     }
 }
 
-#ifdef CNERF_STAMPS
-// Diagnostic build only: per-phase cycle totals (s_memtime) summed over all tiles of all waves into a.stamps[0..7].
-#define STAMP(i)                                                                                     \
-    do {                                                                                             \
-        __builtin_amdgcn_sched_barrier(0);                                                           \
-        const unsigned long long now_ = __builtin_readcyclecounter();                                \
-        __builtin_amdgcn_sched_barrier(0);                                                           \
-        st_[i] += now_ - last_;                                                                      \
-        last_ = now_;                                                                                \
-    } while (0)
-#else
-#define STAMP(i)
-#endif
-
 // Measured on one MI355X (bench.py, batch 8): parking the next tile's lookups in LDS by DMA removes 7.4 k cycles of wait
 // from layer 0 but the 32 scattered global_load_lds instructions cost 8.6 k cycles to issue in the head (~200 cycles each:
 // M0 rewrite + 32 distinct lines per instruction), a net loss of 0.5 %; only the one-tile-ahead fetch of the raw sample
@@ -317,10 +300,6 @@ __device__ __forceinline__ void film_all(const f32x16* y, f32x16* x, const float
 
 template <int NT, bool HAS_RES, bool STORE, bool DROP, bool FOLD = false, int WFOLD = 0>
 __global__ __launch_bounds__(256) void field_tile_kernel(FieldArgs a) {
-#ifdef CNERF_STAMPS
-    unsigned long long st_[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    unsigned long long last_ = __builtin_readcyclecounter();
-#endif
     const int lane = threadIdx.x & 63;
     const int j = lane & 31, h = lane >> 5;
     constexpr int H = NT * 32;
@@ -351,7 +330,6 @@ __global__ __launch_bounds__(256) void field_tile_kernel(FieldArgs a) {
         tile_point(a, b, nn, valid, h, true, px, py, pz);
     }
     for (long long tile = tr.begin; tile < tr.end; tile += tr.stride) {
-        STAMP(0);   // loop overhead / previous store
         // raw sample coordinate of the next tile of this wave (this tile again at the end of the range)
         const bool has_next = tile + tr.stride < tr.end;
         int nb;
@@ -397,7 +375,6 @@ __global__ __launch_bounds__(256) void field_tile_kernel(FieldArgs a) {
             }
             layer0_accumulate<NT>(wp, a.n_in, tk, feat, y.v, lane);
         }
-        STAMP(1);   // position + lookups + layer-0 products
         {
             const bool film = a.layer_kind[0] == CNERF_LAYER_FILM;
             film_all<NT, STORE, DROP, FOLD, WFOLD>(y.v, x.v, (FOLD || film) ? freq : ones, (FOLD || film) ? phase : zeros, h, row_h, row_c, &a, drop_gp, fml);
@@ -414,7 +391,6 @@ __global__ __launch_bounds__(256) void field_tile_kernel(FieldArgs a) {
             }
         }
         asm volatile("" :: "v"(x.v[0][0]), "v"(x.v[NT - 1][15]));
-        STAMP(2);   // layer 0 epilogue
         for (int l = 1; l < a.L; ++l) {
             const int kind = a.layer_kind[l];
             if (!HAS_RES || kind != CNERF_LAYER_RES) {
@@ -436,7 +412,6 @@ __global__ __launch_bounds__(256) void field_tile_kernel(FieldArgs a) {
 #pragma unroll
                 for (int t = 0; t < NT; ++t) x.v[t] = y.v[t];
                 asm volatile("" :: "v"(x.v[0][0]), "v"(x.v[NT - 1][15]));
-                STAMP(3);   // hidden layers
             } else {
                 // y = sin(W1 x + b1);  x = sin(x + W2 y + b2)   (tile t of x is dead once its own residual is added)
                 mlp_matrix<NT, NT, EPI_FILM, STORE, false, FOLD, WFOLD>(wp, bias, FOLD ? freq : ones, FOLD ? phase : zeros, x.v, nullptr, y.v, lane, h,
@@ -498,12 +473,7 @@ __global__ __launch_bounds__(256) void field_tile_kernel(FieldArgs a) {
         px = nx;
         py = ny;
         pz = nz;
-        STAMP(4);   // head
     }
-#ifdef CNERF_STAMPS
-    if (a.stamps && lane == 0)
-        for (int i = 0; i < 8; ++i) atomicAdd(a.stamps + i, st_[i]);
-#endif
 }
 
 // ---------------------------------------------------------------------------------------------------------------

@@ -9,7 +9,7 @@
 //
 // How.  A block owns a patch x depth bin = 256 points.  It sorts their 2048 (voxel, point, weight) corner records by voxel with a counting
 // sort on LDS integer atomics (ds_add_rtn_u32: 5-6 cycles per wave instruction; ds_add_f32 takes 194 -- scripts/ubench/lds_atomic.hip --
-// which is what stopped a box of fp32 sums in LDS, csrc/experiments/scatter_patch.hip); the points' gradient rows are parked in LDS;
+// which is what stopped a box of fp32 sums in LDS, commit 8b67246); the points' gradient rows are parked in LDS;
 // then each half-wave walks an equal share of the sorted records, 32 channels across its lanes, sums a run of equal voxels in a register
 // and adds the run to the volume once (a 128-byte row per half-wave: the shape float atomics run at full rate in).  53.6 KiB of LDS per
 // block, three blocks per CU; sums stay fp32.  The window of a block is 8 x 8 x 8 voxels from the smallest voxel index of the 8 corners of
@@ -20,7 +20,7 @@
 // Fine pass: the resampled depths of a ray are unordered (inverse-CDF draws), so a block tests all S depths of its 64 rays against its bin
 // (16 depth loads in flight per lane, one result bit per round), queues the matches and processes a batch whenever 256 wait; a tail of at
 // most 48 points is added directly.  bench.py train_step at batch 8, 128 x 128 x (64 + 64), random cameras: 84.2 ms with the chain's own
-// atomics, 77.6 with the coarse pass here, 74.9 with both (the default; CNERF_SCATTER=chain / coarse select the others: A/B and tests).
+// atomics, 77.6 with the coarse pass here, 74.9 with both (the default; CNERF_SCATTER=chain selects the chain's atomics: A/B and tests).
 #include <hip/hip_runtime.h>
 
 #include "cnerf_kernels.hpp"

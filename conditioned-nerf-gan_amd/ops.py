@@ -9,17 +9,14 @@ import torch.nn.functional as F
 
 from . import _lib as L
 
-# packed weights per field network: dropped with the module (weak keys), re-packed when a parameter's version changes
+# packed weights per field network and layout: dropped with the module (weak keys), re-packed when a parameter's version changes
 _pack_cache = weakref.WeakKeyDictionary()
-_packt_cache = weakref.WeakKeyDictionary()
 
 
 def clear_pack_cache():
     """Forget every packed weight buffer (a training step that changed the weights re-packs anyway: the cache keys hold the
     parameters' version counters; bench.py calls this so that every timed step pays the packing like a training step)."""
     _pack_cache.clear()
-    _packt_cache.clear()
-    _pack16_cache.clear()
 
 
 def _stream():
@@ -133,20 +130,31 @@ def _field_params_struct(net, params):
     return fp
 
 
-def pack_field(net, cfg):
-    """Packed MFMA-order weights of `net` (device tensor), re-packed only when a parameter changed."""
-    params = [_f32(p.detach()) for p in net.field_params()]
-    key = tuple((p.data_ptr(), p._version) for p in net.field_params()) + (cfg.precision,)
-    hit = _pack_cache.setdefault(net, {}).get(cfg.precision)
+def _cached_pack(net, cfg, layout, nbytes, entry, dtype):
+    """The buffer the ABI entry point `entry` (cfg, field params, buffer, stream) packs from the parameters of `net`, cached per
+    (net, layout) and re-packed only when a parameter changed; nbytes() sizes it on a miss."""
+    key = tuple((p.data_ptr(), p._version) for p in net.field_params())
+    hit = _pack_cache.setdefault(net, {}).get(layout)
     if hit is not None and hit[0] == key:
         return hit[1]
-    nbytes, _, _ = sizes(cfg, render=False)
-    packed = torch.empty(nbytes // 4, dtype=torch.float32, device=params[0].device)
+    params = [_f32(p.detach()) for p in net.field_params()]
+    buf = torch.empty(nbytes() // dtype.itemsize, dtype=dtype, device=params[0].device)
     fp = _field_params_struct(net, params)
-    L.check(L.lib().cnerf_pack_field(C.byref(cfg), C.byref(fp), L.ptr(packed), _stream()), "cnerf_pack_field")
-    packed._keepalive = params
-    _pack_cache[net][cfg.precision] = (key, packed)
-    return packed
+    L.check(getattr(L.lib(), entry)(C.byref(cfg), C.byref(fp), L.ptr(buf), _stream()), entry)
+    buf._keepalive = params
+    _pack_cache[net][layout] = (key, buf)
+    return buf
+
+
+def _abi_bytes(entry, cfg):
+    nb = C.c_size_t(0)
+    L.check(getattr(L.lib(), entry)(C.byref(cfg), C.byref(nb)), entry)
+    return nb.value
+
+
+def pack_field(net, cfg):
+    """Packed MFMA-order weights of `net` in cfg's precision (cnerf_pack_field)."""
+    return _cached_pack(net, cfg, ("forward", cfg.precision), lambda: sizes(cfg, render=False)[0], "cnerf_pack_field", torch.float32)
 
 
 def channel_last_levels(vols):
@@ -319,20 +327,8 @@ SAVED_KEYS = ("coarse_rgb_sigma", "coarse_z", "fine_rgb_sigma", "fine_z")
 
 
 def pack_field_transposed(net, cfg):
-    params = [_f32(p.detach()) for p in net.field_params()]
-    key = tuple((p.data_ptr(), p._version) for p in net.field_params())
-    hit = _packt_cache.get(net)
-    if hit is not None and hit[0] == key:
-        return hit[1]
-    nb = C.c_size_t(0)
-    L.check(L.lib().cnerf_backward_bytes(C.byref(cfg), C.byref(nb)), "cnerf_backward_bytes")
-    packed_t = torch.empty(nb.value // 4, dtype=torch.float32, device=params[0].device)
-    fp = _field_params_struct(net, params)
-    L.check(L.lib().cnerf_pack_field_transposed(C.byref(cfg), C.byref(fp), L.ptr(packed_t), _stream()),
-            "cnerf_pack_field_transposed")
-    packed_t._keepalive = params
-    _packt_cache[net] = (key, packed_t)
-    return packed_t
+    """Transposed fp32 weights of the exact gradient chain (cnerf_pack_field_transposed)."""
+    return _cached_pack(net, cfg, "transposed", lambda: _abi_bytes("cnerf_backward_bytes", cfg), "cnerf_pack_field_transposed", torch.float32)
 
 
 DEBUG_CAPTURE = None            # set to a dict to capture the chunk buffers of the per-point FiLM backward (debugging)
@@ -429,24 +425,9 @@ def n_matrices(net):
     return sum(2 if k == "res" else 1 for k in net.spec.layers)
 
 
-_pack16_cache = weakref.WeakKeyDictionary()
-
-
 def pack_field_chain16(net, cfg):
-    """Transposed fp16 weight units of the half-precision gradient chain (cnerf_pack_field_chain16), cached per parameter version."""
-    params = [_f32(p.detach()) for p in net.field_params()]
-    key = tuple((p.data_ptr(), p._version) for p in net.field_params())
-    hit = _pack16_cache.get(net)
-    if hit is not None and hit[0] == key:
-        return hit[1]
-    nb = C.c_size_t(0)
-    L.check(L.lib().cnerf_backward16_bytes(C.byref(cfg), C.byref(nb)), "cnerf_backward16_bytes")
-    packed16 = torch.empty(nb.value, dtype=torch.uint8, device=params[0].device)
-    fp = _field_params_struct(net, params)
-    L.check(L.lib().cnerf_pack_field_chain16(C.byref(cfg), C.byref(fp), L.ptr(packed16), _stream()), "cnerf_pack_field_chain16")
-    packed16._keepalive = params
-    _pack16_cache[net] = (key, packed16)
-    return packed16
+    """Transposed fp16 weight units of the half-precision gradient chain (cnerf_pack_field_chain16)."""
+    return _cached_pack(net, cfg, "chain16", lambda: _abi_bytes("cnerf_backward16_bytes", cfg), "cnerf_pack_field_chain16", torch.uint8)
 
 
 RESIDENT_BUDGET_BYTES = 160 << 30    # fp16 activations kept from the forward for the backward: at most this much (288 GB of HBM per GPU) ...
@@ -522,16 +503,16 @@ def render_backward(net, o, levels, freq, phase, cam2world, rng, saved, grad_pix
     B, R, S, hier = o["B"], o["R"], o["S"], o["hier"]
     dev = cam2world.device
     bprec = backward_precision_of(net)
-    # cfg: precision of the forward (the activation-storing re-run follows it; the fp16 backward re-runs the fp16x3 kernel)
-    cfg = make_cfg(net, B, levels, R, S, o["fov"], o["ray_start"], o["ray_end"], o["noise_std"], hier,
-                   o["white_back"], o["last_back"], o["clamp_mode"], precision="fp16x3" if bprec == "fp16" else None,
-                   philox=rng.get("philox"), drop=drop_of(rng))
+    pfilm32 = net.spec.layers[0] == "pfilm" and bprec == "fp32"
+    # cfg: precision of the forward (the activation-storing re-run follows it); the fp16 backward re-runs the fp16x3 kernel, the per-point
+    # FiLM family's fp32 chain the fp32 kernel (its packed weights are that kernel's)
+    cfg = make_cfg(net, B, levels, R, S, o["fov"], o["ray_start"], o["ray_end"], o["noise_std"], hier, o["white_back"], o["last_back"],
+                   o["clamp_mode"], precision="fp16x3" if bprec == "fp16" else ("fp32" if pfilm32 else None), philox=rng.get("philox"),
+                   drop=drop_of(rng))
     c_rs, c_z, f_rs, f_z = saved[:4]
     grad_pixels = _f32(grad_pixels)
     grad_depth = _f32(grad_depth) if grad_depth is not None else None
-    if net.spec.layers[0] == "pfilm" and bprec == "fp32":      # (fp32 chain: the activation-storing re-run and its packed weights are the fp32 kernel's)
-        cfg = make_cfg(net, B, levels, R, S, o["fov"], o["ray_start"], o["ray_end"], o["noise_std"], hier, o["white_back"], o["last_back"],
-                       o["clamp_mode"], precision="fp32", philox=rng.get("philox"), drop=drop_of(rng))
+    if pfilm32:
         gc = torch.empty_like(c_rs)
         gf = torch.empty_like(f_rs) if hier else None
         eps_final = _f32(rng.get("eps_final")) if o["noise_std"] != 0 else None

@@ -22,7 +22,7 @@
 extern "C" {
 #endif
 
-#define CNERF_ABI_VERSION 7
+#define CNERF_ABI_VERSION 8
 
 #define CNERF_OK 0
 #define CNERF_EINVAL (-22)  /* bad argument / unsupported shape (message via cnerf_last_error) */
@@ -331,28 +331,6 @@ int cnerf_weight_grad16(int32_t n_images, int64_t tiles_per_image, int32_t n_row
 int cnerf_backward16_bytes(const cnerf_cfg* cfg, size_t* packed16);
 int cnerf_pack_field_chain16(const cnerf_cfg* cfg, const cnerf_field_params* params, void* packed16, void* stream);
 
-/* cnerf_field_backward16.mode */
-#define CNERF_B16_STORE 1u /* re-run the field forward (fp16x3 kernel) storing x0, sin(arg_m), cos(arg_m) as fp16 TB16 */
-#define CNERF_B16_DRY 2u   /* run the chain over every `group_step`-th tile group WITHOUT stores: only gmax[m] = max |d/d arg_m| */
-#define CNERF_B16_CHAIN 4u /* the chain: g16, go16, feature-volume gradients */
-
-/* Twin of cnerf_field_backward (same pass / image-range / per-image-input conventions) for the half-precision path.
- *   cfg->precision must be CNERF_PREC_FP16X3 and `packed` its forward layout (the re-run is that kernel);
- *   act_feat16 (T, n_in, 32, 32), act_h16 / act_g16 (n_mats, T, H/32, 32, 32), act_go16 (T, 1, 32, 32; ZERO it first: only
- *   channels 0..3 are written): fp16 TB16 chunk buffers, T = n_images * ceil(R*R*S / 32); act_c16: the same number of bytes as
- *   act_h16, private to the storing forward and the chain (fragment-major, csrc/bwd16.hpp "COS16");
- *   scales (DEVICE, 2 * (n_mats + 1) floats): per matrix m {S_m, 1 / S_m} = power-of-two scale of act_g16[m], then
- *   {S_go, 1 / S_go} of act_go16 -- the caller derives them from gmax;  gmax (DEVICE, n_mats + 1 uint32, zero it first): bit
- *   patterns of the sampled maxima written by a CNERF_B16_DRY call (max |d/d arg_m| per matrix, then max |go'|).
- * Typical sequence per chunk: STORE | DRY (group_step 16)  ->  scales from gmax  ->  CHAIN  ->  cnerf_weight_grad16 per matrix
- * (G = act_g16[m], X = act_feat16 or act_h16[m-1]; head: G = act_go16, n_rows 4, X = act_h16[last]). */
-int cnerf_field_backward16(const cnerf_cfg* cfg, uint32_t mode, int32_t group_step, int32_t pass, int32_t image0, int32_t n_images,
-                           const cnerf_volumes* vols, const float* packed, const void* packed16, const float* freq,
-                           const float* phase, const float* cam2world, const float* u_strat, const float* fine_z,
-                           const float* grad_rgb_sigma, const float* saved_rgb_sigma, void* act_feat16, void* act_h16, void* act_c16,
-                           void* act_g16, void* act_go16, const float* scales, uint32_t* gmax, const cnerf_grad_volumes* grad_vols,
-                           void* stream);
-
 /* ---- the whole backward in ONE call (ABI v6) --------------------------------------------------------------------------
  * Autograd twin of cnerf_render_forward for hosts without an autograd engine of their own (and the path the PyTorch mirror
  * takes): given d loss / d pixels and d loss / d depth it runs the steps above -- cnerf_merge_composite_backward, then per
@@ -362,7 +340,7 @@ int cnerf_field_backward16(const cnerf_cfg* cfg, uint32_t mode, int32_t group_st
  * Replaces loss.backward() through ImplicitGenerator3d.forward (utils.py:638-711; generators.py:33-187 under autograd).
  *
  *   backward_precision  CNERF_PREC_FP32: exact fp32 chain and weight reductions (re-run in cfg->precision);
- *                       CNERF_PREC_FP16: fp16 operands, fp32 sums (cnerf_field_backward16 / cnerf_weight_grad16; cfg->precision must
+ *                       CNERF_PREC_FP16: fp16 operands, fp32 sums (csrc/bwd16.hip, cnerf_weight_grad16; cfg->precision must
  *                       be CNERF_PREC_FP16X3).  Per-point FiLM networks (ABI v7): CNERF_PREC_FP16 runs here (csrc/chain_pw16.hip; grads->map_*
  *                       receive the mapping network's gradients); CNERF_PREC_FP32 answers CNERF_ENOSYS -- the exact path finishes its
  *                       mapping-MLP reductions with library GEMMs on the host (cnerf_field_backward + cnerf_weight_grad + cnerf_scatter_features).
@@ -377,8 +355,7 @@ int cnerf_field_backward16(const cnerf_cfg* cfg, uint32_t mode, int32_t group_st
  *                       all B).  workspace: cnerf_backward_workspace_bytes(cfg, backward_precision, images_per_chunk, act16 != NULL).
  *   saturated           optional DEVICE uint32 (zero it first), fp16 backward: incremented once per (tile, matrix) in which a stored
  *                       gradient exceeded fp16's range and was clamped -- the per-matrix scale comes from a SAMPLED maximum
- *                       (every 16th tile group once there are >= 32768 of them); non-zero means: repeat with exhaustive sampling
- *                       (cnerf_field_backward16 with group_step 1) or in fp32. */
+ *                       (every 16th tile group once there are >= 32768 of them); non-zero means: repeat in fp32. */
 typedef struct cnerf_field_param_grads {
     float* w[CNERF_MAX_LAYERS];
     float* b[CNERF_MAX_LAYERS];
@@ -401,9 +378,8 @@ typedef struct cnerf_saved {
 } cnerf_saved;
 
 /* Half-precision backward, feature-volume gradient: the ray passes' input-tile gradients go through the workspace (128 B per point) and
- * are added to grad_vols pre-reduced per 8 x 8-pixel patch (csrc/scatter_patch.hip); explicit points are added by the gradient chain
- * itself.  Same addends either way.  Environment CNERF_SCATTER=chain | coarse makes the chain add both ray passes' / the fine pass's
- * too (A/B runs and tests only). */
+ * are added to grad_vols pre-reduced per 8 x 8-pixel patch (csrc/scatter_patch.hip).  Environment CNERF_SCATTER=chain makes the
+ * gradient chain add them itself (A/B runs and tests only): the same addends in another order. */
 int cnerf_backward_workspace_bytes(const cnerf_cfg* cfg, int32_t backward_precision, int32_t images_per_chunk, int32_t have_act16,
                                    size_t* bytes);
 int cnerf_render_backward(const cnerf_cfg* cfg, int32_t backward_precision, int32_t images_per_chunk, const cnerf_volumes* vols,

@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """Feature-volume gradient of the half-precision backward with the chain's own scatter (CNERF_SCATTER=chain) against the sorted patch
-scatter: same addends, different summation order.  Usage: scatter_ab.py run OUT.pt [R S V B] | scatter_ab.py cmp A.pt B.pt"""
+scatter (the default): same addends, different summation order.  Usage: scatter_ab.py run OUT.pt [R S V B] once with CNERF_SCATTER=chain and
+once without it, then scatter_ab.py cmp A.pt B.pt"""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch

@@ -1,7 +1,7 @@
 #!/bin/bash
-# bench.py's train_step (render forward + backward at batch 8) under the three settings of CNERF_SCATTER
+# bench.py's train_step (render forward + backward at batch 8) with the sorted patch scatter (default) and CNERF_SCATTER=chain
 out=$(mktemp -d)
-for n in default coarse chain; do
+for n in default chain; do
   if [ "$n" = default ]; then unset CNERF_SCATTER; else export CNERF_SCATTER=$n; fi
   timeout -k 10 120 python bench.py --full --no-cpu-baseline --no-fast-path --no-gan-step --steps 3 --warmup 1 > $out/ab_$n.json 2>/dev/null
   python -c "

@@ -1300,36 +1300,43 @@ def test_dropout_in_kernel_decisions_equal_their_numpy_twin(golden, dev, name):
     assert not torch.equal(px2, runs[0][0])
 
 
-def test_dropout_decisions_do_not_depend_on_the_chunking(dev, golden):
-    """The backward re-runs the forward per chunk of images (ops.ACT_BUDGET_BYTES); keep decisions are indexed by the point's position
+def test_dropout_decisions_do_not_depend_on_the_chunking(dev, golden, monkeypatch):
+    """The backward re-runs the forward per chunk of images (ops.backward_chunk); keep decisions are indexed by the point's position
     in the WHOLE call (image0 offsets of the Philox counter and of the injected bytes), so one image per chunk must give the
     gradients of all images in one chunk -- in-kernel draws and injected bytes alike."""
+    import ctypes as C
     import cnerf_amd
     from cnerf_amd import ops
+    L = cnerf_amd._lib
     g = golden("short_fg_drop_small")
     m = g.meta
     assert m["B"] == 2
     gen = make_generator(g, dev)
     gen.train()
+    real_chunk = ops.backward_chunk
+    seen = []
+
+    def by_image(cfg, code, nb_max, have_act16, d):
+        need = C.c_size_t(0)
+        L.check(L.lib().cnerf_backward_workspace_bytes(C.byref(cfg), code, 1, 0, C.byref(need)), "cnerf_backward_workspace_bytes")
+        seen.append(nb_max)
+        return 1, need.value
     base = {k: v for k, v in _dropout_rng(g, dev).items() if not k.startswith("drop_")}
     for rng in (dict(base, drop=(m["drop_out"], (99, 3))), _dropout_rng(g, dev)):
         res = []
-        budget = ops.ACT_BUDGET_BYTES
-        try:
-            for b in (budget, 1):                      # 1 byte: one image per chunk
-                ops.ACT_BUDGET_BYTES = b
-                z, vleaves, glob = make_z(g, dev, requires_grad=True)
-                gen.zero_grad()
-                px, dp = gen(z, G(g["cam2worlds"], dev), m["R"], m["fov"], m["ray_start"], m["ray_end"], m["S"], True, clamp_mode=m["clamp"],
-                             nerf_noise=m["noise"], white_back=m["white_back"], last_back=m["last_back"], _rng=dict(rng))
-                (px.square().mean() + dp.mean()).backward()
-                res.append({"feature_volume": vleaves[0].grad.clone(), "global": glob.grad.clone(),
-                            **{k: q.grad.clone() for k, q in gen.named_parameters()}})
-        finally:
-            ops.ACT_BUDGET_BYTES = budget
+        for chunk in (real_chunk, by_image):             # all images in one chunk, then one image per chunk
+            monkeypatch.setattr(ops, "backward_chunk", chunk)
+            z, vleaves, glob = make_z(g, dev, requires_grad=True)
+            gen.zero_grad()
+            px, dp = gen(z, G(g["cam2worlds"], dev), m["R"], m["fov"], m["ray_start"], m["ray_end"], m["S"], True, clamp_mode=m["clamp"],
+                         nerf_noise=m["noise"], white_back=m["white_back"], last_back=m["last_back"], _rng=dict(rng))
+            (px.square().mean() + dp.mean()).backward()
+            res.append({"feature_volume": vleaves[0].grad.clone(), "global": glob.grad.clone(),
+                        **{k: q.grad.clone() for k, q in gen.named_parameters()}})
+        monkeypatch.setattr(ops, "backward_chunk", real_chunk)
         for k in res[0]:
             assert scaled_err(res[1][k].cpu().numpy(), res[0][k].cpu().numpy()) < 1e-5, k
-
+    assert seen == [m["B"], m["B"]]
 
 
 @pytest.mark.parametrize("precision", ["fp32", "fp16x3"])
@@ -1382,7 +1389,7 @@ def test_forward_replays_from_a_hip_graph(dev, precision):
 def test_sorted_patch_scatter_matches_the_chain_scatter(dev, monkeypatch, shape, variant):
     """The feature-volume gradient of the half-precision backward is added to the volume by scatter_sorted_kernel (scatter_patch.hip:
     8 x 8-pixel patches x depth bins, corner records sorted by voxel in LDS, one add per run) from the input-tile gradients the chain
-    stores.  CNERF_SCATTER=chain makes the chain add its tiles itself (the path explicit points take): the same addends in another
+    stores.  CNERF_SCATTER=chain makes the chain add its tiles itself: the same addends in another
     order, so the volumes agree to fp32 summation noise.  Shapes: pixels ~3 voxels apart in a 40-voxel volume (most patches outgrow the
     8-voxel window: the direct path), ragged patches / a ragged last quad / several images in a 12-voxel volume (everything inside one
     window, long runs), and a 64-voxel volume at 64 x 64 rays; oblique cameras; a single level and the three-level pyramid."""
@@ -1412,17 +1419,14 @@ def test_sorted_patch_scatter_matches_the_chain_scatter(dev, monkeypatch, shape,
 
     monkeypatch.setenv("CNERF_SCATTER", "chain")
     ref = grads()
-    monkeypatch.setenv("CNERF_SCATTER", "coarse")       # the coarse pass through the sorted scatter, the fine pass by the chain
-    coarse = grads()
     monkeypatch.delenv("CNERF_SCATTER")                  # the default: both ray passes sorted (the fine pass: depth bins, queued candidates)
     default = grads()
-    for got in (coarse, default):
-        for g, r_ in zip(got, ref):
-            assert r_.abs().max() > 0
-            # fp32 sums of the same addends in two orders: 2e-7 .. 4e-7 apart in the 40- and 64-voxel volumes, ~2e-6 in the pyramid's 3-voxel level
-            # (each of its 27 voxels sums ~2e4 addends); a single point lost or added twice would show at 1e-3 or more
-            assert ((g - r_).norm() / r_.norm()).item() < 2e-5
-            assert ((g - r_).abs().max() / r_.abs().max()).item() < 1e-4
+    for g, r_ in zip(default, ref):
+        assert r_.abs().max() > 0
+        # fp32 sums of the same addends in two orders: 2e-7 .. 4e-7 apart in the 40- and 64-voxel volumes, ~2e-6 in the pyramid's 3-voxel level
+        # (each of its 27 voxels sums ~2e4 addends); a single point lost or added twice would show at 1e-3 or more
+        assert ((g - r_).norm() / r_.norm()).item() < 2e-5
+        assert ((g - r_).abs().max() / r_.abs().max()).item() < 1e-4
 
 
 def test_half_precision_backward_reports_clamped_outliers(dev):
