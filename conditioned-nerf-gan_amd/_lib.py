@@ -8,7 +8,7 @@ LIB_PATH = os.path.join(HERE, "libcnerf_hip.so")
 
 MAX_LAYERS = 16
 MAX_LEVELS = 4
-ABI_VERSION = 8
+ABI_VERSION = 9
 F_HIERARCHICAL, F_WHITE_BACK, F_LAST_BACK, F_SOFTPLUS, F_SIGMOID_RGB, F_INPUT_XYZ = 1, 2, 4, 8, 16, 32
 PREC_FP32, PREC_FP16, PREC_FP16X3 = 0, 1, 2
 PREC_CODE = {"fp32": PREC_FP32, "fp16": PREC_FP16, "fp16x3": PREC_FP16X3}
@@ -96,6 +96,14 @@ PROTOTYPES = {
     "cnerf_render_backward": (C.c_int, [C.POINTER(Cfg), C.c_int32, C.c_int32, C.POINTER(Volumes), C.POINTER(FieldParams), C.c_void_p, C.c_void_p,
                                         C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(Rng), C.POINTER(Saved), C.POINTER(Aux), C.c_void_p, C.c_void_p,
                                         C.POINTER(FieldParamGrads), C.c_void_p, C.c_void_p, C.POINTER(Volumes), C.c_void_p, C.c_void_p, C.c_void_p]),
+    "cnerf_field_query_backward_workspace_bytes": (C.c_int, [C.POINTER(Cfg), C.c_int32, C.c_int64, C.POINTER(C.c_size_t)]),
+    "cnerf_field_query_backward": (C.c_int, [C.POINTER(Cfg), C.c_int32, C.c_int64, C.POINTER(Volumes), C.POINTER(FieldParams), C.c_void_p, C.c_void_p,
+                                             C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.POINTER(FieldParamGrads),
+                                             C.c_void_p, C.c_void_p, C.POINTER(Volumes), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "cnerf_field_backward_points": (C.c_int, [C.POINTER(Cfg), C.POINTER(Volumes), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                              C.c_int64] + [C.c_void_p] * 7 + [C.POINTER(Volumes), C.c_void_p, C.c_void_p]),
+    "cnerf_feature_points_grad": (C.c_int, [C.POINTER(Cfg), C.POINTER(Volumes), C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "cnerf_dropout_keep": (C.c_int, [C.POINTER(Cfg), C.c_uint32, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p]),
 }
 
 _lib = None

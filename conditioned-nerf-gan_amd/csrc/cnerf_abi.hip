@@ -274,6 +274,26 @@ FieldArgs storing_args(const FieldArgs& a, long long n_points, void* feat, void*
     return s;
 }
 
+// The exact fp32 backward of one field pass `fa` (n_points rows, gradient volumes and dropout set): the activation-storing re-run
+// in cfg->precision (`packed` is in that precision's layout), then the fp32 gradient chain on the transposed fp32 weights, which
+// scatters d(feature volume) itself.  grad_out / saved_out: the rows of this launch.
+int field_backward_run(FieldArgs fa, const cnerf_cfg* cfg, long long n_points, const float* packed_t, const float* grad_out, const float* saved_out,
+                       float* act_feat, float* act_h, float* act_c, float* act_g, float* act_go, hipStream_t stream) {
+    fa.rgb_sigma = act_go;          // the re-run forward needs somewhere to put its head output: overwritten below by go'
+    fa.act_points = n_points;
+    fa.act_feat = act_feat;
+    fa.act_h = act_h;
+    fa.act_c = act_c;
+    if (hipError_t e = launch_forward(fa, cfg, stream)) return hip_fail(e, "field kernel (activation store)");
+    fa.packed_t = packed_t;
+    fa.grad_out = grad_out;
+    fa.saved_out = saved_out;
+    fa.act_g = act_g;
+    fa.act_go = act_go;
+    if (hipError_t e = launch_field_backward(fa, cfg->H, stream)) return hip_fail(e, "field backward kernel");
+    return CNERF_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -754,22 +774,33 @@ int cnerf_field_backward(const cnerf_cfg* cfg, int32_t pass, int32_t image0, int
 
     FieldArgs fa;
     if (int rc = pass_args(fa, cfg, pass, image0, n_images, vols, grad_vols, packed, freq, phase, cam2world, u_strat, fine_z)) return rc;
-    fa.rgb_sigma = act_go;          // the re-run forward needs somewhere to put its head output: overwritten below by go'
-    fa.act_points = (long long)n_images * npi;
-    fa.act_feat = act_feat;
-    fa.act_h = act_h;
-    fa.act_c = act_c;
     set_dropout(fa, cfg, drop_mask, pass == 0 ? PHILOX_DROP_COARSE : pass == 1 ? PHILOX_DROP_FINE : PHILOX_DROP_POINTS, npi);
-    // the activation-storing forward runs in cfg->precision (`packed` is in that precision's layout); the gradient chain
-    // below is fp32 on the transposed fp32 weights either way
-    if (hipError_t e = launch_forward(fa, cfg, stream)) return hip_fail(e, "field kernel (activation store)");
-    fa.packed_t = packed_t;
-    fa.grad_out = grad_rgb_sigma + (size_t)image0 * npi * 4;
-    fa.saved_out = saved_rgb_sigma + (size_t)image0 * npi * 4;
-    fa.act_g = act_g;
-    fa.act_go = act_go;
-    if (hipError_t e = launch_field_backward(fa, cfg->H, stream)) return hip_fail(e, "field backward kernel");
-    return CNERF_OK;
+    return field_backward_run(fa, cfg, (long long)n_images * npi, packed_t, grad_rgb_sigma + (size_t)image0 * npi * 4,
+                              saved_rgb_sigma + (size_t)image0 * npi * 4, act_feat, act_h, act_c, act_g, act_go, stream);
+}
+
+int cnerf_field_backward_points(const cnerf_cfg* cfg, const cnerf_volumes* vols, const float* packed, const float* packed_t, const float* freq,
+                                const float* phase, const float* points, int64_t n_per_image, const float* grad_rgb_sigma,
+                                const float* saved_rgb_sigma, float* act_feat, float* act_h, float* act_c, float* act_g, float* act_go,
+                                const cnerf_grad_volumes* grad_vols, const uint8_t* drop_mask, void* stream) {
+    g_err[0] = 0;
+    if (int rc = check_cfg(cfg, false)) return rc;
+    if (cfg->layer_kind[0] == CNERF_LAYER_PFILM && cfg->precision != CNERF_PREC_FP32)
+        return fail(CNERF_EINVAL, "field_backward_points: the per-point FiLM family's fp32 chain needs a cfg (and packed weights) of precision fp32");
+    if (!vols || !packed || !packed_t || !points || n_per_image < 1 || !grad_rgb_sigma || !saved_rgb_sigma || !act_feat || !act_h || !act_c || !act_g ||
+        !act_go || !grad_vols)
+        return fail(CNERF_EINVAL, "field_backward_points: NULL argument");
+    for (int i = 0; i < n_levels_of(cfg); ++i)
+        if (!grad_vols->level[i]) return fail(CNERF_EINVAL, "field_backward_points: gradient volume %d is NULL", i);
+    if (packed_layout(cfg).n_film && (!freq || !phase)) return fail(CNERF_EINVAL, "field_backward_points: FiLM layers need freq and phase");
+    FieldArgs fa;
+    if (int rc = fill_field_args(fa, cfg, vols, grad_vols, packed, freq, phase)) return rc;
+    fa.mode = FIELD_MODE_POINTS;
+    fa.points = points;
+    set_points(fa, cfg->B, n_per_image);
+    set_dropout(fa, cfg, drop_mask, PHILOX_DROP_POINTS, n_per_image);
+    return field_backward_run(fa, cfg, (long long)cfg->B * n_per_image, packed_t, grad_rgb_sigma, saved_rgb_sigma, act_feat, act_h, act_c, act_g,
+                              act_go, (hipStream_t)stream);
 }
 
 int cnerf_weight_grad16(int32_t n_images, int64_t tiles_per_image, int32_t n_rows, int32_t g_ct, int32_t x_ct, const void* G,
@@ -898,8 +929,9 @@ int cnerf_pack_field_chain16(const cnerf_cfg* cfg, const cnerf_field_params* p, 
 // the whole backward in one call
 // ---------------------------------------------------------------------------------------------------------------------
 namespace {
-// Workspace of cnerf_render_backward, carved in this order (every piece 256-byte aligned).  n = images_per_chunk * points per
-// image (fp32 backward: row-major fp32 chunk matrices), T = images_per_chunk * tiles per image (fp16 backward: TB16 blocks).
+// Workspace of cnerf_render_backward and cnerf_field_query_backward, carved in this order (every piece 256-byte aligned).  A chunk is
+// cnt images of npi points each: n = cnt * npi (fp32 backward: row-major fp32 chunk matrices), T = cnt * tiles per image (fp16 backward:
+// TB16 blocks).  N_out: rows of the whole call's d loss / d rgb_sigma the render derives from d(pixels, depth) (0 for a query).
 struct BackwardLayout {
     size_t gc, gf;                                   // d loss / d rgb_sigma of the coarse / fine samples, whole call
     size_t a_feat, a_h, a_c, a_g, a_go;              // chunk buffers (a_feat / a_h / a_c absent when the forward kept its activations)
@@ -911,25 +943,25 @@ struct BackwardLayout {
     size_t total;
     int n_mats, n_in, k0;
 };
-int backward_layout(const cnerf_cfg* c, int bprec, int cnt, bool have_act16, BackwardLayout& L) {
-    if (bprec != CNERF_PREC_FP32 && bprec != CNERF_PREC_FP16) return fail(CNERF_EINVAL, "render_backward: backward_precision must be CNERF_PREC_FP32 or CNERF_PREC_FP16");
+int chunk_layout(const cnerf_cfg* c, int bprec, int cnt, size_t npi, size_t N_out, bool hier, bool have_act16, bool gin, const char* who,
+                 BackwardLayout& L) {
+    if (bprec != CNERF_PREC_FP32 && bprec != CNERF_PREC_FP16) return fail(CNERF_EINVAL, "%s: backward_precision must be CNERF_PREC_FP32 or CNERF_PREC_FP16", who);
     if (c->layer_kind[0] == CNERF_LAYER_PFILM && bprec != CNERF_PREC_FP16)
-        return fail(CNERF_ENOSYS, "render_backward: the per-point FiLM family's exact fp32 backward finishes its mapping-MLP gradients with library "
-                                  "GEMMs on the host (cnerf_field_backward + cnerf_weight_grad + cnerf_scatter_features); backward_precision fp16 runs here");
-    if (cnt < 1 || cnt > c->B) return fail(CNERF_EINVAL, "render_backward: images_per_chunk=%d out of [1,B]", cnt);
+        return fail(CNERF_ENOSYS, "%s: the per-point FiLM family's exact fp32 backward finishes its mapping-MLP gradients with library "
+                                  "GEMMs on the host (cnerf_field_backward + cnerf_weight_grad + cnerf_scatter_features); backward_precision fp16 runs here", who);
+    if (cnt < 1 || cnt > c->B) return fail(CNERF_EINVAL, "%s: images_per_chunk=%d out of [1,B]", who, cnt);
     if (c->layer_kind[0] == CNERF_LAYER_PFILM) {      // chain_pw16.hip: three stored derivatives and three gradient slabs per layer, m and g_mpre
-        if (have_act16 && cnt != c->B) return fail(CNERF_EINVAL, "render_backward: kept activations need images_per_chunk = B");
-        if (c->precision != CNERF_PREC_FP16X3) return fail(CNERF_EINVAL, "render_backward: the fp16 backward re-runs the fp16x3 forward (cfg->precision)");
-        const size_t H = c->H, NT = H / 32, Lc = c->L, npi = (size_t)c->R * c->R * c->S, tpi = (npi + 31) / 32;
-        const size_t N = (size_t)c->B * npi, T = (size_t)cnt * tpi;
-        const bool hier = c->flags & CNERF_F_HIERARCHICAL;
+        if (have_act16 && cnt != c->B) return fail(CNERF_EINVAL, "%s: kept activations need images_per_chunk = B", who);
+        if (c->precision != CNERF_PREC_FP16X3) return fail(CNERF_EINVAL, "%s: the fp16 backward re-runs the fp16x3 forward (cfg->precision)", who);
+        const size_t H = c->H, NT = H / 32, Lc = c->L, tpi = (npi + 31) / 32;
+        const size_t T = (size_t)cnt * tpi;
         L.n_in = 2;
         L.k0 = 3;
         L.n_mats = c->L;
         size_t off = 0;
         auto take = [&](size_t bytes) { const size_t o = off; off += align256(bytes); return o; };
-        L.gc = take(N * 4 * sizeof(float));
-        L.gf = take(hier ? N * 4 * sizeof(float) : 0);
+        L.gc = take(N_out * 4 * sizeof(float));
+        L.gf = take(hier ? N_out * 4 * sizeof(float) : 0);
         L.a_feat = take(have_act16 ? 0 : T * 2 * 2048);
         L.a_h = take(have_act16 ? 0 : (Lc * NT + 8) * T * 2048);
         L.a_c = take(have_act16 ? 0 : 3 * Lc * NT * T * 2048);
@@ -947,27 +979,26 @@ int backward_layout(const cnerf_cfg* c, int bprec, int cnt, bool have_act16, Bac
         L.total = off;
         return CNERF_OK;
     }
-    if (have_act16 && (bprec != CNERF_PREC_FP16 || cnt != c->B)) return fail(CNERF_EINVAL, "render_backward: kept activations need the fp16 backward and images_per_chunk = B");
-    if (bprec == CNERF_PREC_FP16 && c->precision != CNERF_PREC_FP16X3) return fail(CNERF_EINVAL, "render_backward: the fp16 backward re-runs the fp16x3 forward (cfg->precision)");
+    if (have_act16 && (bprec != CNERF_PREC_FP16 || cnt != c->B)) return fail(CNERF_EINVAL, "%s: kept activations need the fp16 backward and images_per_chunk = B", who);
+    if (bprec == CNERF_PREC_FP16 && c->precision != CNERF_PREC_FP16X3) return fail(CNERF_EINVAL, "%s: the fp16 backward re-runs the fp16x3 forward (cfg->precision)", who);
     const PackedLayout pl = packed_layout(c);
     L.n_in = pl.n_in;
     L.k0 = pl.k0;
     L.n_mats = 0;
     for (int l = 0; l < c->L; ++l) L.n_mats += c->layer_kind[l] == CNERF_LAYER_RES ? 2 : 1;
-    const size_t H = c->H, NT = H / 32, npi = (size_t)c->R * c->R * c->S, tpi = (npi + 31) / 32;
-    const size_t N = (size_t)c->B * npi, n = (size_t)cnt * npi, T = (size_t)cnt * tpi;
-    const bool hier = c->flags & CNERF_F_HIERARCHICAL;
+    const size_t H = c->H, NT = H / 32, tpi = (npi + 31) / 32;
+    const size_t n = (size_t)cnt * npi, T = (size_t)cnt * tpi;
     size_t off = 0;
     auto take = [&](size_t bytes) { const size_t o = off; off += align256(bytes); return o; };
-    L.gc = take(N * 4 * sizeof(float));
-    L.gf = take(hier ? N * 4 * sizeof(float) : 0);
+    L.gc = take(N_out * 4 * sizeof(float));
+    L.gf = take(hier ? N_out * 4 * sizeof(float) : 0);
     if (bprec == CNERF_PREC_FP16) {
         L.a_feat = take(have_act16 ? 0 : T * L.n_in * 2048);
         L.a_h = take(have_act16 ? 0 : (size_t)L.n_mats * T * NT * 2048);
         L.a_c = take(have_act16 ? 0 : (size_t)L.n_mats * T * NT * 2048);
         L.a_g = take((size_t)L.n_mats * T * NT * 2048);
         L.a_go = take(T * 2048);
-        L.a_gin = take((size_t)L.n_in * n * 32 * sizeof(float));
+        L.a_gin = take(gin ? (size_t)L.n_in * n * 32 * sizeof(float) : 0);
     } else {
         L.a_gin = 0;
         L.a_feat = take(n * 32 * L.n_in * sizeof(float));
@@ -987,6 +1018,10 @@ int backward_layout(const cnerf_cfg* c, int bprec, int cnt, bool have_act16, Bac
     L.csh = take((size_t)cnt * 4 * sizeof(float));
     L.total = off;
     return CNERF_OK;
+}
+int backward_layout(const cnerf_cfg* c, int bprec, int cnt, bool have_act16, BackwardLayout& L) {
+    const size_t npi = (size_t)c->R * c->R * c->S;
+    return chunk_layout(c, bprec, cnt, npi, (size_t)c->B * npi, c->flags & CNERF_F_HIERARCHICAL, have_act16, true, "render_backward", L);
 }
 
 // Scales of a half-precision chunk before its dry run: {1, 1} for slots 0 .. head - 1, slot `head` {S, 1 / S} from the largest
@@ -1021,6 +1056,198 @@ bool scatter_by_chain() {
     const char* s = getenv("CNERF_SCATTER");
     return s && !strcmp(s, "chain");
 }
+
+// The matrices of a FiLM / plain-sine / residual network in slab order (a residual block: fc1, fc2), their kinds and gradient buffers
+struct MatrixSet {
+    const float *W[2 * CNERF_MAX_LAYERS], *b[2 * CNERF_MAX_LAYERS];
+    float *dW[2 * CNERF_MAX_LAYERS], *db[2 * CNERF_MAX_LAYERS];
+    int film_of[2 * CNERF_MAX_LAYERS];
+    int H, film_stride;
+    // matrix m's slice of freq / grad_freq / grad_phase for the chunk from image b0 (NULL unless m is a FiLM matrix)
+    const float* film(const float* t, int m, int b0) const { return film_of[m] >= 0 ? t + (size_t)b0 * film_stride + (size_t)film_of[m] * H : nullptr; }
+    float* film(float* t, int m, int b0) const { return film_of[m] >= 0 ? t + (size_t)b0 * film_stride + (size_t)film_of[m] * H : nullptr; }
+};
+int matrix_set(const cnerf_cfg* cfg, const cnerf_field_params* P, const cnerf_field_param_grads* G, const char* who, MatrixSet& ms) {
+    int nm = 0, nfilm = 0;
+    for (int l = 0; l < cfg->L; ++l) {
+        const bool res = cfg->layer_kind[l] == CNERF_LAYER_RES;
+        if (!P->w[l] || !P->b[l] || (res && (!P->w2[l] || !P->b2[l]))) return fail(CNERF_EINVAL, "%s: parameters of layer %d are NULL", who, l);
+        ms.W[nm] = P->w[l]; ms.b[nm] = P->b[l]; ms.dW[nm] = G->w[l]; ms.db[nm] = G->b[l];
+        ms.film_of[nm] = cfg->layer_kind[l] == CNERF_LAYER_FILM ? nfilm++ : -1;
+        ++nm;
+        if (res) {
+            ms.W[nm] = P->w2[l]; ms.b[nm] = P->b2[l]; ms.dW[nm] = G->w2[l]; ms.db[nm] = G->b2[l];
+            ms.film_of[nm] = -1;
+            ++nm;
+        }
+    }
+    ms.H = cfg->H;
+    ms.film_stride = packed_layout(cfg).n_film * cfg->H;
+    return CNERF_OK;
+}
+
+// ---- chunk bodies: one chunk of cnt images (from image b0 of the call) of npi points (tpi tiles) each.  The render runs them per ray
+// pass and chunk of images, cnerf_field_query_backward per image and range of query points.
+struct Chunk {
+    int b0, cnt;
+    long long npi, tpi;
+};
+
+// exact fp32: cnerf_field_backward's re-run and chain (fa: the chunk's pass with gradient volumes and dropout set), one weight_grad
+// per matrix, the head
+int chunk32(const cnerf_cfg* cfg, const MatrixSet& ms, const BackwardLayout& L, char* ws, const FieldArgs& fa, const Chunk& k,
+            const float* packed_t, const float* g_out, const float* s_out, const float* freq, const cnerf_field_param_grads* G, float* grad_freq,
+            float* grad_phase, hipStream_t stream) {
+    const int H = cfg->H;
+    const size_t n = (size_t)k.cnt * k.npi;
+    float* a_feat = (float*)(ws + L.a_feat);
+    float* a_h = (float*)(ws + L.a_h);
+    float* a_c = (float*)(ws + L.a_c);
+    float* a_g = (float*)(ws + L.a_g);
+    float* a_go = (float*)(ws + L.a_go);
+    float* dwarg = (float*)(ws + L.dwarg);
+    float* cs = (float*)(ws + L.cs);
+    if (int rc = field_backward_run(fa, cfg, (long long)n, packed_t, g_out, s_out, a_feat, a_h, a_c, a_g, a_go, stream)) return rc;
+    for (int m = 0; m < L.n_mats; ++m) {
+        const int K = m == 0 ? 32 * L.n_in : H;
+        const float* X = m == 0 ? a_feat : a_h + (size_t)(m - 1) * n * H;
+        if (hipError_t e = hipMemsetAsync(dwarg, 0, (size_t)k.cnt * H * K * sizeof(float), stream)) return hip_fail(e, "memset");
+        if (hipError_t e = hipMemsetAsync(cs, 0, (size_t)k.cnt * H * sizeof(float), stream)) return hip_fail(e, "memset");
+        if (int rc = cnerf_weight_grad(k.cnt, k.npi, H, K, a_g + (size_t)m * n * H, X, dwarg, cs, stream)) return rc;
+        if (hipError_t e = launch_param_reduce(k.cnt, H, K, m == 0 ? L.k0 : H, dwarg, cs, ms.film(freq, m, k.b0), ms.film_stride, ms.W[m], ms.b[m], ms.dW[m],
+                                               ms.db[m], ms.film(grad_freq, m, k.b0), ms.film(grad_phase, m, k.b0), stream))
+            return hip_fail(e, "param_reduce");
+    }
+    if (G->w_final && G->b_final)
+        if (hipError_t e = launch_head_grad32(a_go, a_h + (size_t)(L.n_mats - 1) * n * H, (long long)n, H, G->w_final, G->b_final, stream))
+            return hip_fail(e, "head_grad32");
+    return CNERF_OK;
+}
+
+// half precision, FiLM / plain-sine / residual networks (bwd16.hip): the storing re-run (fp16x3 kernel) unless the activations are given,
+// the chain's dry run for the per-matrix scales, the chain, the patch scatter of the input-tile gradients (fc.gin set), one weight_grad16
+// per matrix.  fa: the chunk's pass without gradient volumes (re-run, dry run), fc: with them.
+int chunk16(const cnerf_cfg* cfg, const MatrixSet& ms, const BackwardLayout& L, char* ws, const void* packed_bwd, FieldArgs fa, FieldArgs fc,
+            const Chunk& k, const float* g_out, const float* s_out, void* a_feat, void* a_h, void* a_c, bool store, const float* freq,
+            const cnerf_field_param_grads* G, float* grad_freq, float* grad_phase, uint32_t* saturated, hipStream_t stream) {
+    const int H = cfg->H, NT = H / 32;
+    const long long T = (long long)k.cnt * k.tpi;
+    Chain16Layout cl;
+    if (int rc = chain16_layout(cfg, cl)) return rc;
+    const char* base16 = (const char*)packed_bwd;
+    const float* winv = (const float*)(base16 + cl.winv_off);
+    uint32_t* gmax = (uint32_t*)(ws + L.gmax);
+    float* scales = (float*)(ws + L.scales);
+    char* a_g = ws + L.a_g;
+    char* a_go = ws + L.a_go;
+    if (int rc = head_scales(g_out, (long long)k.cnt * k.npi * 4, gmax, L.n_mats + 2, gmax + L.n_mats + 1, scales, L.n_mats, stream)) return rc;
+    const long long groups = (long long)k.cnt * ((k.tpi + 3) / 4);
+    long long step = groups / 2048;                       // dry-run sampling: every 16th tile group once there are plenty
+    step = step < 1 ? 1 : (step > 16 ? 16 : step);
+    // the storing re-run and the dry run leave the gradient volumes alone; the chain (fc) adds to them
+    if (store)
+        if (hipError_t e = launch_field_h3(storing_args(fa, (long long)k.cnt * k.npi, a_feat, a_h, a_c, nullptr, a_g), H, stream))
+            return hip_fail(e, "field kernel (fp16 activation store)");
+    fa.grad_out = fc.grad_out = g_out;
+    fa.saved_out = fc.saved_out = s_out;
+    if (hipError_t e = launch_chain16(fa, H, base16, base16 + cl.head_off, winv, scales, a_c, nullptr, nullptr, gmax, nullptr, cl.n_mats, 1, (int)step,
+                                      stream))
+        return hip_fail(e, "chain16 (dry run)");
+    if (hipError_t e = launch_pow2_scales(gmax, L.n_mats, scales, stream)) return hip_fail(e, "pow2_scales");
+    if (hipError_t e = launch_chain16(fc, H, base16, base16 + cl.head_off, winv, scales, a_c, a_g, a_go, nullptr, saturated, cl.n_mats, 0, 1, stream))
+        return hip_fail(e, "chain16");
+    if (fc.gin)
+        if (hipError_t e = launch_scatter_patch(fc, fc.gin, stream)) return hip_fail(e, "scatter_patch");
+    float* dwarg = (float*)(ws + L.dwarg);
+    float* cs = (float*)(ws + L.cs);
+    const size_t slab = (size_t)T * NT * 2048;             // bytes per matrix in a_h / a_g
+    for (int m = 0; m < L.n_mats; ++m) {
+        const int x_ct = m == 0 ? L.n_in : NT;
+        const void* X = m == 0 ? a_feat : (const void*)((const char*)a_h + (size_t)(m - 1) * slab);
+        if (int rc = reduce16(k.cnt, k.tpi, H, NT, x_ct, a_g + (size_t)m * slab, X, scales + 2 * m + 1, dwarg, cs, 0, m == 0 ? L.k0 : H,
+                              ms.film(freq, m, k.b0), ms.film_stride, ms.W[m], ms.b[m], ms.dW[m], ms.db[m], ms.film(grad_freq, m, k.b0),
+                              ms.film(grad_phase, m, k.b0), stream))
+            return rc;
+    }
+    return reduce16(k.cnt, k.tpi, 4, 1, NT, a_go, (const char*)a_h + (size_t)(L.n_mats - 1) * slab, scales + 2 * L.n_mats + 1, (float*)(ws + L.dwh),
+                    (float*)(ws + L.csh), 0, H, nullptr, 0, nullptr, nullptr, G->w_final, G->b_final, nullptr, nullptr, stream);
+}
+
+// half precision, per-point FiLM family: storing forward (field_pw16.hip) unless the activations are given, the two chain kernels with
+// their dry runs (chain_pw16.hip), one weight_grad16 reduction per matrix: dW_l = g_pre_l^T y_{l-1}, dWm2 rows = (g_fr_l | g_ph_l)^T m,
+// dWm1 = g_mpre^T feat, head.  fa: the chunk's pass with gradient volumes.
+int chunk_pw16(const cnerf_cfg* cfg, const BackwardLayout& L, char* ws, const void* packed_bwd, FieldArgs fa, const Chunk& k, const float* g_out,
+               const float* s_out, char* a_feat, char* a_h, char* a_c, float* a_amax, bool store, const cnerf_field_param_grads* G, uint32_t* saturated,
+               hipStream_t stream) {
+    const int H = cfg->H, NT = H / 32, Lc = cfg->L, n_slots = 3 * Lc + 2;
+    const long long T = (long long)k.cnt * k.tpi;
+    const PwChainLayout cl = pw_chain_layout(cfg);
+    const char* base16 = (const char*)packed_bwd;
+    uint32_t* gmax = (uint32_t*)(ws + L.gmax);
+    float* scales = (float*)(ws + L.scales);
+    char* a_g = ws + L.a_g;
+    char* a_go = ws + L.a_go;
+    float* dwarg = (float*)(ws + L.dwarg);
+    float* cs = (float*)(ws + L.cs);
+    if (store)
+        if (hipError_t e = launch_field_pw3(storing_args(fa, (long long)k.cnt * k.npi, a_feat, a_h, a_c, a_amax, a_g), H, stream))
+            return hip_fail(e, "field kernel (fp16 activation store)");
+    fa.grad_out = g_out;
+    fa.saved_out = s_out;
+    if (int rc = head_scales(fa.grad_out, (long long)k.cnt * k.npi * 4, gmax, 5 * Lc + 2, gmax + n_slots - 1, scales, n_slots - 1, stream)) return rc;
+    const size_t slabH = (size_t)T * NT * 2048;            // bytes per (tiles, NT, 32, 32) slab
+    float* lay = scales + 2 * (4 * Lc + 2);
+    PwChainBuffers cb{base16, base16 + cl.m_off, base16 + cl.head_off, (const float*)(base16 + cl.winv_off), (const float*)(base16 + cl.anorm_off),
+                      scales, lay, a_c, a_amax, a_h + (size_t)Lc * slabH, ws + L.a_gy, a_g, a_go, gmax, nullptr};
+    const long long groups = (long long)k.cnt * ((k.tpi + 3) / 4);
+    long long step = groups / 1024;                       // dry-run sampling: at least 1024 tile groups (131 k points), every 32nd at most
+    step = step < 1 ? 1 : (step > 32 ? 32 : step);
+    // g_y through the layer matrices (dry run -> its scales), then the stored slabs and the mapping products (dry run -> g_mpre's scale)
+    for (int m = 0; m < Lc; ++m)
+        if (hipError_t e = launch_fill(scales + 2 * (3 * Lc + 2 + m), 1.0f, 2, stream)) return hip_fail(e, "fill");
+    if (hipError_t e = launch_chain_pre(fa, H, cb, 1, (int)step, stream)) return hip_fail(e, "chain_pre (dry run)");
+    if (hipError_t e = launch_pow2_scales(gmax + 3 * Lc + 2, Lc, scales + 2 * (3 * Lc + 2), stream)) return hip_fail(e, "pow2_scales");
+    for (int m = 0; m < Lc; ++m)      // the largest stored derivative of each layer over the chunk's points
+        if (hipError_t e = launch_absmax_bits(a_amax + (size_t)m * T * 32, T * 32, gmax + 4 * Lc + 2 + m, stream)) return hip_fail(e, "absmax");
+    if (hipError_t e = launch_pw_split_scales(gmax + 4 * Lc + 2, Lc, scales, lay, stream)) return hip_fail(e, "split_scales");
+    cb.sat = saturated;
+    if (hipError_t e = launch_chain_pre(fa, H, cb, 0, 1, stream)) return hip_fail(e, "chain_pre");
+    cb.sat = nullptr;
+    if (hipError_t e = launch_pw_gm(fa, H, cb, 1, (int)step, stream)) return hip_fail(e, "pw_gm (dry run)");
+    if (hipError_t e = launch_pow2_scales(gmax + 3 * Lc, 1, scales + 2 * (3 * Lc), stream)) return hip_fail(e, "pow2_scales");
+    cb.sat = saturated;
+    if (hipError_t e = launch_pw_gm(fa, H, cb, 0, 1, stream)) return hip_fail(e, "pw_gm");
+    // one reduction per matrix: G (n_rows of slab `slot`) against X (x_ct channel tiles), k_real columns from column k0 on
+    auto reduce = [&](const void* Gs, int g_ct, int n_rows, int slot, const void* X, int x_ct, int k0, int k_real, float* dW, float* db) {
+        return reduce16(k.cnt, k.tpi, n_rows, g_ct, x_ct, Gs, X, scales + 2 * slot + 1, dwarg, cs, k0, k_real, nullptr, 0, nullptr, nullptr, dW, db,
+                        nullptr, nullptr, stream);
+    };
+    const char* m16 = a_h + (size_t)Lc * slabH;
+    const size_t LH = (size_t)Lc * H;
+    for (int l = 0; l < Lc; ++l) {
+        const char* g_pre = a_g + (size_t)(3 * l) * slabH;
+        if (l == 0) {      // X = [feature | position]: the position's three columns
+            if (int rc = reduce(g_pre, NT, H, 3 * l, a_feat, 2, 32, 3, G->w[0], G->b[0])) return rc;
+        } else {
+            if (int rc = reduce(g_pre, NT, H, 3 * l, a_h + (size_t)(l - 1) * slabH, NT, 0, H, G->w[l], G->b[l])) return rc;
+        }
+        if (int rc = reduce(g_pre + slabH, NT, H, 3 * l + 1, m16, 8, 0, 256, G->map_w2 + (size_t)l * H * 256, G->map_b2 + (size_t)l * H)) return rc;
+        if (int rc = reduce(g_pre + 2 * slabH, NT, H, 3 * l + 2, m16, 8, 0, 256, G->map_w2 + (LH + (size_t)l * H) * 256, G->map_b2 + LH + (size_t)l * H))
+            return rc;
+    }
+    if (int rc = reduce(a_g + (size_t)(3 * Lc) * slabH, 8, 256, 3 * Lc, a_feat, 2, 0, 32, G->map_w1, G->map_b1)) return rc;
+    return reduce16(k.cnt, k.tpi, 4, 1, NT, a_go, a_h + (size_t)(Lc - 1) * slabH, scales + 2 * (n_slots - 1) + 1, (float*)(ws + L.dwh), (float*)(ws + L.csh),
+                    0, H, nullptr, 0, nullptr, nullptr, G->w_final, G->b_final, nullptr, nullptr, stream);
+}
+
+int pfilm_grads_complete(const cnerf_field_params* P, const cnerf_field_param_grads* G, int Lc, const char* who) {
+    if (!P->map_w1 || !P->map_w2 || !P->w_final) return fail(CNERF_EINVAL, "%s: mapping network / head parameters are NULL", who);
+    if (!G->map_w1 || !G->map_b1 || !G->map_w2 || !G->map_b2 || !G->w_final || !G->b_final)
+        return fail(CNERF_EINVAL, "%s: per-point FiLM needs the mapping network's and the head's gradient buffers", who);
+    for (int l = 0; l < Lc; ++l)
+        if (!G->w[l] || !G->b[l]) return fail(CNERF_EINVAL, "%s: gradient buffers of layer %d are NULL", who, l);
+    return CNERF_OK;
+}
 }  // namespace
 
 int cnerf_backward_workspace_bytes(const cnerf_cfg* cfg, int32_t backward_precision, int32_t images_per_chunk, int32_t have_act16, size_t* bytes) {
@@ -1054,18 +1281,11 @@ int cnerf_render_backward(const cnerf_cfg* cfg, int32_t bprec, int32_t cnt_max, 
     static const cnerf_rng no_rng = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
     if (!rng) rng = &no_rng;
     hipStream_t stream = (hipStream_t)stream_;
-    const int H = cfg->H, NT = H / 32, B = cfg->B;
+    const int B = cfg->B;
     const long long npi = (long long)cfg->R * cfg->R * cfg->S, tpi = (npi + 31) / 32;
     char* ws = (char*)workspace;
     float* gc = (float*)(ws + L.gc);
     float* gf = hier ? (float*)(ws + L.gf) : nullptr;
-    float* dwarg = (float*)(ws + L.dwarg);
-    float* cs = (float*)(ws + L.cs);
-    float* dwh = (float*)(ws + L.dwh);
-    float* csh = (float*)(ws + L.csh);
-    uint32_t* gmax = (uint32_t*)(ws + L.gmax);
-    float* scales = (float*)(ws + L.scales);
-    char* a_g = ws + L.a_g;
     char* a_go = ws + L.a_go;
 
     // 1. d(pixels, depth) -> d(rgb_sigma) of every coarse / fine sample
@@ -1074,23 +1294,14 @@ int cnerf_render_backward(const cnerf_cfg* cfg, int32_t bprec, int32_t cnt_max, 
         return rc;
 
     if (cfg->layer_kind[0] == CNERF_LAYER_PFILM) {
-        // ---- per-point FiLM family, half-precision backward: storing forward (field_pw16.hip), the two chain kernels with their dry runs
-        // (chain_pw16.hip), one weight_grad16 reduction per matrix: dW_l = g_pre_l^T y_{l-1}, dWm2 rows = (g_fr_l | g_ph_l)^T m, dWm1 = g_mpre^T feat, head
-        const int Lc = cfg->L, n_slots = 3 * Lc + 2;
-        if (!P->map_w1 || !P->map_w2 || !P->w_final) return fail(CNERF_EINVAL, "render_backward: mapping network / head parameters are NULL");
-        if (!G->map_w1 || !G->map_b1 || !G->map_w2 || !G->map_b2 || !G->w_final || !G->b_final)
-            return fail(CNERF_EINVAL, "render_backward: per-point FiLM needs the mapping network's and the head's gradient buffers");
-        for (int l = 0; l < Lc; ++l)
-            if (!G->w[l] || !G->b[l]) return fail(CNERF_EINVAL, "render_backward: gradient buffers of layer %d are NULL", l);
-        const PwChainLayout cl = pw_chain_layout(cfg);
-        const char* base16 = (const char*)packed_bwd;
+        // ---- per-point FiLM family, half-precision backward (chunk_pw16)
+        if (int rc = pfilm_grads_complete(P, G, cfg->L, "render_backward")) return rc;
         if (hipError_t e = hipMemsetAsync(a_go, 0, (size_t)cnt_max * tpi * 2048, stream)) return hip_fail(e, "memset");
         for (int pass = 0; pass < (hier ? 2 : 1); ++pass) {
             const float* g_out = pass ? gf : gc;
             const float* s_out = pass ? saved->fine_rgb_sigma : saved->coarse_rgb_sigma;
             for (int b0 = 0; b0 < B; b0 += cnt_max) {
                 const int cnt = b0 + cnt_max <= B ? cnt_max : B - b0;
-                const long long T = (long long)cnt * tpi;
                 // the pass's activations: kept by the forward (all images), or re-computed into the workspace
                 char* a_feat = have_act16 ? (char*)kept->act16[pass].feat : ws + L.a_feat;
                 char* a_h = have_act16 ? (char*)kept->act16[pass].h : ws + L.a_h;
@@ -1099,89 +1310,21 @@ int cnerf_render_backward(const cnerf_cfg* cfg, int32_t bprec, int32_t cnt_max, 
                 if (have_act16 && (!a_feat || !a_h || !a_c || !a_amax)) return fail(CNERF_EINVAL, "render_backward: act16 of pass %d is incomplete", pass);
                 FieldArgs fa;
                 if (int rc = pass_args(fa, cfg, pass, b0, cnt, vols, grad_vols, packed, nullptr, nullptr, cam2world, rng->u_strat, saved->fine_z)) return rc;
-                if (!have_act16)
-                    if (hipError_t e = launch_field_pw3(storing_args(fa, (long long)cnt * npi, a_feat, a_h, a_c, a_amax, a_g), H, stream))
-                        return hip_fail(e, "field kernel (fp16 activation store)");
-                fa.grad_out = g_out + (size_t)b0 * npi * 4;
-                fa.saved_out = s_out + (size_t)b0 * npi * 4;
-                if (int rc = head_scales(fa.grad_out, (long long)cnt * npi * 4, gmax, 5 * Lc + 2, gmax + n_slots - 1, scales, n_slots - 1, stream)) return rc;
-                const size_t slabH = (size_t)T * NT * 2048;            // bytes per (tiles, NT, 32, 32) slab
-                float* lay = scales + 2 * (4 * Lc + 2);
-                PwChainBuffers cb{base16, base16 + cl.m_off, base16 + cl.head_off, (const float*)(base16 + cl.winv_off), (const float*)(base16 + cl.anorm_off),
-                                  scales, lay, a_c, a_amax, a_h + (size_t)Lc * slabH, ws + L.a_gy, a_g, a_go, gmax, nullptr};
-                const long long groups = (long long)cnt * ((tpi + 3) / 4);
-                long long step = groups / 1024;                       // dry-run sampling: at least 1024 tile groups (131 k points), every 32nd at most
-                step = step < 1 ? 1 : (step > 32 ? 32 : step);
-                // g_y through the layer matrices (dry run -> its scales), then the stored slabs and the mapping products (dry run -> g_mpre's scale)
-                for (int m = 0; m < Lc; ++m)
-                    if (hipError_t e = launch_fill(scales + 2 * (3 * Lc + 2 + m), 1.0f, 2, stream)) return hip_fail(e, "fill");
-                if (hipError_t e = launch_chain_pre(fa, H, cb, 1, (int)step, stream)) return hip_fail(e, "chain_pre (dry run)");
-                if (hipError_t e = launch_pow2_scales(gmax + 3 * Lc + 2, Lc, scales + 2 * (3 * Lc + 2), stream)) return hip_fail(e, "pow2_scales");
-                for (int m = 0; m < Lc; ++m)      // the largest stored derivative of each layer over the chunk's points
-                    if (hipError_t e = launch_absmax_bits(a_amax + (size_t)m * T * 32, T * 32, gmax + 4 * Lc + 2 + m, stream)) return hip_fail(e, "absmax");
-                if (hipError_t e = launch_pw_split_scales(gmax + 4 * Lc + 2, Lc, scales, lay, stream)) return hip_fail(e, "split_scales");
-                cb.sat = saturated;
-                if (hipError_t e = launch_chain_pre(fa, H, cb, 0, 1, stream)) return hip_fail(e, "chain_pre");
-                cb.sat = nullptr;
-                if (hipError_t e = launch_pw_gm(fa, H, cb, 1, (int)step, stream)) return hip_fail(e, "pw_gm (dry run)");
-                if (hipError_t e = launch_pow2_scales(gmax + 3 * Lc, 1, scales + 2 * (3 * Lc), stream)) return hip_fail(e, "pow2_scales");
-                cb.sat = saturated;
-                if (hipError_t e = launch_pw_gm(fa, H, cb, 0, 1, stream)) return hip_fail(e, "pw_gm");
-                // one reduction per matrix: G (n_rows of slab `slot`) against X (x_ct channel tiles), k_real columns from column k0 on
-                auto reduce = [&](const void* Gs, int g_ct, int n_rows, int slot, const void* X, int x_ct, int k0, int k_real, float* dW, float* db) {
-                    return reduce16(cnt, tpi, n_rows, g_ct, x_ct, Gs, X, scales + 2 * slot + 1, dwarg, cs, k0, k_real, nullptr, 0, nullptr, nullptr, dW, db,
-                                    nullptr, nullptr, stream);
-                };
-                const char* m16 = a_h + (size_t)Lc * slabH;
-                const size_t LH = (size_t)Lc * H;
-                for (int l = 0; l < Lc; ++l) {
-                    const char* g_pre = a_g + (size_t)(3 * l) * slabH;
-                    if (l == 0) {      // X = [feature | position]: the position's three columns
-                        if (int rc = reduce(g_pre, NT, H, 3 * l, a_feat, 2, 32, 3, G->w[0], G->b[0])) return rc;
-                    } else {
-                        if (int rc = reduce(g_pre, NT, H, 3 * l, a_h + (size_t)(l - 1) * slabH, NT, 0, H, G->w[l], G->b[l])) return rc;
-                    }
-                    if (int rc = reduce(g_pre + slabH, NT, H, 3 * l + 1, m16, 8, 0, 256, G->map_w2 + (size_t)l * H * 256, G->map_b2 + (size_t)l * H)) return rc;
-                    if (int rc = reduce(g_pre + 2 * slabH, NT, H, 3 * l + 2, m16, 8, 0, 256, G->map_w2 + (LH + (size_t)l * H) * 256, G->map_b2 + LH + (size_t)l * H))
-                        return rc;
-                }
-                if (int rc = reduce(a_g + (size_t)(3 * Lc) * slabH, 8, 256, 3 * Lc, a_feat, 2, 0, 32, G->map_w1, G->map_b1)) return rc;
-                if (int rc = reduce16(cnt, tpi, 4, 1, NT, a_go, a_h + (size_t)(Lc - 1) * slabH, scales + 2 * (n_slots - 1) + 1, dwh, csh, 0, H, nullptr, 0,
-                                      nullptr, nullptr, G->w_final, G->b_final, nullptr, nullptr, stream))
+                if (int rc = chunk_pw16(cfg, L, ws, packed_bwd, fa, Chunk{b0, cnt, npi, tpi}, g_out + (size_t)b0 * npi * 4, s_out + (size_t)b0 * npi * 4,
+                                        a_feat, a_h, a_c, a_amax, !have_act16, G, saturated, stream))
                     return rc;
             }
         }
         return CNERF_OK;
     }
 
-    // the matrices in slab order (a residual block: fc1, fc2), their kinds and gradient buffers
-    const float *Wm[2 * CNERF_MAX_LAYERS], *bm[2 * CNERF_MAX_LAYERS];
-    float *dWm[2 * CNERF_MAX_LAYERS], *dbm[2 * CNERF_MAX_LAYERS];
-    int film_of[2 * CNERF_MAX_LAYERS];
-    int nm = 0, nfilm = 0;
-    for (int l = 0; l < cfg->L; ++l) {
-        const bool res = cfg->layer_kind[l] == CNERF_LAYER_RES;
-        if (!P->w[l] || !P->b[l] || (res && (!P->w2[l] || !P->b2[l]))) return fail(CNERF_EINVAL, "render_backward: parameters of layer %d are NULL", l);
-        Wm[nm] = P->w[l]; bm[nm] = P->b[l]; dWm[nm] = G->w[l]; dbm[nm] = G->b[l];
-        film_of[nm] = cfg->layer_kind[l] == CNERF_LAYER_FILM ? nfilm++ : -1;
-        ++nm;
-        if (res) {
-            Wm[nm] = P->w2[l]; bm[nm] = P->b2[l]; dWm[nm] = G->w2[l]; dbm[nm] = G->b2[l];
-            film_of[nm] = -1;
-            ++nm;
-        }
-    }
-    const int film_stride = pl.n_film * H;
-    // matrix m's slice of freq / grad_freq / grad_phase for the chunk from image b0 (NULL unless m is a FiLM matrix)
-    auto film = [&](auto* t, int m, int b0) { return film_of[m] >= 0 ? t + (size_t)b0 * film_stride + (size_t)film_of[m] * H : nullptr; };
+    MatrixSet ms;
+    if (int rc = matrix_set(cfg, P, G, "render_backward", ms)) return rc;
 
     if (bprec == CNERF_PREC_FP16) {
-        // ---- FiLM / plain-sine / residual networks, half-precision backward (bwd16.hip): per chunk the storing re-run (fp16x3 kernel), the
-        // chain's dry run for the per-matrix scales, the chain, the patch scatter of the input-tile gradients, one weight_grad16 per matrix
-        Chain16Layout cl;
-        if (int rc = chain16_layout(cfg, cl)) return rc;
-        const char* base16 = (const char*)packed_bwd;
-        const float* winv = (const float*)(base16 + cl.winv_off);
+        // ---- FiLM / plain-sine / residual networks, half-precision backward (chunk16); the chain stores its input-tile gradients (fp32,
+        // 128 B per point) and scatter_sorted_kernel adds them to the volume pre-reduced per pixel patch (scatter_patch.hip), or the chain
+        // adds them itself (CNERF_SCATTER=chain)
         float* gin = (float*)(ws + L.a_gin);
         const bool patch = !scatter_by_chain();
         // only channels 0..3 of a row are ever written: the rest must read as zero
@@ -1191,82 +1334,246 @@ int cnerf_render_backward(const cnerf_cfg* cfg, int32_t bprec, int32_t cnt_max, 
             const float* s_out = pass ? saved->fine_rgb_sigma : saved->coarse_rgb_sigma;
             for (int b0 = 0; b0 < B; b0 += cnt_max) {
                 const int cnt = b0 + cnt_max <= B ? cnt_max : B - b0;
-                const long long T = (long long)cnt * tpi;
                 void* a_feat = have_act16 ? kept->act16[pass].feat : (void*)(ws + L.a_feat);
                 void* a_h = have_act16 ? kept->act16[pass].h : (void*)(ws + L.a_h);
                 void* a_c = have_act16 ? kept->act16[pass].c : (void*)(ws + L.a_c);
                 if (have_act16 && (!a_feat || !a_h || !a_c)) return fail(CNERF_EINVAL, "render_backward: act16 of pass %d is incomplete", pass);
-                if (int rc = head_scales(g_out + (size_t)b0 * npi * 4, (long long)cnt * npi * 4, gmax, L.n_mats + 2, gmax + L.n_mats + 1, scales, L.n_mats,
-                                         stream))
-                    return rc;
-                const long long groups = (long long)cnt * ((tpi + 3) / 4);
-                long long step = groups / 2048;                       // dry-run sampling: every 16th tile group once there are plenty
-                step = step < 1 ? 1 : (step > 16 ? 16 : step);
-                // the storing re-run and the dry run leave the gradient volumes alone; the chain (fc) adds to them
                 FieldArgs fa, fc;
                 if (int rc = pass_args(fa, cfg, pass, b0, cnt, vols, nullptr, packed, freq, phase, cam2world, rng->u_strat, saved->fine_z)) return rc;
                 if (int rc = pass_args(fc, cfg, pass, b0, cnt, vols, grad_vols, packed, freq, phase, cam2world, rng->u_strat, saved->fine_z)) return rc;
-                if (!have_act16)
-                    if (hipError_t e = launch_field_h3(storing_args(fa, (long long)cnt * npi, a_feat, a_h, a_c, nullptr, a_g), H, stream))
-                        return hip_fail(e, "field kernel (fp16 activation store)");
-                fa.grad_out = fc.grad_out = g_out + (size_t)b0 * npi * 4;
-                fa.saved_out = fc.saved_out = s_out + (size_t)b0 * npi * 4;
-                if (hipError_t e = launch_chain16(fa, H, base16, base16 + cl.head_off, winv, scales, a_c, nullptr, nullptr, gmax, nullptr, cl.n_mats, 1, (int)step,
-                                                  stream))
-                    return hip_fail(e, "chain16 (dry run)");
-                if (hipError_t e = launch_pow2_scales(gmax, L.n_mats, scales, stream)) return hip_fail(e, "pow2_scales");
-                // the chain stores its input-tile gradients (fp32, 128 B per point) and scatter_sorted_kernel adds them to the volume pre-reduced
-                // per pixel patch (scatter_patch.hip), or the chain adds them itself (CNERF_SCATTER=chain)
                 fc.gin = patch ? gin : nullptr;
-                if (hipError_t e = launch_chain16(fc, H, base16, base16 + cl.head_off, winv, scales, a_c, a_g, a_go, nullptr, saturated, cl.n_mats, 0, 1, stream))
-                    return hip_fail(e, "chain16");
-                if (patch)
-                    if (hipError_t e = launch_scatter_patch(fc, gin, stream)) return hip_fail(e, "scatter_patch");
-                const size_t slab = (size_t)T * NT * 2048;             // bytes per matrix in a_h / a_g
-                for (int m = 0; m < L.n_mats; ++m) {
-                    const int x_ct = m == 0 ? L.n_in : NT;
-                    const void* X = m == 0 ? a_feat : (const void*)((const char*)a_h + (size_t)(m - 1) * slab);
-                    if (int rc = reduce16(cnt, tpi, H, NT, x_ct, a_g + (size_t)m * slab, X, scales + 2 * m + 1, dwarg, cs, 0, m == 0 ? L.k0 : H, film(freq, m, b0),
-                                          film_stride, Wm[m], bm[m], dWm[m], dbm[m], film(grad_freq, m, b0), film(grad_phase, m, b0), stream))
-                        return rc;
-                }
-                if (int rc = reduce16(cnt, tpi, 4, 1, NT, a_go, (const char*)a_h + (size_t)(L.n_mats - 1) * slab, scales + 2 * L.n_mats + 1, dwh, csh, 0, H,
-                                      nullptr, 0, nullptr, nullptr, G->w_final, G->b_final, nullptr, nullptr, stream))
+                if (int rc = chunk16(cfg, ms, L, ws, packed_bwd, fa, fc, Chunk{b0, cnt, npi, tpi}, g_out + (size_t)b0 * npi * 4, s_out + (size_t)b0 * npi * 4,
+                                     a_feat, a_h, a_c, !have_act16, freq, G, grad_freq, grad_phase, saturated, stream))
                     return rc;
             }
         }
         return CNERF_OK;
     }
 
-    // ---- exact fp32 backward: per chunk cnerf_field_backward (re-run in cfg->precision, fp32 chain, scatter), one weight_grad per matrix
+    // ---- exact fp32 backward (chunk32)
     for (int pass = 0; pass < (hier ? 2 : 1); ++pass) {
         const float* g_out = pass ? gf : gc;
         const float* s_out = pass ? saved->fine_rgb_sigma : saved->coarse_rgb_sigma;
         const uint8_t* drop = pass ? rng->drop_fine : rng->drop_coarse;
         for (int b0 = 0; b0 < B; b0 += cnt_max) {
             const int cnt = b0 + cnt_max <= B ? cnt_max : B - b0;
-            const size_t n = (size_t)cnt * npi;
-            float* a_feat = (float*)(ws + L.a_feat);
-            float* a_h = (float*)(ws + L.a_h);
-            float* a_c = (float*)(ws + L.a_c);
-            if (int rc = cnerf_field_backward(cfg, pass, b0, cnt, vols, packed, (const float*)packed_bwd, freq, phase, cam2world, rng->u_strat, saved->fine_z,
-                                              g_out, s_out, a_feat, a_h, a_c, (float*)a_g, (float*)a_go, grad_vols, drop, stream_))
+            FieldArgs fa;
+            if (int rc = pass_args(fa, cfg, pass, b0, cnt, vols, grad_vols, packed, freq, phase, cam2world, rng->u_strat, saved->fine_z)) return rc;
+            set_dropout(fa, cfg, drop, pass == 0 ? PHILOX_DROP_COARSE : PHILOX_DROP_FINE, npi);
+            if (int rc = chunk32(cfg, ms, L, ws, fa, Chunk{b0, cnt, npi, tpi}, (const float*)packed_bwd, g_out + (size_t)b0 * npi * 4,
+                                 s_out + (size_t)b0 * npi * 4, freq, G, grad_freq, grad_phase, stream))
                 return rc;
-            for (int m = 0; m < L.n_mats; ++m) {
-                const int K = m == 0 ? 32 * L.n_in : H;
-                const float* X = m == 0 ? a_feat : a_h + (size_t)(m - 1) * n * H;
-                if (hipError_t e = hipMemsetAsync(dwarg, 0, (size_t)cnt * H * K * sizeof(float), stream)) return hip_fail(e, "memset");
-                if (hipError_t e = hipMemsetAsync(cs, 0, (size_t)cnt * H * sizeof(float), stream)) return hip_fail(e, "memset");
-                if (int rc = cnerf_weight_grad(cnt, npi, H, K, (const float*)a_g + (size_t)m * n * H, X, dwarg, cs, stream_)) return rc;
-                if (hipError_t e = launch_param_reduce(cnt, H, K, m == 0 ? L.k0 : H, dwarg, cs, film(freq, m, b0), film_stride, Wm[m], bm[m], dWm[m], dbm[m],
-                                                       film(grad_freq, m, b0), film(grad_phase, m, b0), stream))
-                    return hip_fail(e, "param_reduce");
-            }
-            if (G->w_final && G->b_final)
-                if (hipError_t e = launch_head_grad32((const float*)a_go, a_h + (size_t)(L.n_mats - 1) * n * H, (long long)n, H, G->w_final, G->b_final, stream))
-                    return hip_fail(e, "head_grad32");
         }
     }
+    return CNERF_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// gradients of a field query (autograd twin of cnerf_field_forward)
+// ---------------------------------------------------------------------------------------------------------------------
+namespace {
+// Behind the chunk buffers of chunk_layout(cnt = 1, npi = points_per_chunk): the input-gradient rows of the position gradient
+// (points_per_chunk, 256) fp32 -- feature columns, then the xyz columns -- and, with dropout, the keep bytes of the chunk
+// (n_drop, points_per_chunk, H).
+struct QueryLayout {
+    BackwardLayout L;
+    size_t rows, mask, total;
+};
+int query_layout(const cnerf_cfg* c, int bprec, long long ppc, QueryLayout& Q) {
+    if (ppc < 1) return fail(CNERF_EINVAL, "field_query_backward: points_per_chunk=%lld must be >= 1", ppc);
+    if (int rc = chunk_layout(c, bprec, 1, (size_t)ppc, 0, false, false, false, "field_query_backward", Q.L)) return rc;
+    int n_drop = 0;
+    for (int l = 0; l < c->L; ++l) n_drop += c->layer_kind[l] != CNERF_LAYER_RES;
+    Q.rows = Q.L.total;
+    Q.mask = Q.rows + align256((size_t)ppc * 256 * sizeof(float));
+    Q.total = Q.mask + align256(c->drop_p > 0.0f ? (size_t)n_drop * ppc * c->H : 0);
+    return CNERF_OK;
+}
+}  // namespace
+
+int cnerf_field_query_backward_workspace_bytes(const cnerf_cfg* cfg, int32_t backward_precision, int64_t points_per_chunk, size_t* bytes) {
+    g_err[0] = 0;
+    if (int rc = check_cfg(cfg, false)) return rc;
+    QueryLayout Q;
+    if (int rc = query_layout(cfg, backward_precision, (long long)points_per_chunk, Q)) return rc;
+    if (bytes) *bytes = Q.total;
+    return CNERF_OK;
+}
+
+int cnerf_field_query_backward(const cnerf_cfg* cfg, int32_t bprec, int64_t points_per_chunk, const cnerf_volumes* vols, const cnerf_field_params* P,
+                               const float* packed, const void* packed_bwd, const float* freq, const float* phase, const float* points,
+                               int64_t n_per_image, const float* saved_rgb_sigma, const float* grad_rgb_sigma, const cnerf_field_param_grads* G,
+                               float* grad_freq, float* grad_phase, const cnerf_grad_volumes* grad_vols, float* grad_points, uint32_t* saturated,
+                               void* workspace, void* stream_) {
+    g_err[0] = 0;
+    if (int rc = check_cfg(cfg, false)) return rc;
+    QueryLayout Q;
+    if (int rc = query_layout(cfg, bprec, (long long)points_per_chunk, Q)) return rc;
+    const BackwardLayout& L = Q.L;
+    if (!vols || !P || !packed || !packed_bwd || !points || !saved_rgb_sigma || !grad_rgb_sigma || !G || !grad_vols || !workspace || n_per_image < 1)
+        return fail(CNERF_EINVAL, "field_query_backward: NULL argument or no points");
+    for (int i = 0; i < n_levels_of(cfg); ++i)
+        if (!grad_vols->level[i]) return fail(CNERF_EINVAL, "field_query_backward: gradient volume %d is NULL", i);
+    const PackedLayout pl = packed_layout(cfg);
+    if (pl.n_film && (!freq || !phase || !grad_freq || !grad_phase))
+        return fail(CNERF_EINVAL, "field_query_backward: FiLM layers need freq, phase and their gradient buffers");
+    const bool pfilm = cfg->layer_kind[0] == CNERF_LAYER_PFILM;
+    if (pfilm) {
+        if (int rc = pfilm_grads_complete(P, G, cfg->L, "field_query_backward")) return rc;
+        if (grad_points && !P->w[0]) return fail(CNERF_EINVAL, "field_query_backward: layer 0 weight is NULL");
+    }
+    MatrixSet ms;
+    if (!pfilm)
+        if (int rc = matrix_set(cfg, P, G, "field_query_backward", ms)) return rc;
+    hipStream_t stream = (hipStream_t)stream_;
+    const int B = cfg->B, H = cfg->H, NT = H / 32;
+    const long long n = (long long)n_per_image, ppc = points_per_chunk < n ? (long long)points_per_chunk : n;
+    char* ws = (char*)workspace;
+    float* rows = (float*)(ws + Q.rows);
+    uint8_t* mask = (uint8_t*)(ws + Q.mask);
+    // only channels 0..3 of a row of the half-precision head gradient are ever written: the rest must read as zero
+    if (bprec == CNERF_PREC_FP16)
+        if (hipError_t e = hipMemsetAsync(ws + L.a_go, 0, (size_t)((ppc + 31) / 32) * 2048, stream)) return hip_fail(e, "memset");
+    for (int b = 0; b < B; ++b) {
+        for (long long p0 = 0; p0 < n; p0 += ppc) {
+            const long long np = p0 + ppc <= n ? ppc : n - p0;
+            const Chunk k{b, 1, np, (np + 31) / 32};
+            const size_t row0 = (size_t)b * n + p0;
+            const float* pts = points + row0 * 3;
+            const float* g_out = grad_rgb_sigma + row0 * 4;
+            const float* s_out = saved_rgb_sigma + row0 * 4;
+            // the chunk's field pass: image b, points [p0, p0 + np); fa without, fc with the gradient volumes
+            FieldArgs fa, fc;
+            if (int rc = fill_field_args(fa, cfg, vols, nullptr, packed, freq, phase, b)) return rc;
+            fa.mode = FIELD_MODE_POINTS;
+            fa.points = pts;
+            set_points(fa, 1, np);
+            set_dropout(fa, cfg, nullptr, PHILOX_DROP_POINTS, np);
+            if (cfg->drop_p > 0.0f) {
+                // the forward's decisions of these points (Philox stream PHILOX_DROP_POINTS at their index in the whole call), as keep bytes
+                // with chunk-local rows: the kernels index them by (image0 + b) * n_per_image + point = the point's row in the chunk
+                if (hipError_t e = launch_drop_keep(fa.philox, PHILOX_DROP_POINTS, fa.drop_thresh, fa.n_drop, H, (unsigned long long)row0, np, mask, stream))
+                    return hip_fail(e, "drop_keep");
+                fa.drop_mask = mask;
+                fa.drop_points = np;
+                fa.image0 = 0;
+            }
+            fc = fa;
+            for (int i = 0; i < n_levels_of(cfg); ++i) {
+                const int V = level_V_of(cfg, i);
+                fc.lvl_grad[i] = grad_vols->level[i] + (size_t)b * V * V * V * level_C_of(cfg, i);
+            }
+            fc.gin = nullptr;            // points are no pixel patches: the chain adds its input-tile gradients with its own atomics
+            if (pfilm) {
+                if (int rc = chunk_pw16(cfg, L, ws, packed_bwd, fc, k, g_out, s_out, ws + L.a_feat, ws + L.a_h, ws + L.a_c, (float*)(ws + L.a_amax), true, G,
+                                        saturated, stream))
+                    return rc;
+            } else if (bprec == CNERF_PREC_FP16) {
+                if (int rc = chunk16(cfg, ms, L, ws, packed_bwd, fa, fc, k, g_out, s_out, ws + L.a_feat, ws + L.a_h, ws + L.a_c, true, freq, G, grad_freq,
+                                     grad_phase, saturated, stream))
+                    return rc;
+            } else {
+                if (int rc = chunk32(cfg, ms, L, ws, fc, k, (const float*)packed_bwd, g_out, s_out, freq, G, grad_freq, grad_phase, stream)) return rc;
+            }
+            if (!grad_points) continue;
+            // position gradient: layer 0's input gradient from the chunk's layer-0 gradient slab, then its lookup term plus the xyz columns
+            const float* scales = (const float*)(ws + L.scales);
+            InputGradArgs ig{};
+            ig.out = rows;
+            ig.ldo = 256;
+            ig.n = np;
+            if (pfilm) {        // feature: g_mpre Wm1 (slot 3 L, 8 channel tiles); xyz: g_pre_0 W_0 (slot 0)
+                const size_t slabH = (size_t)k.tpi * NT * 2048;
+                ig.g16 = ws + L.a_g + (size_t)(3 * cfg->L) * slabH;
+                ig.g_ct = 8;
+                ig.inv_scale = scales + 2 * (3 * cfg->L) + 1;
+                ig.W = P->map_w1;
+                ig.K = 256;
+                ig.k_in = cfg->C;
+                if (hipError_t e = launch_input_grad(ig, stream)) return hip_fail(e, "input_grad");
+                ig.g16 = ws + L.a_g;
+                ig.g_ct = NT;
+                ig.inv_scale = scales + 1;
+                ig.W = P->w[0];
+                ig.K = H;
+                ig.k_in = 3;
+                ig.out = rows + cfg->C;
+            } else {            // [feature | xyz] = (g_arg_0 (.) freq_0) W_0
+                if (bprec == CNERF_PREC_FP16) {
+                    ig.g16 = ws + L.a_g;
+                    ig.g_ct = NT;
+                    ig.inv_scale = scales + 1;
+                } else {
+                    ig.g32 = (const float*)(ws + L.a_g);
+                    ig.ldg = H;
+                }
+                ig.f = ms.film(freq, 0, b);
+                ig.W = ms.W[0];
+                ig.K = H;
+                ig.k_in = L.k0;
+            }
+            if (hipError_t e = launch_input_grad(ig, stream)) return hip_fail(e, "input_grad");
+            PointsGradArgs pg{};
+            for (int i = 0; i < n_levels_of(cfg); ++i) {
+                const int V = level_V_of(cfg, i), Cl = level_C_of(cfg, i);
+                pg.lvl_vol[i] = vols->level[i] + (size_t)b * V * V * V * Cl;
+                pg.lvl_V[i] = V;
+                pg.lvl_C[i] = Cl;
+            }
+            pg.n_levels = n_levels_of(cfg);
+            pg.points = pts;
+            pg.gfeat = rows;
+            pg.ldf = 256;
+            pg.gxyz = (pfilm || (cfg->flags & CNERF_F_INPUT_XYZ)) ? rows + cfg->C : nullptr;
+            pg.ldx = 256;
+            pg.grad_points = grad_points + row0 * 3;
+            pg.n = np;
+            pg.half_voxel = cfg->voxel_length / 2.0f;
+            if (hipError_t e = launch_points_lookup_grad(pg, stream)) return hip_fail(e, "points_lookup_grad");
+        }
+    }
+    return CNERF_OK;
+}
+
+int cnerf_feature_points_grad(const cnerf_cfg* cfg, const cnerf_volumes* vols, const float* points, int64_t n_per_image, const float* grad_feat,
+                              float* grad_points, void* stream) {
+    g_err[0] = 0;
+    if (int rc = check_cfg(cfg, false)) return rc;
+    if (!vols || !points || !grad_feat || !grad_points || n_per_image < 1) return fail(CNERF_EINVAL, "feature_points_grad: bad argument");
+    for (int b = 0; b < cfg->B; ++b) {
+        PointsGradArgs pg{};
+        for (int i = 0; i < n_levels_of(cfg); ++i) {
+            const int V = level_V_of(cfg, i), Cl = level_C_of(cfg, i);
+            if (!vols->level[i]) return fail(CNERF_EINVAL, "feature_points_grad: volume level %d is NULL", i);
+            pg.lvl_vol[i] = vols->level[i] + (size_t)b * V * V * V * Cl;
+            pg.lvl_V[i] = V;
+            pg.lvl_C[i] = Cl;
+        }
+        const size_t row0 = (size_t)b * n_per_image;
+        pg.n_levels = n_levels_of(cfg);
+        pg.points = points + row0 * 3;
+        pg.gfeat = grad_feat + row0 * cfg->C;
+        pg.ldf = cfg->C;
+        pg.grad_points = grad_points + row0 * 3;
+        pg.n = n_per_image;
+        pg.half_voxel = cfg->voxel_length / 2.0f;
+        if (hipError_t e = launch_points_lookup_grad(pg, (hipStream_t)stream)) return hip_fail(e, "points_lookup_grad");
+    }
+    return CNERF_OK;
+}
+
+int cnerf_dropout_keep(const cnerf_cfg* cfg, uint32_t stream_id, int64_t point0, int64_t n_points, uint8_t* mask, void* stream) {
+    g_err[0] = 0;
+    if (int rc = check_cfg(cfg, false)) return rc;
+    if (!mask || point0 < 0 || n_points < 1 || stream_id < PHILOX_DROP_COARSE || stream_id > PHILOX_DROP_POINTS || !(cfg->drop_p > 0.0f))
+        return fail(CNERF_EINVAL, "dropout_keep: bad argument (drop_p > 0, stream 4..6)");
+    const double th = (double)cfg->drop_p * 4294967296.0 + 0.5;
+    const uint32_t thresh = th >= 4294967295.0 ? 0xffffffffu : (uint32_t)th;
+    int n_drop = 0;
+    for (int l = 0; l < cfg->L; ++l) n_drop += cfg->layer_kind[l] != CNERF_LAYER_RES;
+    if (hipError_t e = launch_drop_keep(philox_of(cfg), stream_id, thresh, n_drop, cfg->H, (unsigned long long)point0, (long long)n_points, mask,
+                                        (hipStream_t)stream))
+        return hip_fail(e, "drop_keep");
     return CNERF_OK;
 }
 

@@ -190,6 +190,39 @@ hipError_t launch_gather(const GatherArgs& a, hipStream_t stream);
 hipError_t launch_scatter_patch(const FieldArgs& f, const float* gin, hipStream_t stream);
 hipError_t launch_scatter(const GatherArgs& a, const float* grad_feat, float* grad_fvol, hipStream_t stream);
 
+// points_grad.hip: the position gradient of a field query (never launched by the render path)
+struct InputGradArgs {       // out (n, ldo)[:, 0:k_in) = (g (.) f) W * inv_scale
+    const float* g32;        // fp32 rows (n, ldg), or null: ...
+    const void* g16;         // ... a TB16 fp16 slab with g_ct channel tiles (chunk-local tiles: point p is row p % 32 of tile p / 32)
+    long long ldg;
+    int g_ct;
+    const float* inv_scale;  // device scalar undoing the slab's scale, or null
+    const float* f;          // (K) factor per row of W (FiLM frequencies of the layer), or null
+    const float* W;          // (K, k_in) row-major
+    int K, k_in;             // K a multiple of 32
+    float* out;
+    long long ldo;
+    long long n;
+};
+struct PointsGradArgs {      // grad_points (n,3) += lookup term of gfeat + gxyz
+    const float* lvl_vol[CNERF_MAX_LEVELS];  // one image's channel-last levels
+    int lvl_V[CNERF_MAX_LEVELS];
+    int lvl_C[CNERF_MAX_LEVELS];
+    int n_levels;
+    const float* points;     // (n,3)
+    const float* gfeat;      // (n, ldf): the levels' channels side by side
+    long long ldf;
+    const float* gxyz;       // (n, ldx) d loss / d xyz of layer 0's input, or null
+    long long ldx;
+    float* grad_points;      // (n,3) accumulated into
+    long long n;
+    float half_voxel;
+};
+hipError_t launch_input_grad(const InputGradArgs& a, hipStream_t stream);
+hipError_t launch_points_lookup_grad(const PointsGradArgs& a, hipStream_t stream);
+hipError_t launch_drop_keep(const PhiloxKey& k, uint32_t stream_id, uint32_t thresh, int n_drop, int H, unsigned long long gp0,
+                            long long n_points, uint8_t* mask, hipStream_t stream);
+
 hipError_t launch_weight_grad(int cnt, long long npi, int H, int K, const float* G, const float* X, float* dW, float* colsum,
                               hipStream_t stream);
 hipError_t launch_param_reduce(int cnt, int rows, int ld, int k_real, const float* dWarg, const float* cs, const float* freq, int film_stride,

@@ -198,7 +198,16 @@ def gather_features(net, fvol_cl, points):
 
 
 def field_forward(net, fvol, freq, phase, points, fvol_is_channel_last=False, drop=None):
-    """rgb_sigma (B,n,4) of `net` at explicit world points (B,n,3).  drop = (p, (seed, offset)): dropout of a training-mode call."""
+    """rgb_sigma (B,n,4) of `net` at explicit world points (B,n,3).  drop = (p, (seed, offset)): dropout of a training-mode call.
+    Differentiable (FieldQueryFunction) w.r.t. the volume(s), freq / phase, the points and the field parameters when grad mode is
+    on and one of them requires grad; otherwise the plain forward without an autograd node."""
+    vols = as_levels(fvol)
+    if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (freq, phase, points, *vols, *net.field_params())):
+        return FieldQueryFunction.apply(net, drop, bool(fvol_is_channel_last), freq, phase, points, len(vols), *vols, *net.field_params())
+    return _field_forward(net, fvol, freq, phase, points, fvol_is_channel_last, drop)
+
+
+def _field_forward(net, fvol, freq, phase, points, fvol_is_channel_last=False, drop=None):
     points = _f32(points)
     B, n = points.shape[0], points.shape[1]
     levels = [_f32(v) for v in as_levels(fvol)] if fvol_is_channel_last else channel_last_levels(fvol)
@@ -337,17 +346,18 @@ PHASE_TIMER = None              # an object with begin() / end(name, start) (tra
 ACT_BUDGET_BYTES = 128 << 30    # chunk buffers of the per-point FiLM backward: at most this much, and MEMORY_FRACTION of what is free
 
 
-def _pfilm_backward(net, o, cfg, levels, cam2world, rng, saved, gc, gf):
+def _pfilm_backward(net, o, cfg, levels, cam2world, rng, saved, gc, gf, query=None):
     """Field gradients of the per-point FiLM family (TALLSIREN, siren.py:232-331).  Per pass and chunk of images
     cnerf_field_backward re-runs the forward storing its rows, runs the gradient chain of the eight FiLM layers on the MFMA
     units and leaves g_pre_l = d/d(W_l y_{l-1} + b_l) and G = d/d(output of the mapping network's second Linear) in the
     chunk buffers (include/cnerf.h); what remains are reductions over those matrices: cnerf_weight_grad for the (H,H) layer
-    matrices, library GEMMs for the (2LH, 256) mapping Linear and the two thin ones, cnerf_scatter_features for the volume."""
+    matrices, library GEMMs for the (2LH, 256) mapping Linear and the two thin ones, cnerf_scatter_features for the volume.
+    query = dict(points (B,n,3), g_out / saved_out (B,n,4), drop, grad_points (B,n,3) or None): the same for a field query, per
+    image and range of points (query_chunk) through cnerf_field_backward_points, with the forward's dropout decisions of that
+    range (cnerf_dropout_keep); grad_points receives g_pre_0 W_0 plus the lookup term of d feat (cnerf_feature_points_grad)."""
     fvol = levels[0]
-    B, R, S, hier = o["B"], o["R"], o["S"], o["hier"]
     dev = fvol.device
     H, nl = int(net.hidden_dim), len(net.spec.layers)
-    npi = R * R * S
     vs = volumes_struct(levels)
     packed = pack_field(net, cfg)
     packed_t = pack_field_transposed(net, cfg)
@@ -355,58 +365,97 @@ def _pfilm_backward(net, o, cfg, levels, cam2world, rng, saved, gc, gf):
     grads = [torch.zeros_like(p) for p in ps]
     g_level = torch.zeros_like(fvol)
     gvs = volumes_struct([g_level])
-    c_rs, c_z, f_rs, f_z, c_pts, f_pts = saved[:6]
-    per_image = npi * (32 + 256 + 7 * nl * H + 4) * 4
-    nb = max(1, min(B, int(min(ACT_BUDGET_BYTES, MEMORY_FRACTION * free_device_bytes(dev))) // per_image))
-    u_strat = _f32(rng.get("u_strat"))
+    per_point = (32 + 256 + 7 * nl * H + 4) * 4
     act = None
+
+    def chunk_buffers(n):
+        nonlocal act
+        if act is None or act[0].shape[0] != n:
+            act = None          # release the previous chunk before allocating a differently sized one
+            act = (torch.empty((n, 32), dtype=torch.float32, device=dev),
+                   torch.empty(nl * n * H + n * 256, dtype=torch.float32, device=dev),
+                   torch.empty((3 * nl, n, H), dtype=torch.float32, device=dev),
+                   torch.empty(3 * nl * n * H, dtype=torch.float32, device=dev),
+                   torch.empty((n, 4), dtype=torch.float32, device=dev))
+        return act
+
+    def finish(key, b0, cnt, npi, pts, g_pts):
+        """The reductions of one chunk (cnt images of npi points from image b0, positions pts (cnt*npi, 3)) and, with g_pts, its position gradient."""
+        n = cnt * npi
+        a_feat, a_h, a_c, a_g, a_go = act
+        y, m = a_h[:nl * n * H].view(nl, n, H), a_h[nl * n * H:].view(n, 256)
+        gp, G = a_g[:nl * n * H].view(nl, n, H), a_g[nl * n * H:].view(n, 2 * nl * H)
+        if DEBUG_CAPTURE is not None:
+            DEBUG_CAPTURE.setdefault(key, dict(feat=a_feat.clone(), y=y.clone(), m=m.clone(), c=a_c.clone(), gp=gp.clone(),
+                                               G=G.clone(), go=a_go.clone(), pts=pts.clone()))
+        grads[4] += gp[0].t() @ pts                                   # layer 0 reads the sample position: (H, 3)
+        grads[5] += gp[0].sum(0)
+        for l in range(1, nl):
+            dWl = torch.zeros((cnt, H, H), dtype=torch.float32, device=dev)
+            cs = torch.zeros((cnt, H), dtype=torch.float32, device=dev)
+            L.check(L.lib().cnerf_weight_grad(cnt, npi, H, H, L.ptr(gp[l]), L.ptr(y[l - 1]), L.ptr(dWl), L.ptr(cs), _stream()),
+                    "cnerf_weight_grad")
+            grads[4 + 2 * l] += dWl.sum(0)
+            grads[5 + 2 * l] += cs.sum(0)
+        grads[4 + 2 * nl] += a_go.t() @ y[nl - 1]
+        grads[5 + 2 * nl] += a_go.sum(0)
+        # mapping network: Linear(C, 256) -> LeakyReLU(0.2) -> Linear(256, 2 L H)
+        grads[2] += G.t() @ m
+        grads[3] += G.sum(0)
+        g_m = G @ ps[2]
+        g_m *= torch.where(m > 0, 1.0, 0.2)
+        grads[0] += g_m.t() @ a_feat
+        grads[1] += g_m.sum(0)
+        d_feat = (g_m @ ps[0]).contiguous()
+        cfgc = make_cfg(net, cnt, int(fvol.shape[1]))
+        L.check(L.lib().cnerf_scatter_features(C.byref(cfgc), L.ptr(pts), npi, L.ptr(d_feat), L.ptr(g_level[b0:b0 + cnt]), _stream()),
+                "cnerf_scatter_features")
+        if g_pts is not None:            # position: the xyz input of layer 0, then the lookup term of d feat
+            g_pts += (gp[0] @ ps[4]).view(g_pts.shape)
+            L.check(L.lib().cnerf_feature_points_grad(C.byref(cfgc), C.byref(volumes_struct([fvol[b0:b0 + cnt]])), L.ptr(pts), npi, L.ptr(d_feat),
+                                                      L.ptr(g_pts), _stream()), "cnerf_feature_points_grad")
+
+    if query is not None:
+        pts_all, g_all, s_all, g_pts = query["points"], query["g_out"], query["saved_out"], query["grad_points"]
+        B, n = pts_all.shape[0], pts_all.shape[1]
+        drop = query["drop"]
+        mask_bytes = len(net.spec.layers) * H if drop is not None else 0
+        ppc, _ = query_chunk(n, lambda k: k * (per_point + mask_bytes), dev)
+        for b in range(B):
+            cfgb = make_cfg(net, 1, [fvol[b:b + 1]], precision="fp32", drop=drop)
+            vsb, gvsb = volumes_struct([fvol[b:b + 1]]), volumes_struct([g_level[b:b + 1]])
+            for p0 in range(0, n, ppc):
+                k = min(ppc, n - p0)
+                a_feat, a_h, a_c, a_g, a_go = chunk_buffers(k)
+                mask = None
+                if drop is not None:     # the forward's keep decisions of these points (their index in the whole call)
+                    mask = torch.empty((nl, k, H), dtype=torch.uint8, device=dev)
+                    L.check(L.lib().cnerf_dropout_keep(C.byref(cfg), 6, b * n + p0, k, L.ptr(mask), _stream()), "cnerf_dropout_keep")
+                pts = pts_all[b, p0:p0 + k]
+                L.check(L.lib().cnerf_field_backward_points(C.byref(cfgb), C.byref(vsb), L.ptr(packed), L.ptr(packed_t), None, None, L.ptr(pts), k,
+                                                            L.ptr(g_all[b, p0:p0 + k]), L.ptr(s_all[b, p0:p0 + k]), L.ptr(a_feat), L.ptr(a_h),
+                                                            L.ptr(a_c), L.ptr(a_g), L.ptr(a_go), C.byref(gvsb), L.ptr(mask), _stream()),
+                        "cnerf_field_backward_points")
+                finish(("pfilm", "points"), b, 1, k, pts, g_pts[b, p0:p0 + k] if g_pts is not None else None)
+        return [g_level], None, None, grads
+
+    B, R, S, hier = o["B"], o["R"], o["S"], o["hier"]
+    npi = R * R * S
+    c_rs, c_z, f_rs, f_z, c_pts, f_pts = saved[:6]
+    nb = max(1, min(B, int(min(ACT_BUDGET_BYTES, MEMORY_FRACTION * free_device_bytes(dev))) // (npi * per_point)))
+    u_strat = _f32(rng.get("u_strat"))
     passes = [(0, gc, c_rs, c_pts)] + ([(1, gf, f_rs, f_pts)] if hier else [])
     for pss, g_out, saved_out, pts_all in passes:
         pts_all = pts_all.reshape(B, npi, 3)
         for b0 in range(0, B, nb):
             cnt = min(nb, B - b0)
-            n = cnt * npi
-            if act is None or act[0].shape[0] != n:
-                act = None          # release the previous chunk before allocating a differently sized one
-                act = (torch.empty((n, 32), dtype=torch.float32, device=dev),
-                       torch.empty(nl * n * H + n * 256, dtype=torch.float32, device=dev),
-                       torch.empty((3 * nl, n, H), dtype=torch.float32, device=dev),
-                       torch.empty(3 * nl * n * H, dtype=torch.float32, device=dev),
-                       torch.empty((n, 4), dtype=torch.float32, device=dev))
-            a_feat, a_h, a_c, a_g, a_go = act
+            a_feat, a_h, a_c, a_g, a_go = chunk_buffers(cnt * npi)
             L.check(L.lib().cnerf_field_backward(C.byref(cfg), pss, b0, cnt, C.byref(vs), L.ptr(packed), L.ptr(packed_t), None, None,
                                                  L.ptr(cam2world), L.ptr(u_strat), L.ptr(f_z) if hier else None, L.ptr(g_out),
                                                  L.ptr(saved_out), L.ptr(a_feat), L.ptr(a_h), L.ptr(a_c), L.ptr(a_g), L.ptr(a_go),
                                                  C.byref(gvs), L.ptr(_u8(rng.get("drop_fine" if pss else "drop_coarse"))), _stream()),
                     "cnerf_field_backward")
-            y, m = a_h[:nl * n * H].view(nl, n, H), a_h[nl * n * H:].view(n, 256)
-            gp, G = a_g[:nl * n * H].view(nl, n, H), a_g[nl * n * H:].view(n, 2 * nl * H)
-            pts = pts_all[b0:b0 + cnt].reshape(n, 3)
-            if DEBUG_CAPTURE is not None:
-                DEBUG_CAPTURE.setdefault(("pfilm", pss), dict(feat=a_feat.clone(), y=y.clone(), m=m.clone(), c=a_c.clone(), gp=gp.clone(),
-                                                              G=G.clone(), go=a_go.clone(), pts=pts.clone()))
-            grads[4] += gp[0].t() @ pts                                   # layer 0 reads the sample position: (H, 3)
-            grads[5] += gp[0].sum(0)
-            for l in range(1, nl):
-                dWl = torch.zeros((cnt, H, H), dtype=torch.float32, device=dev)
-                cs = torch.zeros((cnt, H), dtype=torch.float32, device=dev)
-                L.check(L.lib().cnerf_weight_grad(cnt, npi, H, H, L.ptr(gp[l]), L.ptr(y[l - 1]), L.ptr(dWl), L.ptr(cs), _stream()),
-                        "cnerf_weight_grad")
-                grads[4 + 2 * l] += dWl.sum(0)
-                grads[5 + 2 * l] += cs.sum(0)
-            grads[4 + 2 * nl] += a_go.t() @ y[nl - 1]
-            grads[5 + 2 * nl] += a_go.sum(0)
-            # mapping network: Linear(C, 256) -> LeakyReLU(0.2) -> Linear(256, 2 L H)
-            grads[2] += G.t() @ m
-            grads[3] += G.sum(0)
-            g_m = G @ ps[2]
-            g_m *= torch.where(m > 0, 1.0, 0.2)
-            grads[0] += g_m.t() @ a_feat
-            grads[1] += g_m.sum(0)
-            d_feat = (g_m @ ps[0]).contiguous()
-            cfgc = make_cfg(net, cnt, int(fvol.shape[1]))
-            L.check(L.lib().cnerf_scatter_features(C.byref(cfgc), L.ptr(pts), npi, L.ptr(d_feat), L.ptr(g_level[b0:b0 + cnt]), _stream()),
-                    "cnerf_scatter_features")
+            finish(("pfilm", pss), b0, cnt, npi, pts_all[b0:b0 + cnt].reshape(cnt * npi, 3), None)
     return [g_level], None, None, grads
 
 
@@ -632,3 +681,100 @@ def render(net, fvol, freq, phase, cam2world, img_size, fov, ray_start, ray_end,
     o["need_grad"] = torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (freq, phase, *vols, *params))
     pixels, depth = RenderFunction.apply(net, o, rng or {}, cam2world, freq, phase, len(vols), *vols, *params)
     return pixels, depth, (RenderFunction.last_aux if want_aux else {})
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# autograd of a field query: <SIREN>.forward(points, z) (siren.py:628-670) as one node
+# ---------------------------------------------------------------------------------------------------------------------
+def query_chunk(n, bytes_of, dev):
+    """(points per chunk, bytes) of a field query's backward: all n points when bytes_of(n) fits MEMORY_FRACTION of the memory that
+    is free now, else the largest share of n -- halved until it fits, a multiple of 32 -- whose buffers do."""
+    budget = int(MEMORY_FRACTION * free_device_bytes(dev))
+    ppc = int(n)
+    need = bytes_of(ppc)
+    while need > budget and ppc > 32:
+        ppc = max(32, (ppc // 2 + 31) // 32 * 32)
+        need = bytes_of(ppc)
+    if need > budget:
+        raise L.CnerfError(f"field query backward: {ppc} points need {need / 2**30:.1f} GiB of chunk buffers, {budget / 2**30:.1f} GiB are free")
+    return ppc, need
+
+
+def query_workspace_bytes(cfg, bprec_code, points_per_chunk):
+    nb = C.c_size_t(0)
+    L.check(L.lib().cnerf_field_query_backward_workspace_bytes(C.byref(cfg), bprec_code, int(points_per_chunk), C.byref(nb)),
+            "cnerf_field_query_backward_workspace_bytes")
+    return nb.value
+
+
+def query_backward(net, levels, freq, phase, points, out, grad_out, drop, want_points):
+    """Gradients of one field query w.r.t. (channel-last volume levels, freq, phase, field parameters, points or None): ONE call into
+    the library (cnerf_field_query_backward); the exact fp32 backward of the per-point FiLM family finishes its mapping-MLP gradients
+    with library GEMMs (_pfilm_backward).  The backward precision and the re-run's precision follow render_backward."""
+    global LAST_SATURATED
+    B, n = points.shape[0], points.shape[1]
+    dev = points.device
+    bprec = backward_precision_of(net)
+    g_pts = torch.zeros_like(points) if want_points else None
+    if net.spec.layers[0] == "pfilm" and bprec == "fp32":
+        cfg = make_cfg(net, B, levels, precision="fp32", drop=drop)
+        g_levels, _, _, grads = _pfilm_backward(net, None, cfg, levels, None, None, None, None, None,
+                                                query=dict(points=points, g_out=grad_out, saved_out=out, drop=drop, grad_points=g_pts))
+        return g_levels, None, None, grads, g_pts
+    cfg = make_cfg(net, B, levels, precision="fp16x3" if bprec == "fp16" else None, drop=drop)
+    packed = pack_field(net, cfg)
+    packed_bwd = pack_field_chain16(net, cfg) if bprec == "fp16" else pack_field_transposed(net, make_cfg(net, B, levels, precision="fp32"))
+    params = [_f32(p.detach()) for p in net.field_params()]
+    grads = [torch.zeros_like(p) for p in params]
+    fp, gp = _field_params_struct(net, params), _field_param_grads_struct(net, grads)
+    n_film = sum(1 for k in net.spec.layers if k == "film")
+    H = int(net.hidden_dim)
+    g_freq = torch.zeros((B, n_film * H), dtype=torch.float32, device=dev) if n_film else None
+    g_phase = torch.zeros_like(g_freq) if n_film else None
+    grad_levels = [torch.zeros_like(v) for v in levels]
+    vs, gvs = volumes_struct(levels), volumes_struct(grad_levels)
+    code = L.PREC_CODE[bprec]
+    ppc, ws_bytes = query_chunk(n, lambda k: query_workspace_bytes(cfg, code, k), dev)
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+    sat = torch.zeros(1, dtype=torch.int32, device=dev)
+    L.check(L.lib().cnerf_field_query_backward(C.byref(cfg), code, ppc, C.byref(vs), C.byref(fp), L.ptr(packed), L.ptr(packed_bwd), L.ptr(freq),
+                                               L.ptr(phase), L.ptr(points), n, L.ptr(out), L.ptr(grad_out), C.byref(gp), L.ptr(g_freq), L.ptr(g_phase),
+                                               C.byref(gvs), L.ptr(g_pts), L.ptr(sat) if bprec == "fp16" else None, L.ptr(ws), _stream()),
+            "cnerf_field_query_backward")
+    if bprec == "fp16":
+        LAST_SATURATED = sat
+    return grad_levels, g_freq, g_phase, grads, g_pts
+
+
+class FieldQueryFunction(torch.autograd.Function):
+    """<SIREN>.forward(points, z) as one autograd node: differentiable w.r.t. the feature volume(s), freq / phase (and through them the
+    mapping network and the global feature), the query points and the field parameters.  drop = (p, (seed, offset)) of a training-mode
+    call is kept for the backward, which draws the same keep decisions whatever its chunking."""
+
+    @staticmethod
+    def forward(ctx, net, drop, vols_channel_last, freq, phase, points, n_vols, *rest):
+        vols, params = rest[:n_vols], rest[n_vols:]
+        levels = [_f32(v.detach()) for v in vols] if vols_channel_last else [channel_last(v.detach()) for v in vols]
+        # volumes given channel-last get channel-last gradients; a channels_last_3d volume (zero-copy above) gets a view in its format
+        ctx.vols_channel_last = vols_channel_last
+        ctx.vol_is_cl = [lv.data_ptr() == v.data_ptr() and not v.is_contiguous() for lv, v in zip(levels, vols)]
+        fr = _f32(freq.detach()) if freq is not None else None
+        ph = _f32(phase.detach()) if phase is not None else None
+        pts = _f32(points.detach())
+        out = _field_forward(net, levels, fr, ph, pts, fvol_is_channel_last=True, drop=drop)
+        ctx.net, ctx.drop, ctx.n_vols = net, drop, n_vols
+        ctx.saved = (levels, fr, ph, pts)
+        ctx.save_for_backward(out)
+        return out
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        levels, fr, ph, pts = ctx.saved
+        out, = ctx.saved_tensors
+        g_levels, g_freq, g_phase, g_params, g_pts = query_backward(ctx.net, levels, fr, ph, pts, out, _f32(grad_out), ctx.drop,
+                                                                    want_points=ctx.needs_input_grad[5])
+        if ctx.vols_channel_last:
+            g_vols = g_levels
+        else:
+            g_vols = [g.permute(0, 4, 1, 2, 3) if cl else channel_first(g) for g, cl in zip(g_levels, ctx.vol_is_cl)]
+        return (None, None, None, g_freq, g_phase, g_pts, None, *g_vols, *g_params)

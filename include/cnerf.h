@@ -22,7 +22,7 @@
 extern "C" {
 #endif
 
-#define CNERF_ABI_VERSION 8
+#define CNERF_ABI_VERSION 9
 
 #define CNERF_OK 0
 #define CNERF_EINVAL (-22)  /* bad argument / unsupported shape (message via cnerf_last_error) */
@@ -239,7 +239,8 @@ int cnerf_render_forward(const cnerf_cfg* cfg, const cnerf_volumes* vols, const 
                          float* depth, const cnerf_aux* aux, void* workspace, void* stream);
 
 /* ---- backward (autograd twin of cnerf_render_forward; gradients flow to the field parameters, freq/phase and the
- * feature volume, never to cam2world or the sample positions: generators.py:57,111 run them under no_grad) ----------
+ * feature volume, never to cam2world or the sample positions: generators.py:57,111 run them under no_grad.  The render
+ * backward gives no position gradient; a field query's does: cnerf_field_query_backward below) ----------
  *
  * Step 1  cnerf_merge_composite_backward: d(pixels, depth) -> d(rgb_sigma) of the coarse and the fine samples.
  * Step 2  cnerf_field_backward per pass (coarse, fine) and per chunk of images: re-runs the field forward storing the
@@ -388,6 +389,49 @@ int cnerf_render_backward(const cnerf_cfg* cfg, int32_t backward_precision, int3
                           const cnerf_aux* act16, const float* grad_pixels, const float* grad_depth,
                           const cnerf_field_param_grads* grads, float* grad_freq, float* grad_phase,
                           const cnerf_grad_volumes* grad_vols, uint32_t* saturated, void* workspace, void* stream);
+
+/* ---- gradients of a field query (ABI v9): autograd twin of cnerf_field_forward --------------------------------------------
+ * Replaces loss.backward() through <SIREN>.forward(points, z, img_size, num_steps) (siren.py:628-670 under autograd): the inputs are
+ * the forward's (cfg, vols, freq / phase, points (B,n,3), n_per_image), its output rgb_sigma (saved_rgb_sigma, (B,n,4)) and
+ * d loss / d rgb_sigma (grad_rgb_sigma, (B,n,4)).  Per image and range of points_per_chunk points it runs the render's chunk body of
+ * that backward precision -- the activation-storing re-run of the forward, the gradient chain (whose feature-volume gradients go to
+ * grad_vols with the chain's own atomics: points are no pixel patches), one weight reduction per matrix -- and, when grad_points is
+ * given, the position gradient (csrc/points_grad.hip): layer 0's input gradient from the chunk's layer-0 gradient slab, its lookup
+ * term through the trilinear weights of every level (ATen grid_sampler_3d_backward, border padding: zero on an axis whose coordinate
+ * sits at or beyond the clamp) plus the xyz columns of TALLSIREN_dgx / TALLSIREN's layer 0.
+ *   backward_precision  as cnerf_render_backward, with the same coverage: CNERF_PREC_FP32 re-runs the forward in cfg->precision,
+ *                       CNERF_PREC_FP16 needs cfg->precision = CNERF_PREC_FP16X3; per-point FiLM + CNERF_PREC_FP32 answers CNERF_ENOSYS
+ *                       (the host finishes that one: cnerf_field_backward_points + cnerf_feature_points_grad).
+ *   packed / packed_bwd as cnerf_render_backward.  cfg->R, S, fov are not read (check as for cnerf_field_forward).
+ *   grads, grad_freq, grad_phase, grad_vols, grad_points (B,n,3) or NULL = skip: ACCUMULATED INTO (zero them first).
+ *   dropout (cfg->drop_p > 0, fp32 only): the decisions of cnerf_field_forward (stream 6 at the point's index in the whole call),
+ *                       whatever the chunking.
+ *   saturated           as cnerf_render_backward (fp16 backward).
+ *   workspace           cnerf_field_query_backward_workspace_bytes(cfg, backward_precision, points_per_chunk): grows with
+ *                       points_per_chunk, independent of n. */
+int cnerf_field_query_backward_workspace_bytes(const cnerf_cfg* cfg, int32_t backward_precision, int64_t points_per_chunk, size_t* bytes);
+int cnerf_field_query_backward(const cnerf_cfg* cfg, int32_t backward_precision, int64_t points_per_chunk, const cnerf_volumes* vols,
+                               const cnerf_field_params* params, const float* packed, const void* packed_bwd, const float* freq,
+                               const float* phase, const float* points, int64_t n_per_image, const float* saved_rgb_sigma,
+                               const float* grad_rgb_sigma, const cnerf_field_param_grads* grads, float* grad_freq, float* grad_phase,
+                               const cnerf_grad_volumes* grad_vols, float* grad_points, uint32_t* saturated, void* workspace, void* stream);
+
+/* Stage entries of the per-point FiLM family's exact fp32 query backward (the host finishes its mapping-MLP gradients like
+ * ops._pfilm_backward does for the ray passes):
+ *   cnerf_field_backward_points  cnerf_field_backward (pass 2) for ANY point count: points / grad_rgb_sigma / saved_rgb_sigma are
+ *                                (B, n_per_image, ...) of cfg->B images (cfg->R, S unused); act_* sized for B * n_per_image rows;
+ *                                drop_mask (n_drop, B * n_per_image, H) or NULL (then Philox stream 6 at index b * n_per_image + p).
+ *   cnerf_feature_points_grad    position-side counterpart of cnerf_scatter_features: grad_points (B,n,3) += sum over levels and
+ *                                channels of grad_feat (B,n,C) * d feat / d points (lookup term, border rule as above).
+ *   cnerf_dropout_keep           keep bytes (n_drop, n_points, H) of points [point0, point0 + n_points) of a call: the decisions the
+ *                                kernels draw on Philox stream stream_id (4..6) under cfg's key, drop_p and layers. */
+int cnerf_field_backward_points(const cnerf_cfg* cfg, const cnerf_volumes* vols, const float* packed, const float* packed_t, const float* freq,
+                                const float* phase, const float* points, int64_t n_per_image, const float* grad_rgb_sigma,
+                                const float* saved_rgb_sigma, float* act_feat, float* act_h, float* act_c, float* act_g, float* act_go,
+                                const cnerf_grad_volumes* grad_vols, const uint8_t* drop_mask, void* stream);
+int cnerf_feature_points_grad(const cnerf_cfg* cfg, const cnerf_volumes* vols, const float* points, int64_t n_per_image, const float* grad_feat,
+                              float* grad_points, void* stream);
+int cnerf_dropout_keep(const cnerf_cfg* cfg, uint32_t stream_id, int64_t point0, int64_t n_points, uint8_t* mask, void* stream);
 
 #ifdef __cplusplus
 }
