@@ -645,14 +645,6 @@ __global__ __launch_bounds__(256) void chain16_kernel(Chain16Args A) {
 // (i = lane & 31, hh = lane >> 5) = s * M[32 t + i][16 c + 8 (jj >> 2) + 4 hh + (jj & 3)]: the k order in which the
 // accumulator registers of the previous product become the B operand (registers 8 s' .. 8 s' + 7 of tile t' are k-chunk
 // 2 t' + s': element jj <-> channel 32 t' + 16 s' + 8 (jj >> 2) + 4 hh + (jj & 3)).
-__global__ void absmax16_kernel(const float* __restrict__ w, long long n, uint32_t* slot) {
-    float m = 0.0f;
-    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) m = fmaxf(m, fabsf(w[i]));
-#pragma unroll
-    for (int d = WAVE / 2; d >= 1; d >>= 1) m = fmaxf(m, __shfl_xor(m, d, WAVE));
-    if ((threadIdx.x & 63) == 0 && m == m) atomicMax(slot, __float_as_uint(m));
-}
-
 __global__ void pack_t16_kernel(const float* __restrict__ w, int n_rows_w, int n_cols_w, int n_cols_real, int OT, int KCH, const uint32_t* wmax_slot,
                                 float* winv_slot, _Float16* __restrict__ dst) {
     // w: (n_rows_w, n_cols_w) row-major = W; M[r][k] = W[k][r], r < n_cols_real (else 0), k < n_rows_w (= 16 * KCH)
@@ -716,10 +708,7 @@ hipError_t launch_col_abs_sum_max(const float* w, int n_rows, int n_cols, float*
 hipError_t launch_pack_t16(const float* w, int n_rows_w, int n_cols_w, int n_cols_real, int OT_padded, void* dst, float* winv_slot, uint32_t* wmax_slot,
                            hipStream_t stream) {
     if (hipError_t e = hipMemsetAsync(wmax_slot, 0, sizeof(uint32_t), stream)) return e;
-    const long long n = (long long)n_rows_w * n_cols_w;
-    long long rb = (n + 255) / 256;
-    if (rb > 256) rb = 256;
-    hipLaunchKernelGGL(absmax16_kernel, dim3((unsigned)rb), dim3(256), 0, stream, w, n, wmax_slot);
+    if (hipError_t e = launch_absmax_bits(w, (long long)n_rows_w * n_cols_w, wmax_slot, stream)) return e;
     const int KCH = n_rows_w / 16;
     const long long total = (long long)OT_padded * KCH * 64 * 8;
     long long blocks = (total + 255) / 256;
@@ -731,7 +720,7 @@ hipError_t launch_pack_t16(const float* w, int n_rows_w, int n_cols_w, int n_col
 
 hipError_t launch_pack_head_t16(const float* w, int H, void* dst, float* winv_slot, uint32_t* wmax_slot, hipStream_t stream) {
     if (hipError_t e = hipMemsetAsync(wmax_slot, 0, sizeof(uint32_t), stream)) return e;
-    hipLaunchKernelGGL(absmax16_kernel, dim3(4), dim3(256), 0, stream, w, (long long)4 * H, wmax_slot);
+    if (hipError_t e = launch_absmax_bits(w, (long long)4 * H, wmax_slot, stream)) return e;
     hipLaunchKernelGGL(pack_head_t16_kernel, dim3((unsigned)((H / 32) * 2)), dim3(256), 0, stream, w, H, (const uint32_t*)wmax_slot, winv_slot, (_Float16*)dst);
     return hipGetLastError();
 }

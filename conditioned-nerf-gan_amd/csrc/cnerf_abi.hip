@@ -66,83 +66,83 @@ int check_cfg(const cnerf_cfg* c, bool need_render) {
     return CNERF_OK;
 }
 
-// packed layout: [float4 weight stream][biases of every layer in order (RES: b1 then b2)][head bias (4)][ones H][zeros H]
-// (ones/zeros: a plain sine layer runs as a FiLM layer with freq = 1, phase = 0)
-struct PackedLayout {
-    size_t weight_floats;
-    size_t bias_floats;
-    int n_film;
-    int n_in;      // 32-wide input tiles of layer 0
-    int k0;        // real input width of layer 0
-};
-
 int n_levels_of(const cnerf_cfg* c) { return c->n_levels > 0 ? c->n_levels : 1; }
 int level_V_of(const cnerf_cfg* c, int i) { return c->n_levels > 0 ? c->level_V[i] : c->V; }
 int level_C_of(const cnerf_cfg* c, int i) { return c->n_levels > 0 ? c->level_C[i] : c->C; }
+// floats of one image's volume level i (V^3 C, channel-last)
+size_t level_floats(const cnerf_cfg* c, int i) { const size_t V = level_V_of(c, i); return V * V * V * level_C_of(c, i); }
+
+// What every host path derives from the cfg's layer list, computed here only
+struct NetCounts {
+    int n_mats;             // weight matrices before the head (a residual block: fc1 and fc2)
+    int n_film;             // FiLM layers: rows of freq / phase per image
+    int n_drop;             // layers whose output dropout masks (all but residual blocks)
+    int n_in;               // 32-wide input tiles of layer 0
+    int k0;                 // real input width of layer 0
+    float drop_scale;       // ATen: noise.bernoulli_(1 - p).div_(1 - p): the factor is 1 / float(1 - p) in fp32
+    uint32_t drop_thresh;   // a keep draw below p 2^32 drops
+};
+NetCounts counts_of(const cnerf_cfg* c) {
+    NetCounts n{0, 0, 0, 1, 3, 0.0f, 0u};
+    for (int l = 0; l < c->L; ++l) {
+        n.n_mats += c->layer_kind[l] == CNERF_LAYER_RES ? 2 : 1;
+        n.n_film += c->layer_kind[l] == CNERF_LAYER_FILM;
+        n.n_drop += c->layer_kind[l] != CNERF_LAYER_RES;
+    }
+    if (c->layer_kind[0] != CNERF_LAYER_PFILM) {      // (per-point FiLM: layer 0 reads the sample position)
+        n.n_in = c->C / 32 + ((c->flags & CNERF_F_INPUT_XYZ) ? 1 : 0);
+        n.k0 = c->C + ((c->flags & CNERF_F_INPUT_XYZ) ? 3 : 0);
+    }
+    n.drop_scale = 1.0f / (float)(1.0 - (double)c->drop_p);
+    const double th = (double)c->drop_p * 4294967296.0 + 0.5;
+    n.drop_thresh = th >= 4294967295.0 ? 0xffffffffu : (uint32_t)th;
+    return n;
+}
+
+// The packed buffer of cnerf_pack_field, offsets in floats from its start:
+//   [weight stream][biases][head bias (4)][fp16 precisions: 1/S, max|W| slots][ones H][zeros H]
+// weight stream: the matrices in consumption order, fp32 float4 tiles or fp16 fragments (field_kernel.hip, field_h3.hip, field_pw16.hip).
+// biases: FiLM / plain-sine / residual: one per matrix in order (a residual block: b1 then b2); per-point FiLM: mapping b1 (256), then per
+// layer b, freq bias, phase bias.  Per-point FiLM in fp16: the biases, the head bias and pw16_consts_kernel's constants are all written
+// by that kernel.  ones / zeros: a plain sine layer runs as a FiLM layer with freq = 1, phase = 0.
+struct PackedLayout {
+    size_t tile_floats;     // one 32-row output tile against one 32-wide input tile
+    size_t weight_floats;   // = the offset of the biases
+    size_t head_bias;
+    size_t pw_consts;       // per-point FiLM fp16: the scalar constants of pw16_consts_kernel (2 + 4 L, padded to 4)
+    size_t inv_s, wmax;     // fp16 precisions: n_slots 1/S, then n_slots max|W| scratch words (together padded to 4)
+    int n_slots;
+    size_t ones, zeros;
+    size_t total;
+    // floats one packed matrix of n_out rows and K inputs moves the write pointer
+    size_t mat_floats(int n_out, int K) const { return (size_t)((n_out + 31) / 32) * ((K + 31) / 32) * tile_floats; }
+};
 
 PackedLayout packed_layout(const cnerf_cfg* c) {
-    const size_t NT = c->H / 32;
-    const size_t tile = 4 * 64 * 4;  // floats per (t, tk) pair
-    PackedLayout p{0, 0, 0, 0, 0};
-    if (c->layer_kind[0] == CNERF_LAYER_PFILM && c->precision != CNERF_PREC_FP32) {
-        // field_pw16.hip: weight units in consumption order -- Wm1 | W_0 | layer 0: per tile (freq rows, phase rows) | layers >= 1: per
-        // tile (freq rows, W_l, phase rows) | head; units multiplied by m have 16 k-chunks, the others 2 NT.  Behind them the
-        // constants of pw16_consts_kernel, then the 1 / S and max|W| slots of the 3 L + 2 packed matrices
-        const size_t parts = c->precision == CNERF_PREC_FP16 ? 1 : 2;
-        const size_t frag = 64 * 8 / 2;                     // floats per (tile, k-chunk, part)
-        const size_t big = 16 * parts * frag, small = 2 * NT * parts * frag;
-        p.n_in = 1;
-        p.k0 = 3;
-        p.weight_floats = big + small + NT * 2 * big + (size_t)(c->L - 1) * NT * (2 * big + small) + small;
-        p.bias_floats = 256 + 3 * (size_t)c->L * c->H + 4 + (2 + 4 * (size_t)c->L + 3) / 4 * 4 + (2 * (3 * (size_t)c->L + 2) + 3) / 4 * 4;
-        return p;
+    const NetCounts n = counts_of(c);
+    const int H = c->H, L = c->L;
+    const bool pfilm = c->layer_kind[0] == CNERF_LAYER_PFILM, half = c->precision != CNERF_PREC_FP32;
+    PackedLayout p{};
+    // fp32: 4 x 64 lanes x float4; fp16: two k-chunks of 16 x 64 lanes x 8 fp16 per part (fp16x3: two parts)
+    p.tile_floats = half ? (c->precision == CNERF_PREC_FP16 ? 1 : 2) * 2 * 64 * 8 / 2 : 4 * 64 * 4;
+    if (pfilm) {   // Wm1 | per layer: W_l, freq rows, phase rows (fp16: interleaved per output tile) | head
+        p.weight_floats = p.mat_floats(256, 32) + p.mat_floats(4, H);     // (a single 32-channel volume)
+        for (int l = 0; l < L; ++l) p.weight_floats += p.mat_floats(H, l == 0 ? 3 : H) + 2 * p.mat_floats(H, 256);
+        p.head_bias = p.weight_floats + 256 + 3 * (size_t)L * H;
+        p.pw_consts = p.head_bias + 4;
+        p.n_slots = 3 * L + 2;
+        p.inv_s = half ? p.pw_consts + (2 + 4 * (size_t)L + 3) / 4 * 4 : p.pw_consts;
+    } else {
+        p.weight_floats = p.mat_floats(4, H);   // head, one 32-row tile
+        for (int m = 0; m < n.n_mats; ++m) p.weight_floats += p.mat_floats(H, m == 0 ? n.k0 : H);
+        p.head_bias = p.weight_floats + (size_t)n.n_mats * H;
+        p.n_slots = n.n_mats + 1;
+        p.inv_s = p.head_bias + 4;
     }
-    if (c->layer_kind[0] == CNERF_LAYER_PFILM) {   // mapping hidden | per layer (main, freq rows, phase rows) | head
-        p.n_in = 1;
-        p.k0 = 3;
-        p.weight_floats = 8 * tile;
-        p.bias_floats = 256;
-        for (int l = 0; l < c->L; ++l) {
-            p.weight_floats += NT * (l == 0 ? 1 : NT) * tile + 2 * NT * 8 * tile;
-            p.bias_floats += 3 * c->H;
-        }
-        p.weight_floats += NT * tile;
-        p.bias_floats += 4;
-        return p;
-    }
-    p.n_in = c->C / 32 + ((c->flags & CNERF_F_INPUT_XYZ) ? 1 : 0);
-    p.k0 = c->C + ((c->flags & CNERF_F_INPUT_XYZ) ? 3 : 0);
-    if (c->precision == CNERF_PREC_FP16X3 || c->precision == CNERF_PREC_FP16) {
-        const size_t parts = c->precision == CNERF_PREC_FP16 ? 1 : 2;
-        // fp16 fragments: (t, k-chunk of 16, part) x 64 lanes x 8 fp16 = 256 floats' worth of bytes per (t, c, part);
-        // behind the biases: 1/S of every matrix (L + 1), then the max|W| scratch slots (L + 1), padded to 4 floats
-        const size_t frag = 64 * 8 / 2;   // in floats
-        size_t mats = 0;
-        for (int l = 0; l < c->L; ++l) {
-            const size_t kc = (l == 0) ? 2 * (size_t)p.n_in : 2 * NT;
-            const size_t n = c->layer_kind[l] == CNERF_LAYER_RES ? 2 : 1;      // residual block: fc1 and fc2
-            p.weight_floats += n * NT * kc * parts * frag;
-            p.bias_floats += n * c->H;
-            mats += n;
-            if (c->layer_kind[l] == CNERF_LAYER_FILM) p.n_film++;
-        }
-        p.weight_floats += 1 * 2 * NT * parts * frag;   // head, one 32-row tile
-        p.bias_floats += 4 + (2 * (mats + 1) + 3) / 4 * 4;
-        return p;
-    }
-    for (int l = 0; l < c->L; ++l) {
-        const size_t kt = (l == 0) ? (size_t)p.n_in : NT;
-        if (c->layer_kind[l] == CNERF_LAYER_RES) {
-            p.weight_floats += 2 * NT * NT * tile;
-            p.bias_floats += 2 * c->H;
-        } else {
-            p.weight_floats += NT * kt * tile;
-            p.bias_floats += c->H;
-            if (c->layer_kind[l] == CNERF_LAYER_FILM) p.n_film++;
-        }
-    }
-    p.weight_floats += 1 * NT * tile;  // head, one 32-row tile
-    p.bias_floats += 4;
+    p.wmax = p.inv_s + p.n_slots;
+    p.ones = half ? p.inv_s + (2 * (size_t)p.n_slots + 3) / 4 * 4 : p.inv_s;
+    p.zeros = p.ones + H;
+    p.total = p.zeros + H;
     return p;
 }
 
@@ -166,15 +166,16 @@ int fill_field_args(FieldArgs& a, const cnerf_cfg* c, const cnerf_volumes* vols,
                     const float* packed, const float* freq, const float* phase, int image0 = 0) {
     memset(&a, 0, sizeof(a));
     const PackedLayout pl = packed_layout(c);
+    const NetCounts nc = counts_of(c);
     if (!vols) return fail(CNERF_EINVAL, "volumes are NULL");
     int tk = 0;
     for (int i = 0; i < n_levels_of(c); ++i) {
-        const int V = level_V_of(c, i), C = level_C_of(c, i);
+        const int C = level_C_of(c, i);
         if (!vols->level[i]) return fail(CNERF_EINVAL, "volume level %d is NULL", i);
-        const size_t per_image = (size_t)V * V * V * C;
+        const size_t per_image = level_floats(c, i);
         a.lvl_vol[i] = vols->level[i] + (size_t)image0 * per_image;
         a.lvl_grad[i] = (gvols && gvols->level[i]) ? gvols->level[i] + (size_t)image0 * per_image : nullptr;
-        a.lvl_V[i] = V;
+        a.lvl_V[i] = level_V_of(c, i);
         a.lvl_C[i] = C;
         for (int cc = 0; cc < C; cc += 32, ++tk) {
             if (tk >= 8) return fail(CNERF_EINVAL, "more than 8 input tiles");
@@ -189,30 +190,26 @@ int fill_field_args(FieldArgs& a, const cnerf_cfg* c, const cnerf_volumes* vols,
         ++tk;
     }
     a.n_in = tk;
-    freq = (pl.n_film && freq) ? freq + (size_t)image0 * pl.n_film * c->H : freq;
-    phase = (pl.n_film && phase) ? phase + (size_t)image0 * pl.n_film * c->H : phase;
+    freq = (nc.n_film && freq) ? freq + (size_t)image0 * nc.n_film * c->H : freq;
+    phase = (nc.n_film && phase) ? phase + (size_t)image0 * nc.n_film * c->H : phase;
     a.packed = packed;
     a.bias = packed + pl.weight_floats;
-    a.freq = pl.n_film ? freq : nullptr;
-    a.phase = pl.n_film ? phase : nullptr;
-    a.film_stride = pl.n_film * c->H;
-    a.bias_floats = (int)pl.bias_floats;
+    a.freq = nc.n_film ? freq : nullptr;
+    a.phase = nc.n_film ? phase : nullptr;
+    a.film_stride = nc.n_film * c->H;
+    a.bias_floats = (int)(pl.ones - pl.weight_floats);
     a.geom = make_geom(c);
     a.half_voxel = c->voxel_length / 2.0f;
     a.L = c->L;
-    a.n_mats = 0;
-    for (int l = 0; l < c->L; ++l) a.n_mats += c->layer_kind[l] == CNERF_LAYER_RES ? 2 : 1;
+    a.n_mats = nc.n_mats;
     a.flags = c->flags;
     for (int l = 0; l < c->L; ++l) a.layer_kind[l] = c->layer_kind[l];
     a.philox = philox_of(c);
     a.image0 = image0;
     if (c->drop_p > 0.0f) {
-        // ATen: noise.bernoulli_(1 - p).div_(1 - p): the factor is 1 / float(1 - p) in fp32
-        a.drop_scale = 1.0f / (float)(1.0 - (double)c->drop_p);
-        const double th = (double)c->drop_p * 4294967296.0 + 0.5;
-        a.drop_thresh = th >= 4294967295.0 ? 0xffffffffu : (uint32_t)th;
-        a.n_drop = 0;
-        for (int l = 0; l < c->L; ++l) a.n_drop += c->layer_kind[l] != CNERF_LAYER_RES;
+        a.drop_scale = nc.drop_scale;
+        a.drop_thresh = nc.drop_thresh;
+        a.n_drop = nc.n_drop;
     }
     return CNERF_OK;
 }
@@ -258,6 +255,112 @@ int pass_args(FieldArgs& a, const cnerf_cfg* c, int pass, int image0, int n_imag
         a.points = u_strat + (size_t)image0 * npi * 3;
     }
     return CNERF_OK;
+}
+
+// FieldArgs of explicit points: n_images images from image0 of the call, n_per_image positions each (`points`: the first image's), the
+// keep decisions of dropout stream PHILOX_DROP_POINTS (`mask`, or Philox when NULL)
+int points_args(FieldArgs& a, const cnerf_cfg* c, const cnerf_volumes* vols, const cnerf_grad_volumes* gvols, const float* packed, const float* freq,
+                const float* phase, const float* points, int image0, int n_images, long long n_per_image, const uint8_t* mask) {
+    if (int rc = fill_field_args(a, c, vols, gvols, packed, freq, phase, image0)) return rc;
+    a.mode = FIELD_MODE_POINTS;
+    a.points = points;
+    set_points(a, n_images, n_per_image);
+    set_dropout(a, c, mask, PHILOX_DROP_POINTS, n_per_image);
+    return CNERF_OK;
+}
+
+int check_grad_vols(const cnerf_cfg* c, const cnerf_grad_volumes* g, const char* who) {
+    for (int i = 0; i < n_levels_of(c); ++i)
+        if (!g->level[i]) return fail(CNERF_EINVAL, "%s: gradient volume %d is NULL", who, i);
+    return CNERF_OK;
+}
+
+// PointsGradArgs of image b's volume levels and n points; the caller sets the gradient rows it reads (gfeat / gxyz)
+PointsGradArgs points_grad_args(const cnerf_cfg* c, const cnerf_volumes* vols, int b, const float* points, float* grad_points, long long n) {
+    PointsGradArgs pg{};
+    pg.n_levels = n_levels_of(c);
+    for (int i = 0; i < pg.n_levels; ++i) {
+        pg.lvl_vol[i] = vols->level[i] + (size_t)b * level_floats(c, i);
+        pg.lvl_V[i] = level_V_of(c, i);
+        pg.lvl_C[i] = level_C_of(c, i);
+    }
+    pg.points = points;
+    pg.grad_points = grad_points;
+    pg.n = n;
+    pg.half_voxel = c->voxel_length / 2.0f;
+    return pg;
+}
+
+// the draws of a call that passes no cnerf_rng: none
+const cnerf_rng* rng_or_none(const cnerf_rng* rng) {
+    static const cnerf_rng no_rng = {};
+    return rng ? rng : &no_rng;
+}
+
+// The matrices of a FiLM / plain-sine / residual network in slab order (a residual block: fc1, fc2), their kinds and gradient buffers
+// (NULL without G)
+struct MatrixSet {
+    const float *W[2 * CNERF_MAX_LAYERS], *b[2 * CNERF_MAX_LAYERS];
+    float *dW[2 * CNERF_MAX_LAYERS], *db[2 * CNERF_MAX_LAYERS];
+    int film_of[2 * CNERF_MAX_LAYERS];
+    int H, film_stride;
+    // matrix m's slice of freq / grad_freq / grad_phase for the chunk from image b0 (NULL unless m is a FiLM matrix)
+    const float* film(const float* t, int m, int b0) const { return film_of[m] >= 0 ? t + (size_t)b0 * film_stride + (size_t)film_of[m] * H : nullptr; }
+    float* film(float* t, int m, int b0) const { return film_of[m] >= 0 ? t + (size_t)b0 * film_stride + (size_t)film_of[m] * H : nullptr; }
+};
+int matrix_set(const cnerf_cfg* cfg, const cnerf_field_params* P, const cnerf_field_param_grads* G, const char* who, MatrixSet& ms) {
+    int nm = 0, nfilm = 0;
+    for (int l = 0; l < cfg->L; ++l) {
+        const bool res = cfg->layer_kind[l] == CNERF_LAYER_RES;
+        if (!P->w[l] || !P->b[l] || (res && (!P->w2[l] || !P->b2[l]))) return fail(CNERF_EINVAL, "%s: parameters of layer %d are NULL", who, l);
+        ms.W[nm] = P->w[l]; ms.b[nm] = P->b[l]; ms.dW[nm] = G ? G->w[l] : nullptr; ms.db[nm] = G ? G->b[l] : nullptr;
+        ms.film_of[nm] = cfg->layer_kind[l] == CNERF_LAYER_FILM ? nfilm++ : -1;
+        ++nm;
+        if (res) {
+            ms.W[nm] = P->w2[l]; ms.b[nm] = P->b2[l]; ms.dW[nm] = G ? G->w2[l] : nullptr; ms.db[nm] = G ? G->b2[l] : nullptr;
+            ms.film_of[nm] = -1;
+            ++nm;
+        }
+    }
+    ms.H = cfg->H;
+    ms.film_stride = counts_of(cfg).n_film * cfg->H;
+    return CNERF_OK;
+}
+
+// Workspace of cnerf_render_forward, carved in this order (every piece 256-byte aligned): the coarse and fine rgb_sigma (N, 4) and z (N),
+// then the weight folding.  fp32: the folded FiLM constants (4 per image, matrix and channel) and the row-scaled per-image copies of the
+// layer weights (WFOLD, field_kernel.hip).  fp16 precisions, in the same place: the per-image copies of the whole packed weight stream,
+// their constants K S' / 1 / S' and the row multipliers (field_h3.hip, "weight folding per image").  The per-point FiLM family computes
+// its frequencies per point and folds nothing, yet reserves the fp32 regions.
+struct ForwardLayout {
+    size_t c_rs, f_rs, c_z, f_z;
+    size_t fold, packed_img;            // fp32
+    long long layer_floats;             // fp32: one image's copy of the layer weights
+    size_t img16, fold16, rowf;         // fp16 precisions
+    size_t total;
+};
+ForwardLayout forward_layout(const cnerf_cfg* c) {
+    const PackedLayout pl = packed_layout(c);
+    const NetCounts nc = counts_of(c);
+    const size_t N = (size_t)c->B * c->R * c->R * c->S, B = c->B, H = c->H, NT = H / 32, mats = nc.n_mats;
+    ForwardLayout F{};
+    size_t off = 0;
+    auto take = [&](size_t bytes) { const size_t o = off; off += align256(bytes); return o; };
+    F.c_rs = take(N * 4 * sizeof(float));
+    F.f_rs = take(N * 4 * sizeof(float));
+    F.c_z = take(N * sizeof(float));
+    F.f_z = take(N * sizeof(float));
+    if (c->precision != CNERF_PREC_FP32 && c->layer_kind[0] != CNERF_LAYER_PFILM) {
+        F.img16 = take(B * pl.weight_floats * sizeof(float));
+        F.fold16 = take(B * mats * (H + 1) * sizeof(float));
+        F.rowf = take(B * mats * H * sizeof(float));
+    } else {
+        F.layer_floats = (long long)((NT * nc.n_in + (mats - 1) * NT * NT) * 1024);
+        F.fold = take(4 * B * mats * H * sizeof(float));
+        F.packed_img = take(B * (size_t)F.layer_floats * sizeof(float));
+    }
+    F.total = off;
+    return F;
 }
 
 // the activation-storing re-run of a half-precision backward: the pass `a` again, storing fp16 TB16 activations (amax: per-point FiLM
@@ -313,30 +416,13 @@ int cnerf_philox_fill(uint64_t seed, uint32_t offset, uint32_t stream_id, int64_
 int cnerf_workspace_bytes(const cnerf_cfg* cfg, size_t* packed, size_t* fvol_cl, size_t* fwd_ws) {
     g_err[0] = 0;
     if (int rc = check_cfg(cfg, fwd_ws != nullptr)) return rc;
-    const PackedLayout pl = packed_layout(cfg);
-    if (packed) *packed = align256((pl.weight_floats + pl.bias_floats + 2 * (size_t)cfg->H) * sizeof(float));
+    if (packed) *packed = align256(packed_layout(cfg).total * sizeof(float));
     if (fvol_cl) {   // all levels together
         size_t fl = 0;
-        for (int i = 0; i < n_levels_of(cfg); ++i)
-            fl += (size_t)cfg->B * level_V_of(cfg, i) * level_V_of(cfg, i) * level_V_of(cfg, i) * level_C_of(cfg, i);
+        for (int i = 0; i < n_levels_of(cfg); ++i) fl += (size_t)cfg->B * level_floats(cfg, i);
         *fvol_cl = align256(fl * sizeof(float));
     }
-    if (fwd_ws) {
-        const size_t N = (size_t)cfg->B * cfg->R * cfg->R * cfg->S;
-        // coarse rgb_sigma + z, fine z + rgb_sigma; folded FiLM constants of the call (3 per image, matrix and channel)
-        size_t mats = 0;
-        for (int l = 0; l < cfg->L; ++l) mats += cfg->layer_kind[l] == CNERF_LAYER_RES ? 2 : 1;
-        // ... 4 per image, matrix and channel; and, in fp32, the row-scaled layer weights per image
-        const size_t NT = cfg->H / 32;
-        const size_t layer_floats = (NT * pl.n_in + (mats - 1) * NT * NT) * 1024;
-        *fwd_ws = 2 * align256(N * 4 * sizeof(float)) + 2 * align256(N * sizeof(float)) + align256((size_t)4 * cfg->B * mats * cfg->H * sizeof(float)) +
-                  align256((size_t)cfg->B * layer_floats * sizeof(float));
-        // fp16 precisions: the per-image copies of the whole packed weight stream (rows scaled by the image's FiLM frequencies), their
-        // constants K S' / 1 / S' and the row multipliers (field_h3.hip, "weight folding per image") instead of the fp32 ones
-        if (cfg->precision != CNERF_PREC_FP32 && cfg->layer_kind[0] != CNERF_LAYER_PFILM)
-            *fwd_ws = 2 * align256(N * 4 * sizeof(float)) + 2 * align256(N * sizeof(float)) + align256((size_t)cfg->B * pl.weight_floats * sizeof(float)) +
-                      align256((size_t)cfg->B * mats * (cfg->H + 1) * sizeof(float)) + align256((size_t)cfg->B * mats * cfg->H * sizeof(float));
-    }
+    if (fwd_ws) *fwd_ws = forward_layout(cfg).total;
     return CNERF_OK;
 }
 
@@ -358,135 +444,93 @@ int cnerf_pack_field(const cnerf_cfg* cfg, const cnerf_field_params* p, float* p
     g_err[0] = 0;
     if (int rc = check_cfg(cfg, false)) return rc;
     if (!p || !packed) return fail(CNERF_EINVAL, "pack_field: NULL argument");
-    hipStream_t stream = (hipStream_t)stream_;
-    const PackedLayout pl = packed_layout(cfg);
-    const int H = cfg->H, NT = H / 32;
-    float* wdst = packed;
-    float* bdst = packed + pl.weight_floats;
-    const size_t tile = 4 * 64 * 4;
-    if (cfg->layer_kind[0] == CNERF_LAYER_PFILM) {
+    // every parameter is checked before the first launch is queued
+    const bool pfilm = cfg->layer_kind[0] == CNERF_LAYER_PFILM, half = cfg->precision != CNERF_PREC_FP32;
+    MatrixSet ms;
+    if (pfilm) {
         if (cfg->C != 32 || cfg->n_levels > 1) return fail(CNERF_EINVAL, "per-point FiLM: a single 32-channel feature volume is supported");
         if (!p->map_w1 || !p->map_b1 || !p->map_w2 || !p->map_b2 || !p->w_final || !p->b_final)
             return fail(CNERF_EINVAL, "pack_field: mapping network / head is NULL");
         for (int l = 0; l < cfg->L; ++l)
             if (!p->w[l] || !p->b[l]) return fail(CNERF_EINVAL, "pack_field: layer %d weight/bias is NULL", l);
+    } else {
+        if (int rc = matrix_set(cfg, p, nullptr, "pack_field", ms)) return rc;
+        if (!p->w_final || !p->b_final) return fail(CNERF_EINVAL, "pack_field: head is NULL");
     }
-    if (cfg->layer_kind[0] == CNERF_LAYER_PFILM && cfg->precision != CNERF_PREC_FP32) {      // field_pw16.hip, see packed_layout()
-        const size_t parts = cfg->precision == CNERF_PREC_FP16 ? 1 : 2;
-        const size_t frag = 64 * 8 / 2;
-        const size_t big = 16 * parts * frag, small = 2 * (size_t)NT * parts * frag;
-        auto pack16 = cfg->precision == CNERF_PREC_FP16 ? launch_pack_h1 : launch_pack_h3;
-        const int L = cfg->L, n_slots = 3 * L + 2;
-        float* consts = packed + pl.weight_floats;
-        float* inv_s = consts + 256 + 3 * (size_t)L * H + 4 + (2 + 4 * (size_t)L + 3) / 4 * 4;     // [Wm1 | per layer: W_l, freq rows, phase rows | head]
-        float* wmax = inv_s + n_slots;
-        const size_t LH = (size_t)L * H;
-        if (hipError_t e = pack16(p->map_w1, 256, cfg->C, 8, true, wdst, inv_s, wmax, stream, 0)) return hip_fail(e, "pack_h3");
-        wdst += big;
-        if (hipError_t e = pack16(p->w[0], H, 3, NT, true, wdst, inv_s + 1, wmax + 1, stream, 0)) return hip_fail(e, "pack_h3");
-        wdst += small;
+    hipStream_t stream = (hipStream_t)stream_;
+    const PackedLayout pl = packed_layout(cfg);
+    const NetCounts nc = counts_of(cfg);
+    const int H = cfg->H, NT = H / 32, L = cfg->L;
+    const size_t LH = (size_t)L * H;
+    auto pack16 = cfg->precision == CNERF_PREC_FP16 ? launch_pack_h1 : launch_pack_h3;
+    const char* packer = half ? "pack_h3" : "pack_matrix";
+    float* wdst = packed;
+    float* inv_s = packed + pl.inv_s;
+    float* wmax = packed + pl.wmax;
+    float* bdst = packed + pl.weight_floats;
+    auto copy = [&](const float* src, size_t n) {          // the next n bias floats
+        const hipError_t e = hipMemcpyAsync(bdst, src, n * sizeof(float), hipMemcpyDeviceToDevice, stream);
+        bdst += n;
+        return e ? hip_fail(e, "bias copy") : CNERF_OK;
+    };
+    if (pfilm && half) {      // field_pw16.hip; pw16_consts_kernel writes the biases and constants
+        // slots of 1/S and max|W|: [Wm1 | per layer: W_l, freq rows, phase rows | head]; the layer matrices interleaved per output tile
+        const size_t big = pl.mat_floats(32, 256), small = pl.mat_floats(32, H);       // one output tile of a freq / phase and a W_l matrix
+        if (hipError_t e = pack16(p->map_w1, 256, cfg->C, 8, true, wdst, inv_s, wmax, stream, 0)) return hip_fail(e, packer);
+        wdst += pl.mat_floats(256, cfg->C);
+        if (hipError_t e = pack16(p->w[0], H, 3, NT, true, wdst, inv_s + 1, wmax + 1, stream, 0)) return hip_fail(e, packer);
+        wdst += pl.mat_floats(H, 3);
         for (int l = 0; l < L; ++l) {
             // the tiles of the layer's three matrices interleaved per output tile: [freq rows t | W_l t (l >= 1) | phase rows t]
             const long long t_stride = 16 + 16 + (l ? 2 * NT : 0);          // fragment pairs (one per k-chunk) per output tile
             const float* wf = p->map_w2 + (size_t)l * H * 256;
             const float* wp = p->map_w2 + (LH + (size_t)l * H) * 256;
             float* d = wdst;
-            if (hipError_t e = pack16(wf, H, 256, NT, false, d, inv_s + 2 + 3 * l, wmax + 2 + 3 * l, stream, t_stride)) return hip_fail(e, "pack_h3");
+            if (hipError_t e = pack16(wf, H, 256, NT, false, d, inv_s + 2 + 3 * l, wmax + 2 + 3 * l, stream, t_stride)) return hip_fail(e, packer);
             d += big;
             if (l) {
-                if (hipError_t e = pack16(p->w[l], H, H, NT, false, d, inv_s + 1 + 3 * l, wmax + 1 + 3 * l, stream, t_stride)) return hip_fail(e, "pack_h3");
+                if (hipError_t e = pack16(p->w[l], H, H, NT, false, d, inv_s + 1 + 3 * l, wmax + 1 + 3 * l, stream, t_stride)) return hip_fail(e, packer);
                 d += small;
             }
-            if (hipError_t e = pack16(wp, H, 256, NT, false, d, inv_s + 3 + 3 * l, wmax + 3 + 3 * l, stream, t_stride)) return hip_fail(e, "pack_h3");
+            if (hipError_t e = pack16(wp, H, 256, NT, false, d, inv_s + 3 + 3 * l, wmax + 3 + 3 * l, stream, t_stride)) return hip_fail(e, packer);
             wdst += (size_t)NT * (2 * big + (l ? small : 0));
         }
-        if (hipError_t e = pack16(p->w_final, 4, H, 1, false, wdst, inv_s + 3 * L + 1, wmax + 3 * L + 1, stream, 0)) return hip_fail(e, "pack_h3");
-        if (hipError_t e = launch_pw16_consts(p, L, H, inv_s, consts, stream)) return hip_fail(e, "pw16_consts");
+        if (hipError_t e = pack16(p->w_final, 4, H, 1, false, wdst, inv_s + 3 * L + 1, wmax + 3 * L + 1, stream, 0)) return hip_fail(e, packer);
+        if (hipError_t e = launch_pw16_consts(p, L, H, inv_s, bdst, stream)) return hip_fail(e, "pw16_consts");
         return CNERF_OK;
     }
-    if (cfg->layer_kind[0] == CNERF_LAYER_PFILM) {
-        auto cp = [&](const float* src, size_t n) { return hipMemcpyAsync(bdst, src, n * sizeof(float), hipMemcpyDeviceToDevice, stream); };
-        if (hipError_t e = launch_pack_matrix(p->map_w1, 256, cfg->C, 8, wdst, stream)) return hip_fail(e, "pack_matrix");
-        wdst += 8 * tile;
-        if (hipError_t e = cp(p->map_b1, 256)) return hip_fail(e, "bias copy");
-        bdst += 256;
-        const size_t LH = (size_t)cfg->L * H;
-        for (int l = 0; l < cfg->L; ++l) {
+    if (pfilm) {              // fp32: mapping hidden | per layer (main, freq rows, phase rows) | head
+        if (hipError_t e = launch_pack_matrix(p->map_w1, 256, cfg->C, 8, wdst, stream)) return hip_fail(e, packer);
+        wdst += pl.mat_floats(256, cfg->C);
+        if (int rc = copy(p->map_b1, 256)) return rc;
+        for (int l = 0; l < L; ++l) {
             const int K = (l == 0) ? 3 : H;
-            if (!p->w[l] || !p->b[l]) return fail(CNERF_EINVAL, "pack_field: layer %d weight/bias is NULL", l);
-            if (hipError_t e = launch_pack_matrix(p->w[l], H, K, NT, wdst, stream)) return hip_fail(e, "pack_matrix");
-            wdst += (size_t)NT * ((K + 31) / 32) * tile;
-            if (hipError_t e = launch_pack_matrix(p->map_w2 + (size_t)l * H * 256, H, 256, NT, wdst, stream)) return hip_fail(e, "pack_matrix");
-            wdst += (size_t)NT * 8 * tile;
-            if (hipError_t e = launch_pack_matrix(p->map_w2 + (LH + (size_t)l * H) * 256, H, 256, NT, wdst, stream)) return hip_fail(e, "pack_matrix");
-            wdst += (size_t)NT * 8 * tile;
-            if (hipError_t e = cp(p->b[l], H)) return hip_fail(e, "bias copy");
-            bdst += H;
-            if (hipError_t e = cp(p->map_b2 + (size_t)l * H, H)) return hip_fail(e, "bias copy");
-            bdst += H;
-            if (hipError_t e = cp(p->map_b2 + LH + (size_t)l * H, H)) return hip_fail(e, "bias copy");
-            bdst += H;
+            if (hipError_t e = launch_pack_matrix(p->w[l], H, K, NT, wdst, stream)) return hip_fail(e, packer);
+            wdst += pl.mat_floats(H, K);
+            if (hipError_t e = launch_pack_matrix(p->map_w2 + (size_t)l * H * 256, H, 256, NT, wdst, stream)) return hip_fail(e, packer);
+            wdst += pl.mat_floats(H, 256);
+            if (hipError_t e = launch_pack_matrix(p->map_w2 + (LH + (size_t)l * H) * 256, H, 256, NT, wdst, stream)) return hip_fail(e, packer);
+            wdst += pl.mat_floats(H, 256);
+            if (int rc = copy(p->b[l], H)) return rc;
+            if (int rc = copy(p->map_b2 + (size_t)l * H, H)) return rc;
+            if (int rc = copy(p->map_b2 + LH + (size_t)l * H, H)) return rc;
         }
-        if (hipError_t e = launch_pack_head(p->w_final, H, wdst, stream)) return hip_fail(e, "pack_matrix");
-        if (hipError_t e = cp(p->b_final, 4)) return hip_fail(e, "bias copy");
-        bdst += 4;
-        if (hipError_t e = launch_fill(bdst, 1.0f, H, stream)) return hip_fail(e, "fill");
-        if (hipError_t e = launch_fill(bdst + H, 0.0f, H, stream)) return hip_fail(e, "fill");
-        return CNERF_OK;
-    }
-    if (cfg->precision == CNERF_PREC_FP16X3 || cfg->precision == CNERF_PREC_FP16) {
-        const size_t frag = 64 * 8 / 2;
-        const size_t parts = cfg->precision == CNERF_PREC_FP16 ? 1 : 2;
-        auto pack16 = cfg->precision == CNERF_PREC_FP16 ? launch_pack_h1 : launch_pack_h3;
-        int mats = 0;
-        for (int l = 0; l < cfg->L; ++l) mats += cfg->layer_kind[l] == CNERF_LAYER_RES ? 2 : 1;
-        float* inv_scale = packed + pl.weight_floats + (size_t)mats * H + 4;     // 1/S per matrix and the head's, then the max|W| scratch
-        float* wmax = inv_scale + mats + 1;
-        int m = 0;
-        for (int l = 0; l < cfg->L; ++l) {
-            const int K = (l == 0) ? pl.k0 : H;
-            const bool res = cfg->layer_kind[l] == CNERF_LAYER_RES;
-            if (!p->w[l] || !p->b[l]) return fail(CNERF_EINVAL, "pack_field: layer %d weight/bias is NULL", l);
-            if (res && (!p->w2[l] || !p->b2[l])) return fail(CNERF_EINVAL, "pack_field: residual layer %d fc2 is NULL", l);
-            for (int half = 0; half < (res ? 2 : 1); ++half) {
-                const float* w = half ? p->w2[l] : p->w[l];
-                const float* b = half ? p->b2[l] : p->b[l];
-                if (hipError_t e = pack16(w, H, K, NT, l == 0, wdst, inv_scale + m, wmax + m, stream, 0)) return hip_fail(e, "pack_h3");
-                wdst += (size_t)NT * ((K + 31) / 32 * 2) * parts * frag;
-                if (hipError_t e = hipMemcpyAsync(bdst, b, H * sizeof(float), hipMemcpyDeviceToDevice, stream)) return hip_fail(e, "bias copy");
-                bdst += H;
-                ++m;
-            }
-        }
-        if (!p->w_final || !p->b_final) return fail(CNERF_EINVAL, "pack_field: head is NULL");
-        if (hipError_t e = pack16(p->w_final, 4, H, 1, false, wdst, inv_scale + m, wmax + m, stream, 0)) return hip_fail(e, "pack_h3");
-        if (hipError_t e = hipMemcpyAsync(bdst, p->b_final, 4 * sizeof(float), hipMemcpyDeviceToDevice, stream)) return hip_fail(e, "bias copy");
-        bdst = packed + pl.weight_floats + pl.bias_floats;
-        if (hipError_t e = launch_fill(bdst, 1.0f, H, stream)) return hip_fail(e, "fill");
-        if (hipError_t e = launch_fill(bdst + H, 0.0f, H, stream)) return hip_fail(e, "fill");
-        return CNERF_OK;
-    }
-    for (int l = 0; l < cfg->L; ++l) {
-        const int K = (l == 0) ? pl.k0 : H;                    // layer 0: C (+3), zero padded to 32 * n_in columns
-        if (!p->w[l] || !p->b[l]) return fail(CNERF_EINVAL, "pack_field: layer %d weight/bias is NULL", l);
-        if (hipError_t e = launch_pack_matrix(p->w[l], H, K, NT, wdst, stream)) return hip_fail(e, "pack_matrix");
-        wdst += (size_t)NT * ((K + 31) / 32) * tile;
-        if (hipError_t e = hipMemcpyAsync(bdst, p->b[l], H * sizeof(float), hipMemcpyDeviceToDevice, stream)) return hip_fail(e, "bias copy");
-        bdst += H;
-        if (cfg->layer_kind[l] == CNERF_LAYER_RES) {
-            if (!p->w2[l] || !p->b2[l]) return fail(CNERF_EINVAL, "pack_field: residual layer %d fc2 is NULL", l);
-            if (hipError_t e = launch_pack_matrix(p->w2[l], H, H, NT, wdst, stream)) return hip_fail(e, "pack_matrix");
-            wdst += (size_t)NT * NT * tile;
-            if (hipError_t e = hipMemcpyAsync(bdst, p->b2[l], H * sizeof(float), hipMemcpyDeviceToDevice, stream)) return hip_fail(e, "bias copy");
-            bdst += H;
+    } else {                  // FiLM / plain-sine / residual: every matrix in slab order, then the head (one 32-row tile)
+        for (int m = 0; m < nc.n_mats; ++m) {
+            const int K = m == 0 ? nc.k0 : H;                  // layer 0: C (+3), zero padded to 32 * n_in columns
+            if (hipError_t e = half ? pack16(ms.W[m], H, K, NT, m == 0, wdst, inv_s + m, wmax + m, stream, 0)
+                                    : launch_pack_matrix(ms.W[m], H, K, NT, wdst, stream))
+                return hip_fail(e, packer);
+            wdst += pl.mat_floats(H, K);
+            if (int rc = copy(ms.b[m], H)) return rc;
         }
     }
-    if (!p->w_final || !p->b_final) return fail(CNERF_EINVAL, "pack_field: head is NULL");
-    if (hipError_t e = launch_pack_head(p->w_final, H, wdst, stream)) return hip_fail(e, "pack_matrix");
-    if (hipError_t e = hipMemcpyAsync(bdst, p->b_final, 4 * sizeof(float), hipMemcpyDeviceToDevice, stream)) return hip_fail(e, "bias copy");
-    bdst += 4;
-    if (hipError_t e = launch_fill(bdst, 1.0f, H, stream)) return hip_fail(e, "fill");
-    if (hipError_t e = launch_fill(bdst + H, 0.0f, H, stream)) return hip_fail(e, "fill");
+    if (hipError_t e = half ? pack16(p->w_final, 4, H, 1, false, wdst, inv_s + nc.n_mats, wmax + nc.n_mats, stream, 0)
+                            : launch_pack_head(p->w_final, H, wdst, stream))
+        return hip_fail(e, packer);
+    if (int rc = copy(p->b_final, 4)) return rc;
+    if (hipError_t e = launch_fill(packed + pl.ones, 1.0f, H, stream)) return hip_fail(e, "fill");
+    if (hipError_t e = launch_fill(packed + pl.zeros, 0.0f, H, stream)) return hip_fail(e, "fill");
     return CNERF_OK;
 }
 
@@ -529,15 +573,10 @@ int cnerf_field_forward(const cnerf_cfg* cfg, const cnerf_volumes* vols, const f
     g_err[0] = 0;
     if (int rc = check_cfg(cfg, false)) return rc;
     if (!vols || !packed || !points || !rgb_sigma || n_per_image < 1) return fail(CNERF_EINVAL, "field_forward: bad argument");
-    const PackedLayout pl = packed_layout(cfg);
-    if (pl.n_film && (!freq || !phase)) return fail(CNERF_EINVAL, "field_forward: FiLM layers need freq and phase");
+    if (counts_of(cfg).n_film && (!freq || !phase)) return fail(CNERF_EINVAL, "field_forward: FiLM layers need freq and phase");
     FieldArgs a;
-    if (int rc = fill_field_args(a, cfg, vols, nullptr, packed, freq, phase)) return rc;
-    a.mode = FIELD_MODE_POINTS;
-    a.points = points;
+    if (int rc = points_args(a, cfg, vols, nullptr, packed, freq, phase, points, 0, cfg->B, n_per_image, nullptr)) return rc;
     a.rgb_sigma = rgb_sigma;
-    set_points(a, cfg->B, n_per_image);
-    set_dropout(a, cfg, nullptr, PHILOX_DROP_POINTS, n_per_image);
     if (hipError_t e = launch_forward(a, cfg, (hipStream_t)stream)) return hip_fail(e, "field kernel");
     return CNERF_OK;
 }
@@ -566,29 +605,20 @@ int cnerf_render_forward(const cnerf_cfg* cfg, const cnerf_volumes* vols, const 
     g_err[0] = 0;
     if (int rc = check_cfg(cfg, true)) return rc;
     if (!vols || !packed || !cam2world || !pixels || !depth || !workspace) return fail(CNERF_EINVAL, "render_forward: NULL argument");
-    const PackedLayout pl = packed_layout(cfg);
-    if (pl.n_film && (!freq || !phase)) return fail(CNERF_EINVAL, "render_forward: FiLM layers need freq and phase");
+    if (counts_of(cfg).n_film && (!freq || !phase)) return fail(CNERF_EINVAL, "render_forward: FiLM layers need freq and phase");
     const bool hier = cfg->flags & CNERF_F_HIERARCHICAL;
-    static const cnerf_rng no_rng = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-    if (!rng) rng = &no_rng;
+    rng = rng_or_none(rng);
     if (hier && !rng->u_fine && !cfg->philox) return fail(CNERF_EINVAL, "render_forward: hierarchical sampling needs rng.u_fine (or cfg.philox)");
     hipStream_t stream = (hipStream_t)stream_;
 
     const long long P = (long long)cfg->R * cfg->R, S = cfg->S;
     const long long npi = P * S;
-    const size_t N = (size_t)cfg->B * npi;
+    const ForwardLayout F = forward_layout(cfg);
     char* ws = (char*)workspace;
-    float* c_rs = (float*)ws; ws += align256(N * 4 * sizeof(float));
-    float* f_rs = (float*)ws; ws += align256(N * 4 * sizeof(float));
-    float* c_z = (float*)ws;  ws += align256(N * sizeof(float));
-    float* f_z = (float*)ws;  ws += align256(N * sizeof(float));
-    float* fold = (float*)ws;
-    {
-        size_t mats = 0;
-        for (int l = 0; l < cfg->L; ++l) mats += cfg->layer_kind[l] == CNERF_LAYER_RES ? 2 : 1;
-        ws += align256((size_t)4 * cfg->B * mats * cfg->H * sizeof(float));
-    }
-    float* packed_img = (float*)ws;
+    float* c_rs = (float*)(ws + F.c_rs);
+    float* f_rs = (float*)(ws + F.f_rs);
+    float* c_z = (float*)(ws + F.c_z);
+    float* f_z = (float*)(ws + F.f_z);
     if (aux) {   // write straight into the caller's buffers where given
         if (aux->coarse_rgb_sigma) c_rs = aux->coarse_rgb_sigma;
         if (aux->fine_rgb_sigma) f_rs = aux->fine_rgb_sigma;
@@ -603,27 +633,23 @@ int cnerf_render_forward(const cnerf_cfg* cfg, const cnerf_volumes* vols, const 
     // the exact fp32 precision: FiLM (plain sine: freq 1, phase 0) folded into one affine map per matrix and channel, prepared once
     // for both passes (per-point FiLM computes its frequencies per point: not foldable)
     if (cfg->precision == CNERF_PREC_FP32 && cfg->layer_kind[0] != CNERF_LAYER_PFILM && cfg->drop_p == 0.0f) {
+        float* fold = (float*)(ws + F.fold);
+        float* packed_img = (float*)(ws + F.packed_img);
         if (hipError_t e = launch_fold_film(fa, cfg->B, cfg->H, fold, stream)) return hip_fail(e, "fold_film");
         fa.fold = fold;
         fa.fold_images = cfg->B;
-        {                                 // the scale goes into per-image copies of the layer weights (WFOLD, field_kernel.hip)
-            const size_t NT = cfg->H / 32;
-            const long long layer_floats = (long long)((NT * pl.n_in + (size_t)(fa.n_mats - 1) * NT * NT) * 1024);
-            if (hipError_t e = launch_scale_packed(fa, cfg->B, cfg->H, fold, layer_floats, packed_img, stream)) return hip_fail(e, "scale_packed");
-            fa.packed_img = packed_img;
-            fa.packed_img_stride = layer_floats;
-        }
+        // the scale goes into per-image copies of the layer weights (WFOLD, field_kernel.hip)
+        if (hipError_t e = launch_scale_packed(fa, cfg->B, cfg->H, fold, F.layer_floats, packed_img, stream)) return hip_fail(e, "scale_packed");
+        fa.packed_img = packed_img;
+        fa.packed_img_stride = F.layer_floats;
     }
     // the fp16 precisions: the same folding on two-part fp16 weights -- per-image copies of the packed stream, the accumulators start
     // from (freq bias + phase) / 2 pi, the epilogue is one multiply, the range reduction and v_sin (field_h3.hip)
     if (cfg->precision != CNERF_PREC_FP32 && cfg->layer_kind[0] != CNERF_LAYER_PFILM) {
-        char* w16 = (char*)fold;                  // (the fp32 regions are not used in these precisions: same place in the workspace)
-        void* img = w16;
-        w16 += align256((size_t)cfg->B * pl.weight_floats * sizeof(float));
-        float* fold16 = (float*)w16;
-        w16 += align256((size_t)cfg->B * fa.n_mats * (cfg->H + 1) * sizeof(float));
-        float* rowf = (float*)w16;
-        const long long img_elems = (long long)pl.weight_floats * 2;            // fp16 elements of the packed weight stream
+        void* img = ws + F.img16;
+        float* fold16 = (float*)(ws + F.fold16);
+        float* rowf = (float*)(ws + F.rowf);
+        const long long img_elems = (long long)packed_layout(cfg).weight_floats * 2;      // fp16 elements of the packed weight stream
         if (hipError_t e = (cfg->precision == CNERF_PREC_FP16 ? launch_fold_h1 : launch_fold_h3)(fa, cfg->B, cfg->H, img, fold16, rowf, img_elems, stream))
             return hip_fail(e, "fold16");
         fa.packed_img = (const float*)img;
@@ -696,11 +722,11 @@ int cnerf_render_forward(const cnerf_cfg* cfg, const cnerf_volumes* vols, const 
 int cnerf_backward_bytes(const cnerf_cfg* cfg, size_t* packed_t) {
     g_err[0] = 0;
     if (int rc = check_cfg(cfg, false)) return rc;
+    const NetCounts nc = counts_of(cfg);
     const size_t NT = cfg->H / 32, tile = 4 * 64 * 4;
-    size_t fl = NT * 2 * 64;                                  // head^T
-    for (int l = cfg->L - 1; l >= 1; --l) fl += (cfg->layer_kind[l] == CNERF_LAYER_RES ? 2 : 1) * NT * NT * tile;
+    size_t fl = NT * 2 * 64 + (size_t)(nc.n_mats - 1) * NT * NT * tile;     // head^T, the matrices after layer 0
     if (cfg->layer_kind[0] != CNERF_LAYER_PFILM)             // (per-point FiLM: layer 0 reads the sample position, no gradient)
-        fl += (size_t)packed_layout(cfg).n_in * NT * tile;   // layer 0 transposed: one 32-row output tile per input tile
+        fl += (size_t)nc.n_in * NT * tile;                   // layer 0 transposed: one 32-row output tile per input tile
     if (packed_t) *packed_t = align256(fl * sizeof(float));
     return CNERF_OK;
 }
@@ -728,8 +754,8 @@ int cnerf_pack_field_transposed(const cnerf_cfg* cfg, const cnerf_field_params* 
     }
     if (cfg->layer_kind[0] == CNERF_LAYER_PFILM) return CNERF_OK;      // head^T and W_l^T of layers L-1..1 only
     if (!p->w[0]) return fail(CNERF_EINVAL, "pack_field_transposed: layer 0 weight is NULL");
-    const PackedLayout pl = packed_layout(cfg);
-    if (hipError_t e = launch_pack_matrix_t(p->w[0], H, pl.k0, pl.n_in, dst, stream)) return hip_fail(e, "pack_matrix_t");
+    const NetCounts nc = counts_of(cfg);
+    if (hipError_t e = launch_pack_matrix_t(p->w[0], H, nc.k0, nc.n_in, dst, stream)) return hip_fail(e, "pack_matrix_t");
     return CNERF_OK;
 }
 
@@ -764,11 +790,9 @@ int cnerf_field_backward(const cnerf_cfg* cfg, int32_t pass, int32_t image0, int
     if (!vols || !packed || !packed_t || !cam2world || !grad_rgb_sigma || !saved_rgb_sigma || !act_feat || !act_h || !act_c ||
         !act_g || !act_go || !grad_vols)
         return fail(CNERF_EINVAL, "field_backward: NULL argument");
-    for (int i = 0; i < n_levels_of(cfg); ++i)
-        if (!grad_vols->level[i]) return fail(CNERF_EINVAL, "field_backward: gradient volume %d is NULL", i);
+    if (int rc = check_grad_vols(cfg, grad_vols, "field_backward")) return rc;
     if (pass == 1 && !fine_z) return fail(CNERF_EINVAL, "field_backward: the fine pass needs fine_z");
-    const PackedLayout pl = packed_layout(cfg);
-    if (pl.n_film && (!freq || !phase)) return fail(CNERF_EINVAL, "field_backward: FiLM layers need freq and phase");
+    if (counts_of(cfg).n_film && (!freq || !phase)) return fail(CNERF_EINVAL, "field_backward: FiLM layers need freq and phase");
     hipStream_t stream = (hipStream_t)stream_;
     const long long npi = (long long)cfg->R * cfg->R * cfg->S;
 
@@ -790,15 +814,10 @@ int cnerf_field_backward_points(const cnerf_cfg* cfg, const cnerf_volumes* vols,
     if (!vols || !packed || !packed_t || !points || n_per_image < 1 || !grad_rgb_sigma || !saved_rgb_sigma || !act_feat || !act_h || !act_c || !act_g ||
         !act_go || !grad_vols)
         return fail(CNERF_EINVAL, "field_backward_points: NULL argument");
-    for (int i = 0; i < n_levels_of(cfg); ++i)
-        if (!grad_vols->level[i]) return fail(CNERF_EINVAL, "field_backward_points: gradient volume %d is NULL", i);
-    if (packed_layout(cfg).n_film && (!freq || !phase)) return fail(CNERF_EINVAL, "field_backward_points: FiLM layers need freq and phase");
+    if (int rc = check_grad_vols(cfg, grad_vols, "field_backward_points")) return rc;
+    if (counts_of(cfg).n_film && (!freq || !phase)) return fail(CNERF_EINVAL, "field_backward_points: FiLM layers need freq and phase");
     FieldArgs fa;
-    if (int rc = fill_field_args(fa, cfg, vols, grad_vols, packed, freq, phase)) return rc;
-    fa.mode = FIELD_MODE_POINTS;
-    fa.points = points;
-    set_points(fa, cfg->B, n_per_image);
-    set_dropout(fa, cfg, drop_mask, PHILOX_DROP_POINTS, n_per_image);
+    if (int rc = points_args(fa, cfg, vols, grad_vols, packed, freq, phase, points, 0, cfg->B, n_per_image, drop_mask)) return rc;
     return field_backward_run(fa, cfg, (long long)cfg->B * n_per_image, packed_t, grad_rgb_sigma, saved_rgb_sigma, act_feat, act_h, act_c, act_g,
                               act_go, (hipStream_t)stream);
 }
@@ -825,17 +844,14 @@ struct Chain16Layout {
     int n_mats, n_in, k0, ot0;
 };
 int chain16_layout(const cnerf_cfg* c, Chain16Layout& l) {
-    l.n_mats = 0;
-    for (int i = 0; i < c->L; ++i) {
-        if (c->layer_kind[i] == CNERF_LAYER_PFILM)
-            return fail(CNERF_ENOSYS, "half-precision backward: FiLM / plain-sine / residual layers only (layer %d is per-point FiLM)", i);
-        l.n_mats += c->layer_kind[i] == CNERF_LAYER_RES ? 2 : 1;      // a residual block: fc1 and fc2
-    }
+    if (c->layer_kind[0] == CNERF_LAYER_PFILM)         // (all layers or none, check_cfg)
+        return fail(CNERF_ENOSYS, "half-precision backward: FiLM / plain-sine / residual layers only (layer 0 is per-point FiLM)");
     const size_t NT = c->H / 32, KCH = 2 * NT, frag = 64 * 16;
-    const PackedLayout pl = packed_layout(c);
-    l.n_in = pl.n_in;
-    l.k0 = pl.k0;
-    l.ot0 = (pl.n_in + 1) / 2 * 2;
+    const NetCounts nc = counts_of(c);
+    l.n_mats = nc.n_mats;
+    l.n_in = nc.n_in;
+    l.k0 = nc.k0;
+    l.ot0 = (nc.n_in + 1) / 2 * 2;
     l.units_bytes = ((size_t)(l.n_mats - 1) * NT + l.ot0) * KCH * frag;
     l.head_off = align256(l.units_bytes);
     l.winv_off = l.head_off + align256(NT * frag);
@@ -981,11 +997,10 @@ int chunk_layout(const cnerf_cfg* c, int bprec, int cnt, size_t npi, size_t N_ou
     }
     if (have_act16 && (bprec != CNERF_PREC_FP16 || cnt != c->B)) return fail(CNERF_EINVAL, "%s: kept activations need the fp16 backward and images_per_chunk = B", who);
     if (bprec == CNERF_PREC_FP16 && c->precision != CNERF_PREC_FP16X3) return fail(CNERF_EINVAL, "%s: the fp16 backward re-runs the fp16x3 forward (cfg->precision)", who);
-    const PackedLayout pl = packed_layout(c);
-    L.n_in = pl.n_in;
-    L.k0 = pl.k0;
-    L.n_mats = 0;
-    for (int l = 0; l < c->L; ++l) L.n_mats += c->layer_kind[l] == CNERF_LAYER_RES ? 2 : 1;
+    const NetCounts nc = counts_of(c);
+    L.n_in = nc.n_in;
+    L.k0 = nc.k0;
+    L.n_mats = nc.n_mats;
     const size_t H = c->H, NT = H / 32, tpi = (npi + 31) / 32;
     const size_t n = (size_t)cnt * npi, T = (size_t)cnt * tpi;
     size_t off = 0;
@@ -1055,35 +1070,6 @@ int reduce16(int cnt, long long tpi, int n_rows, int g_ct, int x_ct, const void*
 bool scatter_by_chain() {
     const char* s = getenv("CNERF_SCATTER");
     return s && !strcmp(s, "chain");
-}
-
-// The matrices of a FiLM / plain-sine / residual network in slab order (a residual block: fc1, fc2), their kinds and gradient buffers
-struct MatrixSet {
-    const float *W[2 * CNERF_MAX_LAYERS], *b[2 * CNERF_MAX_LAYERS];
-    float *dW[2 * CNERF_MAX_LAYERS], *db[2 * CNERF_MAX_LAYERS];
-    int film_of[2 * CNERF_MAX_LAYERS];
-    int H, film_stride;
-    // matrix m's slice of freq / grad_freq / grad_phase for the chunk from image b0 (NULL unless m is a FiLM matrix)
-    const float* film(const float* t, int m, int b0) const { return film_of[m] >= 0 ? t + (size_t)b0 * film_stride + (size_t)film_of[m] * H : nullptr; }
-    float* film(float* t, int m, int b0) const { return film_of[m] >= 0 ? t + (size_t)b0 * film_stride + (size_t)film_of[m] * H : nullptr; }
-};
-int matrix_set(const cnerf_cfg* cfg, const cnerf_field_params* P, const cnerf_field_param_grads* G, const char* who, MatrixSet& ms) {
-    int nm = 0, nfilm = 0;
-    for (int l = 0; l < cfg->L; ++l) {
-        const bool res = cfg->layer_kind[l] == CNERF_LAYER_RES;
-        if (!P->w[l] || !P->b[l] || (res && (!P->w2[l] || !P->b2[l]))) return fail(CNERF_EINVAL, "%s: parameters of layer %d are NULL", who, l);
-        ms.W[nm] = P->w[l]; ms.b[nm] = P->b[l]; ms.dW[nm] = G->w[l]; ms.db[nm] = G->b[l];
-        ms.film_of[nm] = cfg->layer_kind[l] == CNERF_LAYER_FILM ? nfilm++ : -1;
-        ++nm;
-        if (res) {
-            ms.W[nm] = P->w2[l]; ms.b[nm] = P->b2[l]; ms.dW[nm] = G->w2[l]; ms.db[nm] = G->b2[l];
-            ms.film_of[nm] = -1;
-            ++nm;
-        }
-    }
-    ms.H = cfg->H;
-    ms.film_stride = packed_layout(cfg).n_film * cfg->H;
-    return CNERF_OK;
 }
 
 // ---- chunk bodies: one chunk of cnt images (from image b0 of the call) of npi points (tpi tiles) each.  The render runs them per ray
@@ -1271,15 +1257,13 @@ int cnerf_render_backward(const cnerf_cfg* cfg, int32_t bprec, int32_t cnt_max, 
     if (int rc = backward_layout(cfg, bprec, cnt_max, have_act16, L)) return rc;
     if (!vols || !P || !packed || !packed_bwd || !cam2world || !saved || !grad_pixels || !G || !grad_vols || !workspace)
         return fail(CNERF_EINVAL, "render_backward: NULL argument");
-    for (int i = 0; i < n_levels_of(cfg); ++i)
-        if (!grad_vols->level[i]) return fail(CNERF_EINVAL, "render_backward: gradient volume %d is NULL", i);
+    if (int rc = check_grad_vols(cfg, grad_vols, "render_backward")) return rc;
     const bool hier = cfg->flags & CNERF_F_HIERARCHICAL;
     if (!saved->coarse_rgb_sigma || !saved->coarse_z || (hier && (!saved->fine_rgb_sigma || !saved->fine_z)))
         return fail(CNERF_EINVAL, "render_backward: saved rgb_sigma / z of the forward are incomplete");
-    const PackedLayout pl = packed_layout(cfg);
-    if (pl.n_film && (!freq || !phase || !grad_freq || !grad_phase)) return fail(CNERF_EINVAL, "render_backward: FiLM layers need freq, phase and their gradient buffers");
-    static const cnerf_rng no_rng = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-    if (!rng) rng = &no_rng;
+    if (counts_of(cfg).n_film && (!freq || !phase || !grad_freq || !grad_phase))
+        return fail(CNERF_EINVAL, "render_backward: FiLM layers need freq, phase and their gradient buffers");
+    rng = rng_or_none(rng);
     hipStream_t stream = (hipStream_t)stream_;
     const int B = cfg->B;
     const long long npi = (long long)cfg->R * cfg->R * cfg->S, tpi = (npi + 31) / 32;
@@ -1382,11 +1366,9 @@ struct QueryLayout {
 int query_layout(const cnerf_cfg* c, int bprec, long long ppc, QueryLayout& Q) {
     if (ppc < 1) return fail(CNERF_EINVAL, "field_query_backward: points_per_chunk=%lld must be >= 1", ppc);
     if (int rc = chunk_layout(c, bprec, 1, (size_t)ppc, 0, false, false, false, "field_query_backward", Q.L)) return rc;
-    int n_drop = 0;
-    for (int l = 0; l < c->L; ++l) n_drop += c->layer_kind[l] != CNERF_LAYER_RES;
     Q.rows = Q.L.total;
     Q.mask = Q.rows + align256((size_t)ppc * 256 * sizeof(float));
-    Q.total = Q.mask + align256(c->drop_p > 0.0f ? (size_t)n_drop * ppc * c->H : 0);
+    Q.total = Q.mask + align256(c->drop_p > 0.0f ? (size_t)counts_of(c).n_drop * ppc * c->H : 0);
     return CNERF_OK;
 }
 }  // namespace
@@ -1412,10 +1394,8 @@ int cnerf_field_query_backward(const cnerf_cfg* cfg, int32_t bprec, int64_t poin
     const BackwardLayout& L = Q.L;
     if (!vols || !P || !packed || !packed_bwd || !points || !saved_rgb_sigma || !grad_rgb_sigma || !G || !grad_vols || !workspace || n_per_image < 1)
         return fail(CNERF_EINVAL, "field_query_backward: NULL argument or no points");
-    for (int i = 0; i < n_levels_of(cfg); ++i)
-        if (!grad_vols->level[i]) return fail(CNERF_EINVAL, "field_query_backward: gradient volume %d is NULL", i);
-    const PackedLayout pl = packed_layout(cfg);
-    if (pl.n_film && (!freq || !phase || !grad_freq || !grad_phase))
+    if (int rc = check_grad_vols(cfg, grad_vols, "field_query_backward")) return rc;
+    if (counts_of(cfg).n_film && (!freq || !phase || !grad_freq || !grad_phase))
         return fail(CNERF_EINVAL, "field_query_backward: FiLM layers need freq, phase and their gradient buffers");
     const bool pfilm = cfg->layer_kind[0] == CNERF_LAYER_PFILM;
     if (pfilm) {
@@ -1444,11 +1424,7 @@ int cnerf_field_query_backward(const cnerf_cfg* cfg, int32_t bprec, int64_t poin
             const float* s_out = saved_rgb_sigma + row0 * 4;
             // the chunk's field pass: image b, points [p0, p0 + np); fa without, fc with the gradient volumes
             FieldArgs fa, fc;
-            if (int rc = fill_field_args(fa, cfg, vols, nullptr, packed, freq, phase, b)) return rc;
-            fa.mode = FIELD_MODE_POINTS;
-            fa.points = pts;
-            set_points(fa, 1, np);
-            set_dropout(fa, cfg, nullptr, PHILOX_DROP_POINTS, np);
+            if (int rc = points_args(fa, cfg, vols, nullptr, packed, freq, phase, pts, b, 1, np, nullptr)) return rc;
             if (cfg->drop_p > 0.0f) {
                 // the forward's decisions of these points (Philox stream PHILOX_DROP_POINTS at their index in the whole call), as keep bytes
                 // with chunk-local rows: the kernels index them by (image0 + b) * n_per_image + point = the point's row in the chunk
@@ -1459,10 +1435,7 @@ int cnerf_field_query_backward(const cnerf_cfg* cfg, int32_t bprec, int64_t poin
                 fa.image0 = 0;
             }
             fc = fa;
-            for (int i = 0; i < n_levels_of(cfg); ++i) {
-                const int V = level_V_of(cfg, i);
-                fc.lvl_grad[i] = grad_vols->level[i] + (size_t)b * V * V * V * level_C_of(cfg, i);
-            }
+            for (int i = 0; i < n_levels_of(cfg); ++i) fc.lvl_grad[i] = grad_vols->level[i] + (size_t)b * level_floats(cfg, i);
             fc.gin = nullptr;            // points are no pixel patches: the chain adds its input-tile gradients with its own atomics
             if (pfilm) {
                 if (int rc = chunk_pw16(cfg, L, ws, packed_bwd, fc, k, g_out, s_out, ws + L.a_feat, ws + L.a_h, ws + L.a_c, (float*)(ws + L.a_amax), true, G,
@@ -1513,22 +1486,11 @@ int cnerf_field_query_backward(const cnerf_cfg* cfg, int32_t bprec, int64_t poin
                 ig.k_in = L.k0;
             }
             if (hipError_t e = launch_input_grad(ig, stream)) return hip_fail(e, "input_grad");
-            PointsGradArgs pg{};
-            for (int i = 0; i < n_levels_of(cfg); ++i) {
-                const int V = level_V_of(cfg, i), Cl = level_C_of(cfg, i);
-                pg.lvl_vol[i] = vols->level[i] + (size_t)b * V * V * V * Cl;
-                pg.lvl_V[i] = V;
-                pg.lvl_C[i] = Cl;
-            }
-            pg.n_levels = n_levels_of(cfg);
-            pg.points = pts;
+            PointsGradArgs pg = points_grad_args(cfg, vols, b, pts, grad_points + row0 * 3, np);
             pg.gfeat = rows;
             pg.ldf = 256;
             pg.gxyz = (pfilm || (cfg->flags & CNERF_F_INPUT_XYZ)) ? rows + cfg->C : nullptr;
             pg.ldx = 256;
-            pg.grad_points = grad_points + row0 * 3;
-            pg.n = np;
-            pg.half_voxel = cfg->voxel_length / 2.0f;
             if (hipError_t e = launch_points_lookup_grad(pg, stream)) return hip_fail(e, "points_lookup_grad");
         }
     }
@@ -1540,23 +1502,13 @@ int cnerf_feature_points_grad(const cnerf_cfg* cfg, const cnerf_volumes* vols, c
     g_err[0] = 0;
     if (int rc = check_cfg(cfg, false)) return rc;
     if (!vols || !points || !grad_feat || !grad_points || n_per_image < 1) return fail(CNERF_EINVAL, "feature_points_grad: bad argument");
+    for (int i = 0; i < n_levels_of(cfg); ++i)
+        if (!vols->level[i]) return fail(CNERF_EINVAL, "feature_points_grad: volume level %d is NULL", i);
     for (int b = 0; b < cfg->B; ++b) {
-        PointsGradArgs pg{};
-        for (int i = 0; i < n_levels_of(cfg); ++i) {
-            const int V = level_V_of(cfg, i), Cl = level_C_of(cfg, i);
-            if (!vols->level[i]) return fail(CNERF_EINVAL, "feature_points_grad: volume level %d is NULL", i);
-            pg.lvl_vol[i] = vols->level[i] + (size_t)b * V * V * V * Cl;
-            pg.lvl_V[i] = V;
-            pg.lvl_C[i] = Cl;
-        }
         const size_t row0 = (size_t)b * n_per_image;
-        pg.n_levels = n_levels_of(cfg);
-        pg.points = points + row0 * 3;
+        PointsGradArgs pg = points_grad_args(cfg, vols, b, points + row0 * 3, grad_points + row0 * 3, n_per_image);
         pg.gfeat = grad_feat + row0 * cfg->C;
         pg.ldf = cfg->C;
-        pg.grad_points = grad_points + row0 * 3;
-        pg.n = n_per_image;
-        pg.half_voxel = cfg->voxel_length / 2.0f;
         if (hipError_t e = launch_points_lookup_grad(pg, (hipStream_t)stream)) return hip_fail(e, "points_lookup_grad");
     }
     return CNERF_OK;
@@ -1567,11 +1519,8 @@ int cnerf_dropout_keep(const cnerf_cfg* cfg, uint32_t stream_id, int64_t point0,
     if (int rc = check_cfg(cfg, false)) return rc;
     if (!mask || point0 < 0 || n_points < 1 || stream_id < PHILOX_DROP_COARSE || stream_id > PHILOX_DROP_POINTS || !(cfg->drop_p > 0.0f))
         return fail(CNERF_EINVAL, "dropout_keep: bad argument (drop_p > 0, stream 4..6)");
-    const double th = (double)cfg->drop_p * 4294967296.0 + 0.5;
-    const uint32_t thresh = th >= 4294967295.0 ? 0xffffffffu : (uint32_t)th;
-    int n_drop = 0;
-    for (int l = 0; l < cfg->L; ++l) n_drop += cfg->layer_kind[l] != CNERF_LAYER_RES;
-    if (hipError_t e = launch_drop_keep(philox_of(cfg), stream_id, thresh, n_drop, cfg->H, (unsigned long long)point0, (long long)n_points, mask,
+    const NetCounts nc = counts_of(cfg);
+    if (hipError_t e = launch_drop_keep(philox_of(cfg), stream_id, nc.drop_thresh, nc.n_drop, cfg->H, (unsigned long long)point0, (long long)n_points, mask,
                                         (hipStream_t)stream))
         return hip_fail(e, "drop_keep");
     return CNERF_OK;

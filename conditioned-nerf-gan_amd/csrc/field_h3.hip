@@ -46,13 +46,6 @@ namespace H3_NS {
 //   element j of lane (i = lane&31, h = lane>>5) = part_k( S * W[32t + i][16c + 8(j>>2) + 4h + (j&3)] )
 // S = 2^floor(log2(16384 / max|W|)) per matrix (on the device, no host round trip); 1/S goes to the kernel.
 // ---------------------------------------------------------------------------------------------------------------
-__global__ void absmax_kernel(const float* __restrict__ w, long long n, uint32_t* slot) {
-    float m = 0.0f;
-    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) m = fmaxf(m, fabsf(w[i]));
-#pragma unroll
-    for (int d = WAVE / 2; d >= 1; d >>= 1) m = fmaxf(m, __shfl_xor(m, d, WAVE));
-    if ((threadIdx.x & 63) == 0 && m == m) atomicMax(slot, __float_as_uint(m));     // non-negative floats order like their bits
-}
 
 __device__ __forceinline__ float pow2_scale(float wmax) {
     if (!(wmax > 1e-30f) || !(wmax < 3e38f)) return 1.0f;
@@ -90,10 +83,7 @@ __global__ void pack_h3_kernel(const float* __restrict__ w, int n_out, int K_rea
 static hipError_t pack_impl(const float* w, int n_out, int K_real, int OT, bool k_outer, void* dst, float* inv_scale_slot, float* wmax_slot,
                             hipStream_t stream, long long t_stride) {
     if (hipError_t e = hipMemsetAsync(wmax_slot, 0, sizeof(float), stream)) return e;
-    const long long n = (long long)n_out * K_real;
-    long long rb = (n + 255) / 256;
-    if (rb > 256) rb = 256;
-    hipLaunchKernelGGL(absmax_kernel, dim3((unsigned)rb), dim3(256), 0, stream, w, n, (uint32_t*)wmax_slot);
+    if (hipError_t e = launch_absmax_bits(w, (long long)n_out * K_real, (uint32_t*)wmax_slot, stream)) return e;
     const int KC = (K_real + 31) / 32 * 2;
     const long long total = (long long)OT * KC * 64 * 8;
     long long blocks = (total + 255) / 256;

@@ -2,6 +2,7 @@
 stream and autograd plumbing here; every computation below happens in libcnerf_hip.so."""
 import ctypes as C
 import weakref
+from types import SimpleNamespace
 from typing import Optional
 
 import torch
@@ -80,13 +81,8 @@ def make_cfg(net, B, vols, R=1, S=2, fov=30.0, ray_start=0.0, ray_end=1.0, noise
     cfg.ray_start, cfg.ray_end, cfg.voxel_length = float(ray_start), float(ray_end), 1.2
     cfg.noise_std = float(noise_std)
     cfg.fov_deg = float(fov)
-    if clamp_mode not in ("relu", "softplus"):
-        raise TypeError("Need to choose clamp mode")   # the reference raises a str here, i.e. a TypeError
-    flags = 0
+    flags = _ray_flags(clamp_mode, white_back, last_back)
     flags |= L.F_HIERARCHICAL if hierarchical else 0
-    flags |= L.F_WHITE_BACK if white_back else 0
-    flags |= L.F_LAST_BACK if last_back else 0
-    flags |= L.F_SOFTPLUS if clamp_mode == "softplus" else 0
     flags |= L.F_SIGMOID_RGB if net.spec.sigmoid_rgb else 0
     flags |= L.F_INPUT_XYZ if net.spec.input == "feat_xyz" else 0
     cfg.flags = flags
@@ -98,6 +94,13 @@ def make_cfg(net, B, vols, R=1, S=2, fov=30.0, ray_start=0.0, ray_end=1.0, noise
         if philox is None:            # the key of the keep decisions (the four draws stay tensors: cfg.philox = 0)
             cfg.philox_seed, cfg.philox_offset = int(drop[1][0]) & 0xFFFFFFFFFFFFFFFF, int(drop[1][1]) & 0xFFFFFFFF
     return cfg
+
+
+def _ray_flags(clamp_mode, white_back, last_back):
+    """cnerf_cfg.flags of the compositing: clamp mode, white / last background."""
+    if clamp_mode not in ("relu", "softplus"):
+        raise TypeError("Need to choose clamp mode")   # the reference raises a str here, i.e. a TypeError
+    return (L.F_WHITE_BACK if white_back else 0) | (L.F_LAST_BACK if last_back else 0) | (L.F_SOFTPLUS if clamp_mode == "softplus" else 0)
 
 
 def drop_of(rng):
@@ -116,10 +119,11 @@ def sizes(cfg, render=True):
     return a.value, b.value, c.value
 
 
-def _field_params_struct(net, params):
-    """cnerf_field_params from the flat tensor list of net.field_params() (mapping MLP first for the per-point family)."""
-    fp = L.FieldParams()
-    it = iter(params)
+def _params_struct(struct, net, tensors):
+    """cnerf_field_params (struct = L.FieldParams) or cnerf_field_param_grads (L.FieldParamGrads) over a flat tensor list in the order
+    of net.field_params() (mapping MLP first for the per-point family)."""
+    fp = struct()
+    it = iter(tensors)
     if net.spec.input == "xyz":
         fp.map_w1, fp.map_b1, fp.map_w2, fp.map_b2 = (next(it).data_ptr() for _ in range(4))
     for i, kind in enumerate(net.spec.layers):
@@ -139,7 +143,7 @@ def _cached_pack(net, cfg, layout, nbytes, entry, dtype):
         return hit[1]
     params = [_f32(p.detach()) for p in net.field_params()]
     buf = torch.empty(nbytes() // dtype.itemsize, dtype=dtype, device=params[0].device)
-    fp = _field_params_struct(net, params)
+    fp = _params_struct(L.FieldParams, net, params)
     L.check(getattr(L.lib(), entry)(C.byref(cfg), C.byref(fp), L.ptr(buf), _stream()), entry)
     buf._keepalive = params
     _pack_cache[net][layout] = (key, buf)
@@ -226,10 +230,7 @@ def composite(rgb_sigma, z, eps=None, noise_std=0.0, clamp_mode="relu", white_ba
     rays, n = z.shape
     cfg = L.Cfg()
     cfg.noise_std = float(noise_std)
-    if clamp_mode not in ("relu", "softplus"):
-        raise TypeError("Need to choose clamp mode")
-    cfg.flags = (L.F_WHITE_BACK if white_back else 0) | (L.F_LAST_BACK if last_back else 0) | \
-                (L.F_SOFTPLUS if clamp_mode == "softplus" else 0)
+    cfg.flags = _ray_flags(clamp_mode, white_back, last_back)
     dev = z.device
     rgb = torch.empty((rays, 3), dtype=torch.float32, device=dev)
     dist = torch.empty((rays,), dtype=torch.float32, device=dev)
@@ -258,6 +259,27 @@ def philox_fill(seed, offset, stream_id, n, normal, device):
     L.check(L.lib().cnerf_philox_fill(int(seed) & 0xFFFFFFFFFFFFFFFF, int(offset) & 0xFFFFFFFF, int(stream_id), int(n), 1 if normal else 0,
                                       L.ptr(out), _stream()), "cnerf_philox_fill")
     return out
+
+
+def _rng_struct(rng, keys):
+    """(cnerf_rng, the tensors behind it) of the draws `keys` in rng: float32, the injected dropout decisions (tests) uint8."""
+    r, keep = L.Rng(), []
+    for k in keys:
+        t = (_u8 if k.startswith("drop_") else _f32)(rng.get(k))
+        L.ptr(t)   # validates device / contiguity
+        setattr(r, k, None if t is None else t.data_ptr())
+        keep.append(t)
+    return r, keep
+
+
+def _act16_aux(act16, aux=None):
+    """`aux` (or a new cnerf_aux) carrying the fp16 activations of the field passes: one (feat, h, c[, amax]) set per pass."""
+    aux = aux if aux is not None else L.Aux()
+    for i, bufs in enumerate(act16):
+        aux.act16[i].feat, aux.act16[i].h, aux.act16[i].c = (t.data_ptr() for t in bufs[:3])
+        if len(bufs) > 3:
+            aux.act16[i].amax = bufs[3].data_ptr()
+    return aux
 
 
 AUX_SHAPES = {
@@ -295,14 +317,7 @@ def render_forward(net, fvol, freq, phase, cam2world, img_size, fov, ray_start, 
     ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
     pixels = torch.empty((B, 3, R, R), dtype=torch.float32, device=dev)
     depth = torch.empty((B, R, R), dtype=torch.float32, device=dev)
-    rng = rng or {}
-    keep = [_f32(rng.get(k)) for k in ("u_strat", "eps_coarse", "u_fine", "eps_final", "fine_z")]
-    r = L.Rng()
-    r.u_strat, r.eps_coarse, r.u_fine, r.eps_final, r.fine_z = [None if t is None else t.data_ptr() for t in keep]
-    keep += [_u8(rng.get(k)) for k in ("drop_coarse", "drop_fine")]       # injected dropout decisions (tests)
-    r.drop_coarse, r.drop_fine = [None if t is None else t.data_ptr() for t in keep[-2:]]
-    for t in keep:
-        L.ptr(t)   # validates device / contiguity
+    r, keep = _rng_struct(rng or {}, ("u_strat", "eps_coarse", "u_fine", "eps_final", "fine_z", "drop_coarse", "drop_fine"))
     aux_t, aux_s = {}, None
     if want_aux or aux_keys:
         aux_s = L.Aux()
@@ -317,11 +332,7 @@ def render_forward(net, fvol, freq, phase, cam2world, img_size, fov, ray_start, 
         for i, ev in enumerate(field_events):
             aux_s.field_events[i] = ev
     if act16 is not None:          # keep the field passes' activations (fp16 tile blocks) for the half-precision backward
-        aux_s = aux_s if aux_s is not None else L.Aux()
-        for i, bufs in enumerate(act16):
-            aux_s.act16[i].feat, aux_s.act16[i].h, aux_s.act16[i].c = (t.data_ptr() for t in bufs[:3])
-            if len(bufs) > 3:
-                aux_s.act16[i].amax = bufs[3].data_ptr()
+        aux_s = _act16_aux(act16, aux_s)
     L.check(L.lib().cnerf_render_forward(C.byref(cfg), C.byref(vs), L.ptr(packed), L.ptr(_f32(freq)), L.ptr(_f32(phase)),
                                          L.ptr(cam2world), C.byref(r), L.ptr(pixels), L.ptr(depth),
                                          C.byref(aux_s) if aux_s is not None else None, L.ptr(ws), _stream()),
@@ -340,7 +351,6 @@ def pack_field_transposed(net, cfg):
     return _cached_pack(net, cfg, "transposed", lambda: _abi_bytes("cnerf_backward_bytes", cfg), "cnerf_pack_field_transposed", torch.float32)
 
 
-DEBUG_CAPTURE = None            # set to a dict to capture the chunk buffers of the per-point FiLM backward (debugging)
 PHASE_TIMER = None              # an object with begin() / end(name, start) (training.gan_step.PhaseTimer): RenderFunction.backward
                                 # reports its span as "render_bwd" so that a caller can split an autograd pass (bench.py gan_step)
 ACT_BUDGET_BYTES = 128 << 30    # chunk buffers of the per-point FiLM backward: at most this much, and MEMORY_FRACTION of what is free
@@ -379,15 +389,12 @@ def _pfilm_backward(net, o, cfg, levels, cam2world, rng, saved, gc, gf, query=No
                    torch.empty((n, 4), dtype=torch.float32, device=dev))
         return act
 
-    def finish(key, b0, cnt, npi, pts, g_pts):
+    def finish(b0, cnt, npi, pts, g_pts):
         """The reductions of one chunk (cnt images of npi points from image b0, positions pts (cnt*npi, 3)) and, with g_pts, its position gradient."""
         n = cnt * npi
         a_feat, a_h, a_c, a_g, a_go = act
         y, m = a_h[:nl * n * H].view(nl, n, H), a_h[nl * n * H:].view(n, 256)
         gp, G = a_g[:nl * n * H].view(nl, n, H), a_g[nl * n * H:].view(n, 2 * nl * H)
-        if DEBUG_CAPTURE is not None:
-            DEBUG_CAPTURE.setdefault(key, dict(feat=a_feat.clone(), y=y.clone(), m=m.clone(), c=a_c.clone(), gp=gp.clone(),
-                                               G=G.clone(), go=a_go.clone(), pts=pts.clone()))
         grads[4] += gp[0].t() @ pts                                   # layer 0 reads the sample position: (H, 3)
         grads[5] += gp[0].sum(0)
         for l in range(1, nl):
@@ -436,7 +443,7 @@ def _pfilm_backward(net, o, cfg, levels, cam2world, rng, saved, gc, gf, query=No
                                                             L.ptr(g_all[b, p0:p0 + k]), L.ptr(s_all[b, p0:p0 + k]), L.ptr(a_feat), L.ptr(a_h),
                                                             L.ptr(a_c), L.ptr(a_g), L.ptr(a_go), C.byref(gvsb), L.ptr(mask), _stream()),
                         "cnerf_field_backward_points")
-                finish(("pfilm", "points"), b, 1, k, pts, g_pts[b, p0:p0 + k] if g_pts is not None else None)
+                finish(b, 1, k, pts, g_pts[b, p0:p0 + k] if g_pts is not None else None)
         return [g_level], None, None, grads
 
     B, R, S, hier = o["B"], o["R"], o["S"], o["hier"]
@@ -455,7 +462,7 @@ def _pfilm_backward(net, o, cfg, levels, cam2world, rng, saved, gc, gf, query=No
                                                  L.ptr(saved_out), L.ptr(a_feat), L.ptr(a_h), L.ptr(a_c), L.ptr(a_g), L.ptr(a_go),
                                                  C.byref(gvs), L.ptr(_u8(rng.get("drop_fine" if pss else "drop_coarse"))), _stream()),
                     "cnerf_field_backward")
-            finish(("pfilm", pss), b0, cnt, npi, pts_all[b0:b0 + cnt].reshape(cnt * npi, 3), None)
+            finish(b0, cnt, npi, pts_all[b0:b0 + cnt].reshape(cnt * npi, 3), None)
     return [g_level], None, None, grads
 
 
@@ -505,20 +512,6 @@ def resident_act16(net, levels, B, R, S, hier, dev):
             for _ in range(n_pass)]
 
 
-def _field_param_grads_struct(net, grads):
-    """cnerf_field_param_grads over the flat tensor list `grads` (same order as net.field_params(): mapping MLP first for the per-point family)."""
-    gp = L.FieldParamGrads()
-    it = iter(grads)
-    if net.spec.input == "xyz":
-        gp.map_w1, gp.map_b1, gp.map_w2, gp.map_b2 = (next(it).data_ptr() for _ in range(4))
-    for i, kind in enumerate(net.spec.layers):
-        gp.w[i], gp.b[i] = next(it).data_ptr(), next(it).data_ptr()
-        if kind == "res":
-            gp.w2[i], gp.b2[i] = next(it).data_ptr(), next(it).data_ptr()
-    gp.w_final, gp.b_final = next(it).data_ptr(), next(it).data_ptr()
-    return gp
-
-
 def free_device_bytes(dev):
     """What an allocation could get right now: the driver's free memory plus what torch's caching allocator holds unused."""
     free, _ = torch.cuda.mem_get_info(dev)
@@ -542,6 +535,25 @@ def backward_chunk(cfg, bprec_code, B, have_act16, dev):
 
 MEMORY_FRACTION = 0.8
 LAST_SATURATED = None          # device int32 tensor of the most recent fp16 backward: clamped (tile, matrix) blocks, see include/cnerf.h
+
+
+def _backward_setup(net, cfg, levels, B, dev):
+    """What render_backward and query_backward hand to the library besides their own inputs: the packed weights of the re-run (cfg's
+    precision) and of the gradient chain (fp16 units, or the transposed fp32 weights), the field parameters, zeroed gradients of the
+    parameters, of freq / phase (FiLM layers) and of the volume levels, their structs, and the fp16 backward's saturation counter."""
+    bprec = backward_precision_of(net)
+    packed = pack_field(net, cfg)
+    packed_bwd = pack_field_chain16(net, cfg) if bprec == "fp16" else pack_field_transposed(net, make_cfg(net, B, levels, precision="fp32"))
+    params = [_f32(p.detach()) for p in net.field_params()]
+    grads = [torch.zeros_like(p) for p in params]
+    n_film = sum(1 for k in net.spec.layers if k == "film")
+    g_freq = torch.zeros((B, n_film * int(net.hidden_dim)), dtype=torch.float32, device=dev) if n_film else None
+    grad_levels = [torch.zeros_like(v) for v in levels]
+    return SimpleNamespace(code=L.PREC_CODE[bprec], packed=packed, packed_bwd=packed_bwd, params=params, grads=grads,
+                           fp=_params_struct(L.FieldParams, net, params), gp=_params_struct(L.FieldParamGrads, net, grads),
+                           g_freq=g_freq, g_phase=torch.zeros_like(g_freq) if n_film else None, grad_levels=grad_levels,
+                           vs=volumes_struct(levels), gvs=volumes_struct(grad_levels),
+                           sat=torch.zeros(1, dtype=torch.int32, device=dev) if bprec == "fp16" else None)
 
 
 def render_backward(net, o, levels, freq, phase, cam2world, rng, saved, grad_pixels, grad_depth, act16=None):
@@ -570,50 +582,35 @@ def render_backward(net, o, levels, freq, phase, cam2world, rng, saved, grad_pix
                                                        L.ptr(grad_depth), L.ptr(gc), L.ptr(gf) if hier else None, _stream()),
                 "cnerf_merge_composite_backward")
         return _pfilm_backward(net, o, cfg, levels, cam2world, rng, saved, gc, gf)
-    packed = pack_field(net, cfg)
-    if bprec == "fp16":
-        packed_bwd = pack_field_chain16(net, cfg)
-    else:
-        cfg32 = make_cfg(net, B, levels, R, S, precision="fp32")
-        packed_bwd = pack_field_transposed(net, cfg32)
-    params = [_f32(p.detach()) for p in net.field_params()]
-    grads = [torch.zeros_like(p) for p in params]
-    fp, gp = _field_params_struct(net, params), _field_param_grads_struct(net, grads)
-    n_film = sum(1 for k in net.spec.layers if k == "film")
-    H = int(net.hidden_dim)
-    g_freq = torch.zeros((B, n_film * H), dtype=torch.float32, device=dev) if n_film else None
-    g_phase = torch.zeros_like(g_freq) if n_film else None
-    grad_levels = [torch.zeros_like(v) for v in levels]
-    vs, gvs = volumes_struct(levels), volumes_struct(grad_levels)
-    code = L.PREC_CODE[bprec]
-    nb, ws_bytes = backward_chunk(cfg, code, B, act16 is not None, dev)
+    w = _backward_setup(net, cfg, levels, B, dev)
+    nb, ws_bytes = backward_chunk(cfg, w.code, B, act16 is not None, dev)
     ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
-    sat = torch.zeros(1, dtype=torch.int32, device=dev)
-    keep = [_f32(rng.get(k)) for k in ("u_strat", "eps_final")] + [_u8(rng.get(k)) for k in ("drop_coarse", "drop_fine")]
-    r = L.Rng()
-    r.u_strat, r.eps_final, r.drop_coarse, r.drop_fine = [None if t is None else t.data_ptr() for t in keep]
-    for t in keep:
-        L.ptr(t)
+    r, keep = _rng_struct(rng, ("u_strat", "eps_final", "drop_coarse", "drop_fine"))
     sv = L.Saved()
     sv.coarse_rgb_sigma, sv.coarse_z = c_rs.data_ptr(), c_z.data_ptr()
     if hier:
         sv.fine_rgb_sigma, sv.fine_z = f_rs.data_ptr(), f_z.data_ptr()
     for t in (c_rs, c_z) + ((f_rs, f_z) if hier else ()):
         L.ptr(t)
-    aux = None
-    if act16 is not None:
-        aux = L.Aux()
-        for i, bufs in enumerate(act16):
-            aux.act16[i].feat, aux.act16[i].h, aux.act16[i].c = (t.data_ptr() for t in bufs[:3])
-            if len(bufs) > 3:
-                aux.act16[i].amax = bufs[3].data_ptr()
-    L.check(L.lib().cnerf_render_backward(C.byref(cfg), code, nb, C.byref(vs), C.byref(fp), L.ptr(packed), L.ptr(packed_bwd), L.ptr(freq), L.ptr(phase),
-                                          L.ptr(cam2world), C.byref(r), C.byref(sv), C.byref(aux) if aux is not None else None,
-                                          L.ptr(grad_pixels), L.ptr(grad_depth), C.byref(gp), L.ptr(g_freq), L.ptr(g_phase), C.byref(gvs),
-                                          L.ptr(sat) if bprec == "fp16" else None, L.ptr(ws), _stream()), "cnerf_render_backward")
-    if bprec == "fp16":
-        LAST_SATURATED = sat
-    return grad_levels, g_freq, g_phase, grads
+    aux = _act16_aux(act16) if act16 is not None else None
+    L.check(L.lib().cnerf_render_backward(C.byref(cfg), w.code, nb, C.byref(w.vs), C.byref(w.fp), L.ptr(w.packed), L.ptr(w.packed_bwd), L.ptr(freq),
+                                          L.ptr(phase), L.ptr(cam2world), C.byref(r), C.byref(sv), C.byref(aux) if aux is not None else None,
+                                          L.ptr(grad_pixels), L.ptr(grad_depth), C.byref(w.gp), L.ptr(w.g_freq), L.ptr(w.g_phase), C.byref(w.gvs),
+                                          L.ptr(w.sat), L.ptr(ws), _stream()), "cnerf_render_backward")
+    if w.sat is not None:
+        LAST_SATURATED = w.sat
+    return w.grad_levels, w.g_freq, w.g_phase, w.grads
+
+
+def _is_channel_last(levels, vols):
+    """Per volume: did it arrive channels_last_3d, so that channel_last() took it as it is (zero-copy)?"""
+    return [lv.data_ptr() == v.data_ptr() and not v.is_contiguous() for lv, v in zip(levels, vols)]
+
+
+def _caller_format(g_levels, vol_is_cl):
+    """Channel-last volume gradients in the memory format their volumes came in: a channels_last_3d volume gets a view, the others a
+    channel-first copy."""
+    return [g.permute(0, 4, 1, 2, 3) if cl else channel_first(g) for g, cl in zip(g_levels, vol_is_cl)]
 
 
 class RenderFunction(torch.autograd.Function):
@@ -625,8 +622,7 @@ class RenderFunction(torch.autograd.Function):
     def forward(ctx, net, o, rng, cam2world, freq, phase, n_vols, *rest):
         vols, params = rest[:n_vols], rest[n_vols:]
         levels = [channel_last(v.detach()) for v in vols]
-        # a volume that arrived channel-last (zero-copy above) gets its gradient back in the same memory format, again a view
-        ctx.vol_is_cl = [lv.data_ptr() == v.data_ptr() and not v.is_contiguous() for lv, v in zip(levels, vols)]
+        ctx.vol_is_cl = _is_channel_last(levels, vols)
         fr = freq.detach() if freq is not None else None
         ph = phase.detach() if phase is not None else None
         need_grad = o.get("need_grad", any(ctx.needs_input_grad))   # (decided by ops.render: grad mode is always off in here)
@@ -658,7 +654,7 @@ class RenderFunction(torch.autograd.Function):
                                                               grad_depth.contiguous() if grad_depth is not None else None,
                                                               act16=ctx.act16)
         ctx.act16 = None
-        g_vols = [g.permute(0, 4, 1, 2, 3) if cl else channel_first(g) for g, cl in zip(g_levels, ctx.vol_is_cl)]
+        g_vols = _caller_format(g_levels, ctx.vol_is_cl)
         if t0 is not None:
             PHASE_TIMER.end("render_bwd", t0)
         return (None, None, None, None, g_freq, g_phase, None, *g_vols, *g_params)
@@ -671,8 +667,7 @@ def render(net, fvol, freq, phase, cam2world, img_size, fov, ray_start, ray_end,
     o = dict(B=cam2world.shape[0], R=int(img_size), S=int(num_steps), fov=float(fov), ray_start=float(ray_start),
              ray_end=float(ray_end), hier=bool(hierarchical), clamp_mode=clamp_mode, noise_std=float(noise_std),
              white_back=bool(white_back), last_back=bool(last_back), want_aux=bool(want_aux), field_events=field_events)
-    if clamp_mode not in ("relu", "softplus"):
-        raise TypeError("Need to choose clamp mode")
+    _ray_flags(clamp_mode, white_back, last_back)      # refuses an unknown clamp mode before any work
     vols = as_levels(fvol)
     # Will anything back-propagate through this render?  Decided HERE: inside Function.forward grad mode is always off, and
     # ctx.needs_input_grad is True for every parameter even under torch.no_grad() -- the D step's no-grad renders then ran the
@@ -722,28 +717,16 @@ def query_backward(net, levels, freq, phase, points, out, grad_out, drop, want_p
                                                 query=dict(points=points, g_out=grad_out, saved_out=out, drop=drop, grad_points=g_pts))
         return g_levels, None, None, grads, g_pts
     cfg = make_cfg(net, B, levels, precision="fp16x3" if bprec == "fp16" else None, drop=drop)
-    packed = pack_field(net, cfg)
-    packed_bwd = pack_field_chain16(net, cfg) if bprec == "fp16" else pack_field_transposed(net, make_cfg(net, B, levels, precision="fp32"))
-    params = [_f32(p.detach()) for p in net.field_params()]
-    grads = [torch.zeros_like(p) for p in params]
-    fp, gp = _field_params_struct(net, params), _field_param_grads_struct(net, grads)
-    n_film = sum(1 for k in net.spec.layers if k == "film")
-    H = int(net.hidden_dim)
-    g_freq = torch.zeros((B, n_film * H), dtype=torch.float32, device=dev) if n_film else None
-    g_phase = torch.zeros_like(g_freq) if n_film else None
-    grad_levels = [torch.zeros_like(v) for v in levels]
-    vs, gvs = volumes_struct(levels), volumes_struct(grad_levels)
-    code = L.PREC_CODE[bprec]
-    ppc, ws_bytes = query_chunk(n, lambda k: query_workspace_bytes(cfg, code, k), dev)
+    w = _backward_setup(net, cfg, levels, B, dev)
+    ppc, ws_bytes = query_chunk(n, lambda k: query_workspace_bytes(cfg, w.code, k), dev)
     ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
-    sat = torch.zeros(1, dtype=torch.int32, device=dev)
-    L.check(L.lib().cnerf_field_query_backward(C.byref(cfg), code, ppc, C.byref(vs), C.byref(fp), L.ptr(packed), L.ptr(packed_bwd), L.ptr(freq),
-                                               L.ptr(phase), L.ptr(points), n, L.ptr(out), L.ptr(grad_out), C.byref(gp), L.ptr(g_freq), L.ptr(g_phase),
-                                               C.byref(gvs), L.ptr(g_pts), L.ptr(sat) if bprec == "fp16" else None, L.ptr(ws), _stream()),
+    L.check(L.lib().cnerf_field_query_backward(C.byref(cfg), w.code, ppc, C.byref(w.vs), C.byref(w.fp), L.ptr(w.packed), L.ptr(w.packed_bwd),
+                                               L.ptr(freq), L.ptr(phase), L.ptr(points), n, L.ptr(out), L.ptr(grad_out), C.byref(w.gp),
+                                               L.ptr(w.g_freq), L.ptr(w.g_phase), C.byref(w.gvs), L.ptr(g_pts), L.ptr(w.sat), L.ptr(ws), _stream()),
             "cnerf_field_query_backward")
-    if bprec == "fp16":
-        LAST_SATURATED = sat
-    return grad_levels, g_freq, g_phase, grads, g_pts
+    if w.sat is not None:
+        LAST_SATURATED = w.sat
+    return w.grad_levels, w.g_freq, w.g_phase, w.grads, g_pts
 
 
 class FieldQueryFunction(torch.autograd.Function):
@@ -755,9 +738,9 @@ class FieldQueryFunction(torch.autograd.Function):
     def forward(ctx, net, drop, vols_channel_last, freq, phase, points, n_vols, *rest):
         vols, params = rest[:n_vols], rest[n_vols:]
         levels = [_f32(v.detach()) for v in vols] if vols_channel_last else [channel_last(v.detach()) for v in vols]
-        # volumes given channel-last get channel-last gradients; a channels_last_3d volume (zero-copy above) gets a view in its format
+        # volumes given channel-last get channel-last gradients, the others their caller's format
         ctx.vols_channel_last = vols_channel_last
-        ctx.vol_is_cl = [lv.data_ptr() == v.data_ptr() and not v.is_contiguous() for lv, v in zip(levels, vols)]
+        ctx.vol_is_cl = _is_channel_last(levels, vols)
         fr = _f32(freq.detach()) if freq is not None else None
         ph = _f32(phase.detach()) if phase is not None else None
         pts = _f32(points.detach())
@@ -773,8 +756,5 @@ class FieldQueryFunction(torch.autograd.Function):
         out, = ctx.saved_tensors
         g_levels, g_freq, g_phase, g_params, g_pts = query_backward(ctx.net, levels, fr, ph, pts, out, _f32(grad_out), ctx.drop,
                                                                     want_points=ctx.needs_input_grad[5])
-        if ctx.vols_channel_last:
-            g_vols = g_levels
-        else:
-            g_vols = [g.permute(0, 4, 1, 2, 3) if cl else channel_first(g) for g, cl in zip(g_levels, ctx.vol_is_cl)]
+        g_vols = g_levels if ctx.vols_channel_last else _caller_format(g_levels, ctx.vol_is_cl)
         return (None, None, None, g_freq, g_phase, g_pts, None, *g_vols, *g_params)

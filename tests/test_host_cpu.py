@@ -175,3 +175,37 @@ def test_backward_workspace_validation_without_gpu():
     for l in range(4):
         cfg.layer_kind[l] = L.LAYER_PFILM
     assert L.lib().cnerf_backward_workspace_bytes(ctypes.byref(cfg), L.PREC_FP32, 1, 0, ctypes.byref(n)) == -38
+
+
+@pytest.mark.parametrize("kinds,precision,missing", [(("film",) * 4, "fp32", "w_final"), (("film",) * 4, "fp16", "w_final"),
+                                                     (("film",) * 4, "fp16x3", "w_final"), (("film", "res", "sine", "res"), "fp32", "w2")])
+def test_pack_field_checks_every_parameter_before_the_first_launch(kinds, precision, missing):
+    """cnerf_pack_field refuses a parameter set with a NULL late in the walk (the head, the last residual block's fc2) before it queues
+    any packing: without a GPU every launch would fail with CNERF_ELAUNCH, so CNERF_EINVAL proves that nothing was launched."""
+    import cnerf_amd
+    L = cnerf_amd._lib
+    cfg = L.Cfg()
+    cfg.B, cfg.V, cfg.C, cfg.H, cfg.L = 1, 8, 32, 64, len(kinds)
+    for i, k in enumerate(kinds):
+        cfg.layer_kind[i] = L.LAYER_CODE[k]
+    cfg.voxel_length, cfg.precision = 1.2, L.PREC_CODE[precision]
+    nbytes = ctypes.c_size_t()
+    assert L.lib().cnerf_workspace_bytes(ctypes.byref(cfg), ctypes.byref(nbytes), None, None) == 0
+    # never dereferenced; on a machine with a GPU they are real device buffers all the same, large enough for every read and write
+    if torch.cuda.is_available():
+        keep = (torch.zeros(64 * 64, device="cuda"), torch.empty(nbytes.value, dtype=torch.uint8, device="cuda"))
+        src, dst = keep[0].data_ptr(), keep[1].data_ptr()
+    else:
+        src, dst = 0x10000, 0x20000
+    fp = L.FieldParams()
+    for i, k in enumerate(kinds):
+        fp.w[i] = fp.b[i] = src
+        if k == "res":
+            fp.w2[i] = fp.b2[i] = src
+    fp.w_final = fp.b_final = src
+    if missing == "w2":
+        fp.w2[len(kinds) - 1] = None
+    else:
+        setattr(fp, missing, None)
+    assert L.lib().cnerf_pack_field(ctypes.byref(cfg), ctypes.byref(fp), dst, None) == -22
+    assert b"NULL" in L.lib().cnerf_last_error()
