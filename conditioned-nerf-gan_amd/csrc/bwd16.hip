@@ -164,9 +164,7 @@ hipError_t launch_weight_grad16(int cnt, long long tiles_per_image, int n_rows, 
     if (cnt < 1 || tiles_per_image < 1 || n_rows < 1 || g_ct < 1 || x_ct < 1 || x_ct > 8 || n_rows > 32 * g_ct) return hipErrorInvalidValue;
     const int noc = (n_rows + 31) / 32;
     if (noc != 1 && noc != 2 && noc != 4 && noc != 8) return hipErrorInvalidValue;
-    int dev = 0, cus = 256;
-    if (hipGetDevice(&dev) != hipSuccess) dev = 0;
-    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) cus = 256;
+    const int cus = cu_count();
     // blocks per image: one block per CU where a block is 8 waves (H = 256); narrow outputs (the head: one wave per block, 36 KiB of
     // LDS) get several blocks per CU -- with 256 single-wave blocks the head's reduction read its 4.3 GB at 2 TB/s
     const int per_cu = noc >= 4 ? 1 : (noc == 2 ? 2 : 4);
@@ -224,9 +222,8 @@ hipError_t launch_weight_grad16(int cnt, long long tiles_per_image, int n_rows, 
 // so  g_h of that slab = W1^T gp_fc1 + ga_fc2.  ga_fc2 = gp_fc2 is exactly the B operand fc2's epilogue produced (fp16, times
 // that slab's per-point scale T): a copy of those 16 fragments stays in registers across the two products and is added, re-scaled,
 // to the accumulators in the epilogue two slabs further down; the operand bound of that slab grows by the point's max |ga_fc2|.
-// Weight units (two 32-row output tiles of a transposed matrix: 2 * KCH KiB) stream through a three-slot ring in LDS by
-// LDS-DMA, shared by the block's four waves, which work on four tiles of one image in lockstep (one barrier per unit) -- the
-// scheme of field_h3.hip.  cos(arg) is fetched a slab's worth of output tiles ahead of the epilogue that consumes it.
+// Weight units (two 32-row output tiles of a transposed matrix: 2 * KCH KiB) stream through a three-slot LDS ring (the weight-unit
+// ring: bwd16.hpp).  cos(arg) is fetched a slab's worth of output tiles ahead of the epilogue that consumes it.
 constexpr int C16_MAX_SLABS = 2 * CNERF_MAX_LAYERS;
 enum { C16_FILM = 0, C16_SINE = 1, C16_RES_FC1 = 2, C16_RES_FC2 = 3 };
 struct Chain16Args {
@@ -245,13 +242,6 @@ struct Chain16Args {
     unsigned char slab_kind[C16_MAX_SLABS];   // per slab: C16_FILM / C16_SINE / C16_RES_FC1 / C16_RES_FC2
 };
 
-__device__ __forceinline__ float pow2_scale_to_2p14(float bound) {
-    // T = 2^(14 - e) with bound = m 2^e, m in [0.5, 1): bound * T in [2^13, 2^14).  bound == 0 (or denormal / huge) -> 1.
-    const int e = (int)((__float_as_uint(bound) >> 23) & 255u) - 126;
-    const int te = 127 + 14 - e;
-    return (bound >= 1e-30f && te > 0 && te < 255) ? __uint_as_float((uint32_t)te << 23) : 1.0f;
-}
-
 // per-tile state of the pipelined epilogue
 struct Epi16 {
     float US, UT;             // accumulator -> stored scale (U * S_m) and -> operand scale (U * T)
@@ -266,9 +256,6 @@ struct Epi16 {
     float kskip;              // HAS_RES: identity-path fragments (x T_skip) -> accumulator units; 0: this slab has no identity input
 };
 
-__device__ __forceinline__ float h16_lo(uint32_t u) { return (float)__builtin_bit_cast(_Float16, (unsigned short)(u & 0xffffu)); }
-__device__ __forceinline__ float h16_hi(uint32_t u) { return (float)__builtin_bit_cast(_Float16, (unsigned short)(u >> 16)); }
-
 // one element r of output tile t: acc -> (store, operand fragment)
 template <bool DRY, bool HAS_RES>
 __device__ __forceinline__ void epi16_element(const f32x16& acc, const f16x4* cosq, int t, int h, int r, Epi16& st, u32x4* frag_out,
@@ -277,7 +264,7 @@ __device__ __forceinline__ void epi16_element(const f32x16& acc, const f16x4* co
     float av = acc[r];
     if (HAS_RES && st.kskip != 0.0f) {       // (wave-uniform) + the identity path of the residual block above
         const uint32_t w = frag_skip[2 * t + (r >> 3)][(r & 7) >> 1];
-        av = __builtin_fmaf((r & 1) ? h16_hi(w) : h16_lo(w), st.kskip, av);
+        av = __builtin_fmaf((r & 1) ? half_hi(w) : half_lo(w), st.kskip, av);
     }
     const float ac = av * (float)cosq[gq][e];
     const float gs = ac * st.US;                                             // ga * S_m
@@ -320,6 +307,7 @@ __global__ __launch_bounds__(256) void chain16_kernel(Chain16Args A) {
 
     const long long G = (a.tiles_per_image + 3) / 4;
     const long long total_groups = (a.total_tiles / a.tiles_per_image) * G;
+    // group_range() (field_common.hpp) written out: through the function the compiler orders this kernel's scalar prologue differently
     const int nblk = gridDim.x;
     const int cls = blockIdx.x & 7, idx_in_cls = blockIdx.x >> 3;
     const int blk_per_cls = (nblk + 7 - cls) / 8;
@@ -333,12 +321,7 @@ __global__ __launch_bounds__(256) void chain16_kernel(Chain16Args A) {
     // units' worth of MFMAs to land.
     int dma_k = 0, dma_slot = 0, use_slot = 0;
     auto dma_next = [&]() {
-        const f16x8* src = A.units + (size_t)dma_k * UNIT_FR + (size_t)wave_u * PW * 64 + lane;
-        f16x8* dst = lds_units + dma_slot * UNIT_FR + wave_u * PW * 64;
-#pragma unroll
-        for (int q = 0; q < PW; ++q)
-            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(src + q * 64),
-                                             (__attribute__((address_space(3))) void*)(dst + q * 64), 16, 0, 0);
+        dma_unit_ptr<2 * KCH>(A.units + (size_t)dma_k * UNIT_FR, lds_units + dma_slot * UNIT_FR, wave_u, lane);
         dma_k = dma_k + 1 == n_units ? 0 : dma_k + 1;
         dma_slot = dma_slot == 2 ? 0 : dma_slot + 1;
     };
@@ -453,7 +436,7 @@ __global__ __launch_bounds__(256) void chain16_kernel(Chain16Args A) {
             const bool film = A.slab_kind[m] == C16_FILM;
             if (film) --film_idx;
             st.fr = film ? lds_freq + (size_t)film_idx * (NT * 32) : nullptr;
-            const float T = pow2_scale_to_2p14(bound_gp);
+            const float T = pow2_to_2p14(bound_gp);
             st.US = U * A.scales[2 * m];
             st.UT = U * T;
             st.gdst = A.g16 + (size_t)m * slab16 + row16 + 4 * h;
@@ -648,13 +631,7 @@ __global__ __launch_bounds__(256) void chain16_kernel(Chain16Args A) {
 __global__ void pack_t16_kernel(const float* __restrict__ w, int n_rows_w, int n_cols_w, int n_cols_real, int OT, int KCH, const uint32_t* wmax_slot,
                                 float* winv_slot, _Float16* __restrict__ dst) {
     // w: (n_rows_w, n_cols_w) row-major = W; M[r][k] = W[k][r], r < n_cols_real (else 0), k < n_rows_w (= 16 * KCH)
-    const float wmax = __uint_as_float(*wmax_slot);
-    float s = 1.0f;
-    if (wmax > 1e-30f && wmax < 3e38f) {
-        int e;
-        (void)frexpf(16384.0f / wmax, &e);
-        s = ldexpf(1.0f, e - 1 > 100 ? 100 : e - 1);
-    }
+    const float s = pow2_weight_scale(__uint_as_float(*wmax_slot));
     if (blockIdx.x == 0 && threadIdx.x == 0) *winv_slot = 1.0f / s;
     const long long total = (long long)OT * KCH * 64 * 8;
     for (long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += (long long)gridDim.x * blockDim.x) {
@@ -670,13 +647,7 @@ __global__ void pack_t16_kernel(const float* __restrict__ w, int n_rows_w, int n
 
 // head^T: fragment (t * 64 + lane), element jj = s * W_head[k = 8 hh + jj][32 t + i] for k < 4, else 0
 __global__ void pack_head_t16_kernel(const float* __restrict__ w, int H, const uint32_t* wmax_slot, float* winv_slot, _Float16* __restrict__ dst) {
-    const float wmax = __uint_as_float(*wmax_slot);
-    float s = 1.0f;
-    if (wmax > 1e-30f && wmax < 3e38f) {
-        int e;
-        (void)frexpf(16384.0f / wmax, &e);
-        s = ldexpf(1.0f, e - 1 > 100 ? 100 : e - 1);
-    }
+    const float s = pow2_weight_scale(__uint_as_float(*wmax_slot));
     if (blockIdx.x == 0 && threadIdx.x == 0) *winv_slot = 1.0f / s;
     const int total = (H / 32) * 64 * 8;
     for (int idx = blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += gridDim.x * blockDim.x) {
@@ -773,19 +744,10 @@ static hipError_t launch_chain16_nt(const FieldArgs& f, const Chain16Launch& c, 
     A.nslab = c.nslab;
     A.group_step = c.group_step < 1 ? 1 : c.group_step;
     if (!slab_kinds_of(f, A.slab_kind, c.nslab)) return hipErrorInvalidValue;
-    int dev = 0, cus = 256;
-    if (hipGetDevice(&dev) != hipSuccess) dev = 0;
-    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) cus = 256;
     const size_t lds_bytes = (size_t)3 * (2 * 2 * NT * 64) * 16 + (size_t)NT * 64 * 16 + (size_t)(f.film_stride > 0 ? f.film_stride : 4) * 4 +
                              (size_t)C16_MAX_SLABS * 4 + (size_t)4 * 32 * 33 * 4 + (size_t)2 * 4 * 32 * 8 * 4;
-    if (lds_bytes > 160 * 1024) return hipErrorInvalidValue;
-    if (hipError_t e = hipFuncSetAttribute((const void*)chain16_kernel<NT, DRY, HAS_RES>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes)) return e;
-    const long long want = (f.total_tiles / f.tiles_per_image) * ((f.tiles_per_image + 3) / 4);
-    int blocks = (int)(want < cus ? want : cus);
-    if (blocks < 8) blocks = 8;
-    blocks = (blocks + 7) / 8 * 8;
-    hipLaunchKernelGGL((chain16_kernel<NT, DRY, HAS_RES>), dim3(blocks), dim3(256), lds_bytes, stream, A);
-    return hipGetLastError();
+    if (lds_bytes > LDS_LIMIT) return hipErrorInvalidValue;
+    return launch_per_cu(chain16_kernel<NT, DRY, HAS_RES>, f, lds_bytes, lds_bytes, A, stream);
 }
 
 hipError_t launch_chain16(const FieldArgs& f, int H, const void* units, const void* head_t, const float* winv, const float* scales, const void* cos16,
@@ -793,17 +755,11 @@ hipError_t launch_chain16(const FieldArgs& f, int H, const void* units, const vo
     const Chain16Launch c{units, head_t, winv, scales, cos16, g16, go16, gmax, sat, nslab, dry, group_step};
     bool res = false;
     for (int l = 0; l < f.L; ++l) res |= f.layer_kind[l] == CNERF_LAYER_RES;
-#define C16_CASE(NT_)                                                                                                                   \
-    case NT_:                                                                                                                           \
-        if (res) return dry ? launch_chain16_nt<NT_, true, true>(f, c, stream) : launch_chain16_nt<NT_, false, true>(f, c, stream);     \
-        return dry ? launch_chain16_nt<NT_, true, false>(f, c, stream) : launch_chain16_nt<NT_, false, false>(f, c, stream);
-    switch (H / 32) {
-        C16_CASE(2)
-        C16_CASE(4)
-        C16_CASE(8)
-        default: return hipErrorInvalidValue;
-    }
-#undef C16_CASE
+    return dispatch_nt(H, [&](auto nt) {
+        constexpr int NT = decltype(nt)::value;
+        if (res) return dry ? launch_chain16_nt<NT, true, true>(f, c, stream) : launch_chain16_nt<NT, false, true>(f, c, stream);
+        return dry ? launch_chain16_nt<NT, true, false>(f, c, stream) : launch_chain16_nt<NT, false, false>(f, c, stream);
+    });
 }
 
 }  // namespace cnerf

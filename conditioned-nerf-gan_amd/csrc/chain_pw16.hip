@@ -12,8 +12,8 @@
 //
 // Two kernels, each within the register file.  (The first version did all of it in one: 128 resident accumulators of g_m next to two
 // operand arrays, three derivative rows two tiles ahead and the epilogue's three stored quads -- 195 spilled dwords at H = 256, 64 GB of
-// scratch traffic per launch, 31 ms; commit 9b8cfcc has it.)  One wave per 32-point tile, accumulator registers converted pairwise are the
-// next B operands (channel = k) as in the forward kernels, weight units through a three-slot LDS ring by LDS-DMA, counted vmcnt waits.
+// scratch traffic per launch, 31 ms; commit 9b8cfcc has it.)  Accumulator registers converted pairwise are the next B operands (channel
+// = k) as in the forward kernels; weight units through a three-slot LDS ring (the weight-unit ring: bwd16.hpp).
 #include "bwd16.hpp"
 #include "cnerf_dev.hpp"
 #include "cnerf_kernels.hpp"
@@ -21,23 +21,6 @@
 
 namespace cnerf {
 namespace pwchain {
-
-__device__ __forceinline__ float pow2_to_2p14(float bound) {     // T = 2^(14 - e), bound = m 2^e, m in [0.5, 1); 0 / denormal / huge -> 1
-    const int e = (int)((__float_as_uint(bound) >> 23) & 255u) - 126;
-    const int te = 127 + 14 - e;
-    return (bound >= 1e-30f && te > 0 && te < 255) ? __uint_as_float((uint32_t)te << 23) : 1.0f;
-}
-
-template <int PIECES>
-__device__ __forceinline__ void dma_pieces(const f16x8* __restrict__ src, f16x8* lds_dst, int wave_u, int lane) {
-    constexpr int PW = PIECES / 4;
-    const f16x8* s0 = src + (size_t)wave_u * PW * 64 + lane;
-    f16x8* d0 = lds_dst + wave_u * PW * 64;
-#pragma unroll
-    for (int q = 0; q < PW; ++q)
-        __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(s0 + q * 64), (__attribute__((address_space(3))) void*)(d0 + q * 64), 16,
-                                         0, 0);
-}
 
 struct RescaleYes { static constexpr bool value = true; };
 struct RescaleNo { static constexpr bool value = false; };
@@ -84,17 +67,14 @@ __global__ __launch_bounds__(256) void chain_pre_kernel(PreArgs A) {
     const int j = lane & 31, h = lane >> 5;
     const long long G = (a.tiles_per_image + 3) / 4;
     const long long total_groups = (a.total_tiles / a.tiles_per_image) * G;
-    const int nblk = gridDim.x;
-    const int cls = blockIdx.x & 7, idx_in_cls = blockIdx.x >> 3;
-    const int blk_per_cls = (nblk + 7 - cls) / 8;
-    const long long g_begin = total_groups * cls / 8 + (long long)idx_in_cls * A.group_step, g_end = total_groups * (cls + 1) / 8;
-    const long long g_stride = (long long)blk_per_cls * A.group_step;
-    if (g_begin >= g_end) return;
+    const GroupRange gr = group_range(total_groups, gridDim.x, blockIdx.x, A.group_step);
+    const long long g_stride = (long long)gr.blk_per_cls * A.group_step;
+    if (gr.begin >= gr.end) return;
     const int n_units = (L - 1) * NT;                   // 0 for a one-layer network: no unit is ever requested
     int dma_k = 0, dma_slot = 0, use_slot = 0;
     auto dma_next = [&]() {
         if (n_units == 0) return;
-        dma_pieces<KCH>(A.units + (size_t)dma_k * SLOT_FR, lds_units + dma_slot * SLOT_FR, wave_u, lane);
+        dma_unit_ptr<KCH>(A.units + (size_t)dma_k * SLOT_FR, lds_units + dma_slot * SLOT_FR, wave_u, lane);
         dma_k = dma_k + 1 == n_units ? 0 : dma_k + 1;
         dma_slot = dma_slot == SLOTS - 1 ? 0 : dma_slot + 1;
     };
@@ -116,7 +96,7 @@ __global__ __launch_bounds__(256) void chain_pre_kernel(PreArgs A) {
     const float winv_head = A.winv[2 * L + 1];
     const float S_go = A.scales[2 * (3 * L + 1)];
 
-    for (long long g = g_begin; g < g_end; g += g_stride) {
+    for (long long g = gr.begin; g < gr.end; g += g_stride) {
         const int b = (int)(g / G);
         const long long tile_in_image = (g - (long long)b * G) * 4 + wave;
         const bool live = tile_in_image < a.tiles_per_image;
@@ -286,18 +266,15 @@ __global__ __launch_bounds__(256) void pw_gm_kernel(GmArgs A) {
     const int j = lane & 31, h = lane >> 5;
     const long long G = (a.tiles_per_image + 3) / 4;
     const long long total_groups = (a.total_tiles / a.tiles_per_image) * G;
-    const int nblk = gridDim.x;
-    const int cls = blockIdx.x & 7, idx_in_cls = blockIdx.x >> 3;
-    const int blk_per_cls = (nblk + 7 - cls) / 8;
-    const long long g_begin = total_groups * cls / 8 + (long long)idx_in_cls * A.group_step, g_end = total_groups * (cls + 1) / 8;
-    const long long g_stride = (long long)blk_per_cls * A.group_step;
-    if (g_begin >= g_end) return;
+    const GroupRange gr = group_range(total_groups, gridDim.x, blockIdx.x, A.group_step);
+    const long long g_stride = (long long)gr.blk_per_cls * A.group_step;
+    if (gr.begin >= gr.end) return;
     const int n_units = L * NT + 1;
     int dma_k = 0, dma_slot = 0, use_slot = 0;
     auto dma_next = [&]() {
         f16x8* dst = lds_units + dma_slot * SLOT_FR;
-        if (dma_k == n_units - 1) dma_pieces<16>(A.units + (size_t)dma_k * SLOT_FR, dst, wave_u, lane);
-        else dma_pieces<32>(A.units + (size_t)dma_k * SLOT_FR, dst, wave_u, lane);
+        if (dma_k == n_units - 1) dma_unit_ptr<16>(A.units + (size_t)dma_k * SLOT_FR, dst, wave_u, lane);
+        else dma_unit_ptr<32>(A.units + (size_t)dma_k * SLOT_FR, dst, wave_u, lane);
         dma_k = dma_k + 1 == n_units ? 0 : dma_k + 1;
         dma_slot = dma_slot == SLOTS - 1 ? 0 : dma_slot + 1;
     };
@@ -316,7 +293,7 @@ __global__ __launch_bounds__(256) void pw_gm_kernel(GmArgs A) {
     const float* winvM = A.winv + L;
     const float winvW1 = A.winv[2 * L];
 
-    for (long long g = g_begin; g < g_end; g += g_stride) {
+    for (long long g = gr.begin; g < gr.end; g += g_stride) {
         const int b = (int)(g / G);
         const long long tile_in_image = (g - (long long)b * G) * 4 + wave;
         const bool live = tile_in_image < a.tiles_per_image;
@@ -551,17 +528,9 @@ __global__ void pw_split_scales_kernel(const uint32_t* amaxg_bits, int L, float*
 // packing.  Element jj of lane (i = lane & 31, hh = lane >> 5) of a fragment = s * (transposed weight)[row 32 t' + i][k], k in the order
 // in which accumulator registers become B operands: 16 c + 8 (jj >> 2) + 4 hh + (jj & 3) (bwd16.hip).
 // ---------------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ float pow2_weight_scale(uint32_t wmax_bits) {
-    const float wmax = __uint_as_float(wmax_bits);
-    if (!(wmax > 1e-30f) || !(wmax < 3e38f)) return 1.0f;
-    int e;
-    (void)frexpf(16384.0f / wmax, &e);
-    return ldexpf(1.0f, e - 1 > 100 ? 100 : e - 1);
-}
-
 // Y(l, t) for all t: rows [32 t, 32 t + 32) of W_l^T (W_l row-major (H, H)), KCH k-chunks
 __global__ void pack_y_kernel(const float* __restrict__ w, int H, int NT, const uint32_t* wmax_slot, float* winv_slot, _Float16* __restrict__ stage_dst) {
-    const float s = pow2_weight_scale(*wmax_slot);
+    const float s = pow2_weight_scale(__uint_as_float(*wmax_slot));
     if (blockIdx.x == 0 && threadIdx.x == 0) *winv_slot = 1.0f / s;
     const int KCH = 2 * NT;
     const long long total = (long long)NT * KCH * 512;
@@ -577,7 +546,7 @@ __global__ void pack_y_kernel(const float* __restrict__ w, int H, int NT, const 
 // 32 ot + i of the 256 inputs of the mapping network's second Linear (Wm2 row-major (2 L H, 256))
 __global__ void pack_m_kernel(const float* __restrict__ wm2, int H, int NT, int row_f, int row_p, const uint32_t* wmax_slot, float* winv_slot,
                               _Float16* __restrict__ stage_dst) {
-    const float s = pow2_weight_scale(*wmax_slot);
+    const float s = pow2_weight_scale(__uint_as_float(*wmax_slot));
     if (blockIdx.x == 0 && threadIdx.x == 0) *winv_slot = 1.0f / s;
     const long long total = (long long)NT * 32 * 512;
     for (long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += (long long)gridDim.x * blockDim.x) {
@@ -592,34 +561,14 @@ __global__ void pack_m_kernel(const float* __restrict__ wm2, int H, int NT, int 
 
 template <int NT, bool DRY>
 static hipError_t launch_pre_nt(const PreArgs& A, hipStream_t stream) {
-    int dev = 0, cus = 256;
-    if (hipGetDevice(&dev) != hipSuccess) dev = 0;
-    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) cus = 256;
     const size_t lds_bytes = (size_t)3 * 2 * NT * 1024 + (size_t)NT * 1024;
-    if (hipError_t e = hipFuncSetAttribute((const void*)chain_pre_kernel<NT, DRY>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes)) return e;
-    const FieldArgs& f = A.f;
-    const long long want = (f.total_tiles / f.tiles_per_image) * ((f.tiles_per_image + 3) / 4);
-    int blocks = (int)(want < cus ? want : cus);
-    if (blocks < 8) blocks = 8;
-    blocks = (blocks + 7) / 8 * 8;
-    hipLaunchKernelGGL((chain_pre_kernel<NT, DRY>), dim3(blocks), dim3(256), lds_bytes, stream, A);
-    return hipGetLastError();
+    return launch_per_cu(chain_pre_kernel<NT, DRY>, A.f, lds_bytes, lds_bytes, A, stream);
 }
 
 template <int NT, bool DRY>
 static hipError_t launch_gm_nt(const GmArgs& A, hipStream_t stream) {
-    int dev = 0, cus = 256;
-    if (hipGetDevice(&dev) != hipSuccess) dev = 0;
-    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) cus = 256;
     const size_t lds_bytes = (size_t)3 * 32 * 1024 + (size_t)4 * 6400;
-    if (hipError_t e = hipFuncSetAttribute((const void*)pw_gm_kernel<NT, DRY>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes)) return e;
-    const FieldArgs& f = A.f;
-    const long long want = (f.total_tiles / f.tiles_per_image) * ((f.tiles_per_image + 3) / 4);
-    int blocks = (int)(want < cus ? want : cus);
-    if (blocks < 8) blocks = 8;
-    blocks = (blocks + 7) / 8 * 8;
-    hipLaunchKernelGGL((pw_gm_kernel<NT, DRY>), dim3(blocks), dim3(256), lds_bytes, stream, A);
-    return hipGetLastError();
+    return launch_per_cu(pw_gm_kernel<NT, DRY>, A.f, lds_bytes, lds_bytes, A, stream);
 }
 
 }  // namespace pwchain
@@ -640,12 +589,10 @@ hipError_t launch_chain_pre(const FieldArgs& f, int H, const PwChainBuffers& c, 
     A.gmax = c.gmax;
     A.sat = c.sat;
     A.group_step = group_step < 1 ? 1 : group_step;
-    switch (H / 32) {
-        case 2: return dry ? pwchain::launch_pre_nt<2, true>(A, stream) : pwchain::launch_pre_nt<2, false>(A, stream);
-        case 4: return dry ? pwchain::launch_pre_nt<4, true>(A, stream) : pwchain::launch_pre_nt<4, false>(A, stream);
-        case 8: return dry ? pwchain::launch_pre_nt<8, true>(A, stream) : pwchain::launch_pre_nt<8, false>(A, stream);
-        default: return hipErrorInvalidValue;
-    }
+    return dispatch_nt(H, [&](auto nt) {
+        constexpr int NT = decltype(nt)::value;
+        return dry ? pwchain::launch_pre_nt<NT, true>(A, stream) : pwchain::launch_pre_nt<NT, false>(A, stream);
+    });
 }
 
 hipError_t launch_pw_gm(const FieldArgs& f, int H, const PwChainBuffers& c, int dry, int group_step, hipStream_t stream) {
@@ -662,12 +609,10 @@ hipError_t launch_pw_gm(const FieldArgs& f, int H, const PwChainBuffers& c, int 
     A.gmax = c.gmax;
     A.sat = c.sat;
     A.group_step = group_step < 1 ? 1 : group_step;
-    switch (H / 32) {
-        case 2: return dry ? pwchain::launch_gm_nt<2, true>(A, stream) : pwchain::launch_gm_nt<2, false>(A, stream);
-        case 4: return dry ? pwchain::launch_gm_nt<4, true>(A, stream) : pwchain::launch_gm_nt<4, false>(A, stream);
-        case 8: return dry ? pwchain::launch_gm_nt<8, true>(A, stream) : pwchain::launch_gm_nt<8, false>(A, stream);
-        default: return hipErrorInvalidValue;
-    }
+    return dispatch_nt(H, [&](auto nt) {
+        constexpr int NT = decltype(nt)::value;
+        return dry ? pwchain::launch_gm_nt<NT, true>(A, stream) : pwchain::launch_gm_nt<NT, false>(A, stream);
+    });
 }
 
 hipError_t launch_pw_split_scales(const uint32_t* amaxg_bits, int L, float* scales, float* lay, hipStream_t stream) {

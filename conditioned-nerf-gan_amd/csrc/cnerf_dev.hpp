@@ -296,6 +296,8 @@ __device__ __forceinline__ void trilinear_corners(float px, float py, float pz, 
 // the caller states what it needs to have completed: wait_vmcnt<N>() with N = the number of vector-memory operations it has issued
 // SINCE the LDS-DMA copy it is about to read (vmcnt retires in issue order; those N may stay in flight), and nothing for its LDS
 // reads of the slot that is refilled next -- their data has already been consumed by issued MFMAs.
+// Precondition: it waits on no lgkmcnt either, so data written with plain LDS stores (ds_write: constants, the head's fragments) is
+// NOT published by it -- only LDS-DMA data behind the caller's wait_vmcnt is.  Callers publish plain stores with __syncthreads().
 __device__ __forceinline__ void lds_only_barrier() {
     asm volatile("" ::: "memory");
     __builtin_amdgcn_s_barrier();

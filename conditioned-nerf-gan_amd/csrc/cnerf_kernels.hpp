@@ -3,6 +3,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <type_traits>
+
 #include "../../include/cnerf.h"
 #include "cnerf_dev.hpp"
 
@@ -77,6 +79,46 @@ struct FieldArgs {
     const float* packed_img; // WFOLD: per image, the layer part of the packed weights with rows scaled by Mh (scale_packed_kernel), or null
     long long packed_img_stride;
 };
+
+// ---- host side of the kernels that run one block of four waves per CU (the fp16 kernels: 512 registers per wave) ----------------
+constexpr size_t LDS_LIMIT = 160 * 1024;         // LDS of a CU: the most a block can ask for
+
+inline int cu_count() {
+    int dev = 0, cus = 256;
+    if (hipGetDevice(&dev) != hipSuccess) dev = 0;
+    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) cus = 256;
+    return cus;
+}
+
+// blocks for the groups of 4 tiles of one image: at most one per CU, a multiple of 8 (every XCD class owns an eighth: group_range())
+inline int one_block_per_cu_grid(const FieldArgs& a) {
+    const long long want = (a.total_tiles / a.tiles_per_image) * ((a.tiles_per_image + 3) / 4);
+    const int cus = cu_count();
+    int blocks = (int)(want < cus ? want : cus);
+    if (blocks < 8) blocks = 8;
+    return (blocks + 7) / 8 * 8;
+}
+
+// f: the geometry the grid is sized from (the forward kernels' own argument; the chains carry it inside theirs).  lds_attr_bytes: the
+// kernel's dynamic-LDS allowance (>= lds_bytes), set per launch, not once per process: the attribute is per device, and a cached
+// flag would be unsynchronised global state
+template <typename Args>
+inline hipError_t launch_per_cu(void (*kernel)(Args), const FieldArgs& f, size_t lds_bytes, size_t lds_attr_bytes, const Args& args, hipStream_t stream) {
+    if (hipError_t e = hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_attr_bytes)) return e;
+    hipLaunchKernelGGL(kernel, dim3(one_block_per_cu_grid(f)), dim3(256), lds_bytes, stream, args);
+    return hipGetLastError();
+}
+
+// hidden width -> the kernels' template parameter: f(std::integral_constant<int, NT>{}) with NT = H / 32 output tiles
+template <typename F>
+inline hipError_t dispatch_nt(int H, F f) {
+    switch (H / 32) {
+        case 2: return f(std::integral_constant<int, 2>{});
+        case 4: return f(std::integral_constant<int, 4>{});
+        case 8: return f(std::integral_constant<int, 8>{});
+        default: return hipErrorInvalidValue;
+    }
+}
 
 hipError_t launch_fill(float* dst, float value, int n, hipStream_t stream);
 hipError_t launch_pack_matrix(const float* w, int n_out, int K_real, int OT, float* dst, hipStream_t stream);

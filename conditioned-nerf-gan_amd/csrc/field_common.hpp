@@ -275,6 +275,39 @@ __device__ __forceinline__ TileRange tile_range(long long total_tiles) {
     return r;
 }
 
+// The same ownership for the fp16 kernels, whose work unit is a GROUP of 4 consecutive tiles of one image (the four waves of a block
+// work on one group at a time and share the image's constants): the block takes the groups begin, begin + stride, .. below end with
+// stride = blk_per_cls * group_step, i.e. every group_step-th group of its share (1: all of them; the dry runs of the gradient chains
+// sample).  A block without a group has begin >= end (block-uniform).  nblk = gridDim.x and blk = blockIdx.x are read by the kernel
+// itself, and the stride is left to it as well: the compiler arranges the kernels' scalar prologues differently otherwise.
+struct GroupRange {
+    long long begin, end;
+    int blk_per_cls;       // blocks of this block's class
+};
+__device__ __forceinline__ GroupRange group_range(long long total_groups, int nblk, unsigned blk, int group_step = 1) {
+    const int cls = blk & 7, idx_in_cls = blk >> 3;
+    GroupRange r;
+    r.blk_per_cls = (nblk + 7 - cls) / 8;
+    r.begin = total_groups * cls / 8 + (long long)idx_in_cls * group_step;
+    r.end = total_groups * (cls + 1) / 8;
+    return r;
+}
+
+// the point a wave works on: group g of 4 consecutive tiles of one image (G groups per image), tile `wave` of the group
+struct TilePoint {
+    int b;
+    long long nn;      // point inside the image (clamped to the last one for idle waves / padded lanes)
+    bool valid;
+};
+__device__ __forceinline__ TilePoint tile_of_group(const FieldArgs& a, long long g, long long G, int wave, int j) {
+    TilePoint p;
+    p.b = (int)(g / G);
+    const long long n = ((g - (long long)p.b * G) * 4 + wave) * 32 + j;
+    p.valid = n < a.n_per_image;
+    p.nn = p.valid ? n : (a.n_per_image - 1);
+    return p;
+}
+
 // rgb_sigma pre-activations of the tile: returns, in lanes 0..31, the 4 head outputs of the lane's point.
 template <int NT>
 __device__ __forceinline__ f32x4 head_forward(const f32x4* __restrict__ wp, const float* __restrict__ bias, const f32x16* x,

@@ -14,17 +14,13 @@
 // are the B fragment of k-chunk 2t+s of the next layer (k order inside the chunk: 8(j>>2) + 4h + (j&3)), and the packed
 // A fragments follow the same order (pack_h3_kernel).
 //
-// Weight units through LDS.  Per point tile the kernel consumes a flat sequence of equally sized weight units: one per
-// layer-0 input tile (its NT output tiles x 2 k-chunks), then for every hidden layer its NT output tiles (2*NT k-chunks
-// each), then the head -- each 4*NT pieces of 1 KiB (32 KiB at H = 256).  The four waves of a block walk that sequence in
-// lockstep on four point tiles of the same image: each wave copies a quarter of the NEXT unit into the idle half of a
-// double buffer with LDS-DMA (global_load_lds_dwordx4: 1 KiB per wave instruction, no VGPRs), all four read the CURRENT
-// one with ds_read_b128 (conflict-free: lane-linear 16 B), and one s_barrier per unit both publishes the DMA'd half and
-// retires the reads of the other.  Why (scripts/ubench/split_loop_model.hip, one wave per SIMD on all CUs, 20 VALU per
-// k-chunk): with every wave streaming its own copy of the weights from L2 (4x the L2 -> CU traffic, ~20 TB/s aggregate)
-// a chunk of three MFMAs takes 123 ns, staged through LDS 97 ns, 65 ns for the MFMAs alone.  Biases, the per-layer
-// 2^-S factors and the image's freq / phase vectors live in LDS as well: vmcnt retires in order, so a wait for any
-// global load behind a DMA burst is a wait for the whole burst.
+// Weight units through LDS (the weight-unit ring: bwd16.hpp).  Per point tile the kernel consumes a flat sequence of equally sized
+// weight units: one per layer-0 input tile (its NT output tiles x 2 k-chunks), then for every hidden layer its NT output tiles
+// (2*NT k-chunks each), then the head -- each 4*NT pieces of 1 KiB (32 KiB at H = 256), through a double buffer, one s_barrier per
+// unit.  Why (scripts/ubench/split_loop_model.hip, one wave per SIMD on all CUs, 20 VALU per k-chunk): with every wave streaming
+// its own copy of the weights from L2 (4x the L2 -> CU traffic, ~20 TB/s aggregate) a chunk of three MFMAs takes 123 ns, staged
+// through LDS 97 ns, 65 ns for the MFMAs alone.  Biases, the per-layer 2^-S factors and the image's freq / phase vectors live in
+// LDS as well: vmcnt retires in order, so a wait for any global load behind a DMA burst is a wait for the whole burst.
 #include "cnerf_dev.hpp"
 #include "cnerf_kernels.hpp"
 #include "field_common.hpp"
@@ -46,20 +42,11 @@ namespace H3_NS {
 //   element j of lane (i = lane&31, h = lane>>5) = part_k( S * W[32t + i][16c + 8(j>>2) + 4h + (j&3)] )
 // S = 2^floor(log2(16384 / max|W|)) per matrix (on the device, no host round trip); 1/S goes to the kernel.
 // ---------------------------------------------------------------------------------------------------------------
-
-__device__ __forceinline__ float pow2_scale(float wmax) {
-    if (!(wmax > 1e-30f) || !(wmax < 3e38f)) return 1.0f;
-    int e;
-    (void)frexpf(16384.0f / wmax, &e);          // 16384 / wmax = m 2^e, m in [0.5, 1)
-    e = e - 1 > 100 ? 100 : e - 1;
-    return ldexpf(1.0f, e);
-}
-
 // t_stride: fragment pairs between successive output tiles in dst (KC: dense; larger: the tiles of several matrices interleaved,
 // field_pw16.hip)
 __global__ void pack_h3_kernel(const float* __restrict__ w, int n_out, int K_real, int KC, int OT, int k_outer, long long t_stride,
                                const uint32_t* wmax_slot, float* inv_scale_slot, _Float16* __restrict__ dst) {
-    const float S = pow2_scale(__uint_as_float(*wmax_slot));
+    const float S = pow2_weight_scale(__uint_as_float(*wmax_slot));
     if (blockIdx.x == 0 && threadIdx.x == 0) *inv_scale_slot = 1.0f / S;
     const long long total = (long long)OT * KC * 64 * 8;          // one thread per (t, c, lane, j): writes both parts
     for (long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += (long long)gridDim.x * blockDim.x) {
@@ -395,107 +382,12 @@ struct H3Lds {
     static constexpr int KC = 2 * NT;
     static constexpr int PIECES = KC * PARTS;          // 1-KiB pieces (64 fragments) per weight unit
     static constexpr int FRAGS = PIECES * 64;          // f16x8 fragments per weight unit
-    static constexpr int PER_WAVE = PIECES / 4;        // pieces each wave copies
 };
-
-
-// every weight unit is contiguous in the packed stream (pack_h3_kernel); wave w moves the
-// pieces [w*PER_WAVE, (w+1)*PER_WAVE), four per base address (instruction offsets 0, 1, 2, 3 KiB)
-template <int NT>
-__device__ __forceinline__ void dma_unit_flat(const f16x8* __restrict__ src, f16x8* lds_dst, int wave_u, int lane) {
-    constexpr int PW = H3Lds<NT>::PER_WAVE;
-    const f16x8* s0 = src + (size_t)wave_u * PW * 64 + lane;
-    f16x8* d0 = lds_dst + wave_u * PW * 64;
-#pragma unroll
-    for (int q = 0; q < (PW + 3) / 4; ++q) {
-        const f16x8* sq = s0 + q * 256;
-        f16x8* dq = d0 + q * 256;
-        if (4 * q + 0 < PW) dma_piece<0>(sq, dq);
-        if (4 * q + 1 < PW) dma_piece<1024>(sq, dq);
-        if (4 * q + 2 < PW) dma_piece<2048>(sq, dq);
-        if (4 * q + 3 < PW) dma_piece<3072>(sq, dq);
-    }
-}
-
-// acc (one 32-row output tile) += W_unit * x, A fragments from the LDS copy of the unit; the caller's functor runs once
-// per k-chunk (the pipelined epilogue of the previous output tile).  VALU_PER_MFMA sizes the interleave groups.
-template <int NT, int VALU_PER_MFMA, typename PerChunk>
-__device__ __forceinline__ f32x16 h3_tile_from_lds(const f16x8* lds_tile, const Split2* x, f32x16 acc, int lane, PerChunk per_chunk) {
-    constexpr int KC = 2 * NT;
-    constexpr int AHEAD = 2;
-    f16x8 ring[AHEAD][PARTS];
-#pragma unroll
-    for (int i = 0; i < AHEAD; ++i)
-#pragma unroll
-        for (int k = 0; k < PARTS; ++k) ring[i][k] = lds_tile[(i * PARTS + k) * 64 + lane];
-#pragma unroll
-    for (int c = 0; c < KC; ++c) {
-        f16x8 a[PARTS];
-#pragma unroll
-        for (int k = 0; k < PARTS; ++k) a[k] = ring[c % AHEAD][k];
-        if (c + AHEAD < KC) {
-#pragma unroll
-            for (int k = 0; k < PARTS; ++k) ring[c % AHEAD][k] = lds_tile[((c + AHEAD) * PARTS + k) * 64 + lane];
-        }
-        H3_MFMA3(acc, a, x[c]);          // small terms first, the leading product last
-        per_chunk(c);
-        if (VALU_PER_MFMA > 0) {
-#pragma unroll
-            for (int m = 0; m < (PARTS == 1 ? 1 : 3); ++m) {
-                __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-                __builtin_amdgcn_sched_group_barrier(0x002, PARTS == 1 ? 3 * VALU_PER_MFMA : VALU_PER_MFMA, 0);
-            }
-        }
-        __builtin_amdgcn_sched_barrier(0);
-    }
-    return acc;
-}
-
-// layer-0 unit: all NT output tiles, two k-chunks each (the 32 channels of one input tile), one ring across the tiles
-template <int NT>
-__device__ __forceinline__ void h3_layer0_from_lds(const f16x8* lds_unit, const Split2* f2, f32x16* acc0, int lane) {
-    constexpr int Q = 2 * NT;
-    constexpr int AHEAD = 2;
-    f16x8 ring[AHEAD][PARTS];
-#pragma unroll
-    for (int i = 0; i < AHEAD; ++i)
-#pragma unroll
-        for (int k = 0; k < PARTS; ++k) ring[i][k] = lds_unit[(i * PARTS + k) * 64 + lane];
-#pragma unroll
-    for (int q = 0; q < Q; ++q) {
-        f16x8 a[PARTS];
-#pragma unroll
-        for (int k = 0; k < PARTS; ++k) a[k] = ring[q % AHEAD][k];
-        if (q + AHEAD < Q) {
-#pragma unroll
-            for (int k = 0; k < PARTS; ++k) ring[q % AHEAD][k] = lds_unit[((q + AHEAD) * PARTS + k) * 64 + lane];
-        }
-        f32x16 acc = acc0[q >> 1];
-        H3_MFMA3(acc, a, f2[q & 1]);
-        acc0[q >> 1] = acc;
-        __builtin_amdgcn_sched_barrier(0);
-    }
-}
 
 template <int N>
 struct Younger { static constexpr int value = N; };            // compile-time tag of unit_begin() in the kernel
 struct ResidNo { static constexpr bool value = false; };      // compile-time tags for the `matrix` lambda of the kernel
 struct ResidYes { static constexpr bool value = true; };
-
-// the point a wave works on: group g of 4 consecutive tiles of one image, tile `wave` of the group
-struct TilePoint {
-    int b;
-    long long nn;      // point inside the image (clamped to the last one for idle waves / padded lanes)
-    bool valid;
-};
-__device__ __forceinline__ TilePoint tile_of_group(const FieldArgs& a, long long g, long long G, int wave, int j) {
-    TilePoint p;
-    p.b = (int)(g / G);
-    const long long n = ((g - (long long)p.b * G) * 4 + wave) * 32 + j;
-    p.valid = n < a.n_per_image;
-    p.nn = p.valid ? n : (a.n_per_image - 1);
-    return p;
-}
 
 // One block of four waves per CU (512 registers per wave), two weight units in LDS, one barrier per unit.  (Measured in round 2
 // and not kept: four slots with a barrier per two units -- no change; two waves per SIMD by a register cap -- spills, slower; a
@@ -523,13 +415,10 @@ __global__ __launch_bounds__(256) void field_h3_kernel(FieldArgs a) {
     const int j = lane & 31, h = lane >> 5;
 
     // Work units are groups of 4 consecutive tiles of ONE image (so the block shares freq / phase); the four waves run in
-    // lockstep on the tiles of a group.  XCD-aware ownership as in tile_range(): block class c owns a contiguous eighth.
+    // lockstep on the tiles of a group.
     const long long G = (a.tiles_per_image + 3) / 4;
     const long long total_groups = (a.total_tiles / a.tiles_per_image) * G;
-    const int nblk = gridDim.x;
-    const int cls = blockIdx.x & 7, idx_in_cls = blockIdx.x >> 3;
-    const int blk_per_cls = (nblk + 7 - cls) / 8;
-    const long long g_begin = total_groups * cls / 8 + idx_in_cls, g_end = total_groups * (cls + 1) / 8;
+    const GroupRange gr = group_range(total_groups, gridDim.x, blockIdx.x);
 
     // the per-tile unit sequence, back to back.  WF: every image has its own copy (rows scaled by its FiLM frequencies); the copy runs
     // one unit ahead of the MFMAs, across tile boundaries: `dma_base` is the image of the tile whose units are being requested,
@@ -538,7 +427,7 @@ __global__ __launch_bounds__(256) void field_h3_kernel(FieldArgs a) {
     const f16x8* img_units = reinterpret_cast<const f16x8*>(a.packed_img);
     const size_t img_stride = (size_t)a.packed_img_stride;           // f16x8 fragments per image
     int staged_b = -1;                                               // image whose FiLM vectors are in LDS
-    if (g_begin >= g_end) return;                                    // block-uniform
+    if (gr.begin >= gr.end) return;                                  // block-uniform
 
     // The block consumes one flat sequence of weight units: n_units per point tile (layer-0 unit per input tile, NT per
     // hidden layer, head), tile after tile.  Unit i lives in LDS slot i % 2; the barrier at the start of a unit publishes the copy of
@@ -549,7 +438,7 @@ __global__ __launch_bounds__(256) void field_h3_kernel(FieldArgs a) {
     const f16x8* dma_base = w_units;
     const f16x8* next_base = w_units;
     auto dma_next = [&]() {       // (past the block's last tile this re-copies units nobody reads: harmless, drained at the end)
-        dma_unit_flat<NT>(dma_base + (size_t)dma_k * UNIT_FR, lds + dma_slot * UNIT_FR, wave_u, lane);
+        dma_unit<H3Lds<NT>::PIECES>(dma_base + (size_t)dma_k * UNIT_FR, lds + dma_slot * UNIT_FR, wave_u, lane);
         dma_k = dma_k + 1 == n_units ? 0 : dma_k + 1;
         if (WF && dma_k == 0) dma_base = next_base;
         dma_slot = (dma_slot + 1) & (SLOTS - 1);
@@ -586,7 +475,7 @@ __global__ __launch_bounds__(256) void field_h3_kernel(FieldArgs a) {
     // prologue: biases and scales into LDS, the first weight unit (the first barrier publishes both); position and lookups of
     // the first tile
     for (int i = threadIdx.x; i < a.bias_floats + 2 * H; i += 256) lds_bias[i] = a.bias[i];
-    TilePoint tp = tile_of_group(a, g_begin, G, wave, j);
+    TilePoint tp = tile_of_group(a, gr.begin, G, wave, j);
     if (WF) dma_base = next_base = img_units + (size_t)(tp.b + a.image0) * img_stride;
     dma_next();
     float px, py, pz;
@@ -594,7 +483,7 @@ __global__ __launch_bounds__(256) void field_h3_kernel(FieldArgs a) {
     InputTile it;
     input_tile_issue_volume(a, tp.b, 0, px, py, pz, h, it);      // input tile 0 is a volume tile (checked by the launcher)
 
-    for (long long g = g_begin; g < g_end; g += blk_per_cls) {
+    for (long long g = gr.begin; g < gr.end; g += gr.blk_per_cls) {
         const int b = tp.b;
         const long long nn = tp.nn;
         const bool valid = tp.valid;
@@ -634,8 +523,8 @@ __global__ __launch_bounds__(256) void field_h3_kernel(FieldArgs a) {
             __syncthreads();                                        // (once per image: not every unit starts with a barrier)
         }
         // raw sample coordinate of the NEXT tile: one load now, consumed behind the head's barrier
-        const bool has_next = g + blk_per_cls < g_end;
-        const TilePoint tn = tile_of_group(a, has_next ? g + blk_per_cls : g, G, wave, j);
+        const bool has_next = g + gr.blk_per_cls < gr.end;
+        const TilePoint tn = tile_of_group(a, has_next ? g + gr.blk_per_cls : g, G, wave, j);
         const TileRaw raw_next = tile_point_fetch(a, tn.b, tn.nn);
         if (WF) next_base = img_units + (size_t)(tn.b + a.image0) * img_stride;
 
@@ -692,7 +581,7 @@ __global__ __launch_bounds__(256) void field_h3_kernel(FieldArgs a) {
                 Split2 f2[2];
                 f2[0] = split8_clamped(fv);
                 f2[1] = split8_clamped(fv + 8);
-                h3_layer0_from_lds<NT>(unit, f2, acc0, lane);
+                input_unit<NT>(unit, f2, acc0, lane);
             }
             const bool film = a.layer_kind[0] == CNERF_LAYER_FILM;
             const float inv_s = WF ? lds_mh[0] : lds_inv_s[0];
@@ -739,7 +628,8 @@ __global__ __launch_bounds__(256) void field_h3_kernel(FieldArgs a) {
                 else
 #pragma unroll
                     for (int r = 0; r < 16; ++r) acc[r] = 0.0f;
-                acc = h3_tile_from_lds<NT, H3_VPM>(unit, in, acc, lane, [&](int c) {
+                // (2 * NT, not the kernel's KCH: with that local named here the fp32-storing instantiations compile to different code)
+                acc = tile_kc<2 * NT, H3_VPM>(unit, in, acc, lane, [&](int c) {
                     if (t > 0 && c < 16) {                     // epilogue of tile t-1, one pair of elements per two chunks
                         if (WF) {
                             if (c & 1) film_split_pair<STORE, RESID, 0, WF>(acc_prev, inv_s, fp, t - 1, h, c - 1, &out[2 * (t - 1)], st);
@@ -797,7 +687,7 @@ __global__ __launch_bounds__(256) void field_h3_kernel(FieldArgs a) {
             f32x16 acc;
 #pragma unroll
             for (int r = 0; r < 16; ++r) acc[r] = 0.0f;
-            acc = h3_tile_from_lds<NT, 0>(unit, x, acc, lane, [](int) {});
+            acc = tile_kc<2 * NT, 0>(unit, x, acc, lane, [](int) {});
             if (valid && h == 0) {
                 const f32x4 hb = *reinterpret_cast<const f32x4*>(bias);
                 const float inv_s = lds_inv_s[a.n_mats];
@@ -821,8 +711,6 @@ __global__ __launch_bounds__(256) void field_h3_kernel(FieldArgs a) {
     __syncthreads();                                                 // write must not land after the block has given its LDS back
 }
 
-constexpr size_t LDS_LIMIT = 160 * 1024;
-
 template <int NT>
 static size_t h3_lds_bytes(const FieldArgs& a, int slots) {
     // weight units (32 KiB each at H = 256), biases + scales, ones / zeros, freq / phase of one image
@@ -833,19 +721,9 @@ static size_t h3_lds_bytes(const FieldArgs& a, int slots) {
 
 template <int NT, int STORE, bool HAS_RES, int WF>
 static hipError_t launch_h3_inst(const FieldArgs& a, hipStream_t stream) {
-    int dev = 0, cus = 256;
-    if (hipGetDevice(&dev) != hipSuccess) dev = 0;
-    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) cus = 256;
     const size_t lds_bytes = h3_lds_bytes<NT>(a, 2);
     if (lds_bytes > LDS_LIMIT) return hipErrorInvalidValue;
-    // (per launch, not once per process: the attribute is per device, and a cached flag would be unsynchronised global state)
-    if (hipError_t e = hipFuncSetAttribute((const void*)field_h3_kernel<NT, STORE, HAS_RES, WF>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_LIMIT)) return e;
-    const long long want = (a.total_tiles / a.tiles_per_image) * ((a.tiles_per_image + 3) / 4);
-    int blocks = (int)(want < cus ? want : cus);        // one block of four waves per CU (512 registers per wave)
-    if (blocks < 8) blocks = 8;
-    blocks = (blocks + 7) / 8 * 8;
-    hipLaunchKernelGGL((field_h3_kernel<NT, STORE, HAS_RES, WF>), dim3(blocks), dim3(256), lds_bytes, stream, a);
-    return hipGetLastError();
+    return launch_per_cu(field_h3_kernel<NT, STORE, HAS_RES, WF>, a, lds_bytes, LDS_LIMIT, a, stream);
 }
 
 template <int NT, int STORE>
@@ -868,12 +746,10 @@ static hipError_t field_impl(const FieldArgs& a, int H, hipStream_t stream) {
     if (a.n_in < 1 || a.in_level[0] < 0) return hipErrorInvalidValue;      // the cross-tile lookup prefetch assumes a volume tile first
     // a.act_h set: activation-storing forward of the backward pass, fp32 rows or (a.act_tb16) fp16 tile blocks
     const int store = a.act_h == nullptr ? STORE_NONE : (a.act_tb16 ? STORE_TB16 : STORE_F32);
-    switch (H / 32) {
-        case 2: return store == STORE_TB16 ? launch_h3_nt<2, STORE_TB16>(a, stream) : store ? launch_h3_nt<2, STORE_F32>(a, stream) : launch_h3_nt<2, STORE_NONE>(a, stream);
-        case 4: return store == STORE_TB16 ? launch_h3_nt<4, STORE_TB16>(a, stream) : store ? launch_h3_nt<4, STORE_F32>(a, stream) : launch_h3_nt<4, STORE_NONE>(a, stream);
-        case 8: return store == STORE_TB16 ? launch_h3_nt<8, STORE_TB16>(a, stream) : store ? launch_h3_nt<8, STORE_F32>(a, stream) : launch_h3_nt<8, STORE_NONE>(a, stream);
-        default: return hipErrorInvalidValue;
-    }
+    return dispatch_nt(H, [&](auto nt) {
+        constexpr int NT = decltype(nt)::value;
+        return store == STORE_TB16 ? launch_h3_nt<NT, STORE_TB16>(a, stream) : store ? launch_h3_nt<NT, STORE_F32>(a, stream) : launch_h3_nt<NT, STORE_NONE>(a, stream);
+    });
 }
 
 }  // namespace H3_NS

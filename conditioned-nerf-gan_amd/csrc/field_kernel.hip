@@ -1048,23 +1048,11 @@ hipError_t launch_pack_matrix(const float* w, int n_out, int K_real, int OT, flo
 }
 
 static int field_grid(const void* kernel, long long total_tiles) {
-    int dev = 0, cus = 256, per_cu = 1;
-    if (hipGetDevice(&dev) != hipSuccess) dev = 0;
-    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) cus = 256;
+    int per_cu = 1;
     if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, 256, 0) != hipSuccess || per_cu < 1) per_cu = 1;
-    const long long want = (total_tiles + 3) / 4, cap = (long long)cus * per_cu;
+    const long long want = (total_tiles + 3) / 4, cap = (long long)cu_count() * per_cu;
     int blocks = (int)(want < cap ? want : cap);
     if (blocks < 8) blocks = 8;               // every XCD class owns an eighth of the tiles
-    return (blocks + 7) / 8 * 8;
-}
-
-static int field_grid_one_per_cu(long long total_tiles) {
-    int dev = 0, cus = 256;
-    if (hipGetDevice(&dev) != hipSuccess) dev = 0;
-    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) cus = 256;
-    const long long want = (total_tiles + 3) / 4;
-    int blocks = (int)(want < cus ? want : cus);
-    if (blocks < 8) blocks = 8;
     return (blocks + 7) / 8 * 8;
 }
 
@@ -1109,13 +1097,8 @@ hipError_t launch_field_backward(const FieldArgs& a, int H, hipStream_t stream) 
 template <int NT, bool HAS_RES, bool STORE, bool DROP, bool FOLD = false, int WFOLD = 0>
 static hipError_t launch_field_tile(const FieldArgs& a, hipStream_t stream) {
     if (a.n_in < 1 || a.in_level[0] < 0) return hipErrorInvalidValue;      // the lookup prefetch assumes a volume tile first
-    const void* fn = (const void*)field_tile_kernel<NT, HAS_RES, STORE, DROP, FOLD, WFOLD>;
-    const int lds_bytes = 0;
-    // (per launch, not once per process: the attribute is per device, and a cached flag would be unsynchronised global state)
-    if (lds_bytes)
-        if (hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes)) return e;
-    const int blocks = lds_bytes ? field_grid_one_per_cu(a.total_tiles) : field_grid(fn, a.total_tiles);
-    hipLaunchKernelGGL((field_tile_kernel<NT, HAS_RES, STORE, DROP, FOLD, WFOLD>), dim3(blocks), dim3(256), lds_bytes, stream, a);
+    const int blocks = field_grid((const void*)field_tile_kernel<NT, HAS_RES, STORE, DROP, FOLD, WFOLD>, a.total_tiles);
+    hipLaunchKernelGGL((field_tile_kernel<NT, HAS_RES, STORE, DROP, FOLD, WFOLD>), dim3(blocks), dim3(256), 0, stream, a);
     return hipGetLastError();
 }
 

@@ -9,8 +9,8 @@
 // 1.5 M MACs per point at H = 256, two thirds of them in the mapping network's second Linear, whose 2 L H outputs are never
 // materialised: per 32-channel output tile the kernel runs three accumulations (fr and ph against m, pre against x) and combines them
 // in the epilogue.  Same construction as field_h3.hip: one wave per 32-point tile, accumulator registers converted pairwise are the
-// next B operands, four waves of a block walk one flat sequence of weight units through a three-slot LDS ring filled by LDS-DMA (one
-// barrier per unit, counted vmcnt wait in front of it).  The sequence per tile, in the order the packed stream holds it:
+// next B operands, weight units through a three-slot LDS ring (the weight-unit ring: bwd16.hpp).  The sequence per tile, in the order the
+// packed stream holds it:
 //     Wm1 (8 output tiles x 2 k-chunks) | W_0 (NT x 2) | layer 0: per output tile t  fr_t, ph_t  (16 k-chunks each: K = 256)
 //     | layers 1..L-1: per t  fr_t, pre_t (2 NT chunks: K = H), ph_t | head (1 tile x 2 NT chunks)
 // i.e. two unit sizes: 16 PARTS pieces of 1 KiB for everything multiplied by m (and Wm1), 2 NT PARTS for what is multiplied by x.
@@ -40,83 +40,6 @@ namespace H3_NS {
 namespace pw {
 
 constexpr int KCM = 16;            // k-chunks of everything multiplied by m (the mapping network's hidden width is 256)
-
-// PIECES 1-KiB pieces of a weight unit, contiguous in the packed stream: wave w moves the pieces [w PIECES / 4, (w + 1) PIECES / 4)
-template <int PIECES>
-__device__ __forceinline__ void dma_unit(const f16x8* __restrict__ src, f16x8* lds_dst, int wave_u, int lane) {
-    static_assert(PIECES % 4 == 0, "four waves share a unit");
-    constexpr int PW = PIECES / 4;
-    const f16x8* s0 = src + (size_t)wave_u * PW * 64 + lane;
-    f16x8* d0 = lds_dst + wave_u * PW * 64;
-#pragma unroll
-    for (int q = 0; q < (PW + 3) / 4; ++q) {
-        const f16x8* sq = s0 + q * 256;
-        f16x8* dq = d0 + q * 256;
-        if (4 * q + 0 < PW) dma_piece<0>(sq, dq);
-        if (4 * q + 1 < PW) dma_piece<1024>(sq, dq);
-        if (4 * q + 2 < PW) dma_piece<2048>(sq, dq);
-        if (4 * q + 3 < PW) dma_piece<3072>(sq, dq);
-    }
-}
-
-// acc (one 32-row output tile) += W_unit x over KC k-chunks, A fragments from the LDS copy of the unit; the caller's functor runs
-// once per k-chunk (vector work that rides under the MFMAs: VPM vector instructions are scheduled behind each of them)
-template <int KC, int VPM, typename PerChunk>
-__device__ __forceinline__ f32x16 tile_kc(const f16x8* lds_tile, const Split2* x, f32x16 acc, int lane, PerChunk per_chunk) {
-    constexpr int AHEAD = 2;
-    f16x8 ring[AHEAD][PARTS];
-#pragma unroll
-    for (int i = 0; i < AHEAD; ++i)
-#pragma unroll
-        for (int k = 0; k < PARTS; ++k) ring[i][k] = lds_tile[(i * PARTS + k) * 64 + lane];
-#pragma unroll
-    for (int c = 0; c < KC; ++c) {
-        f16x8 a[PARTS];
-#pragma unroll
-        for (int k = 0; k < PARTS; ++k) a[k] = ring[c % AHEAD][k];
-        if (c + AHEAD < KC) {
-#pragma unroll
-            for (int k = 0; k < PARTS; ++k) ring[c % AHEAD][k] = lds_tile[((c + AHEAD) * PARTS + k) * 64 + lane];
-        }
-        H3_MFMA3(acc, a, x[c]);
-        per_chunk(c);
-        if (VPM > 0) {
-#pragma unroll
-            for (int m = 0; m < (PARTS == 1 ? 1 : 3); ++m) {
-                __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-                __builtin_amdgcn_sched_group_barrier(0x002, PARTS == 1 ? 3 * VPM : VPM, 0);
-            }
-        }
-        __builtin_amdgcn_sched_barrier(0);
-    }
-    return acc;
-}
-
-// a unit of OT output tiles x 2 k-chunks (one 32-wide input tile; pack_h3_kernel's k_outer order): acc0[t] += W[t] f
-template <int OT>
-__device__ __forceinline__ void input_unit(const f16x8* lds_unit, const Split2* f2, f32x16* acc0, int lane) {
-    constexpr int Q = 2 * OT;
-    constexpr int AHEAD = 2;
-    f16x8 ring[AHEAD][PARTS];
-#pragma unroll
-    for (int i = 0; i < AHEAD; ++i)
-#pragma unroll
-        for (int k = 0; k < PARTS; ++k) ring[i][k] = lds_unit[(i * PARTS + k) * 64 + lane];
-#pragma unroll
-    for (int q = 0; q < Q; ++q) {
-        f16x8 a[PARTS];
-#pragma unroll
-        for (int k = 0; k < PARTS; ++k) a[k] = ring[q % AHEAD][k];
-        if (q + AHEAD < Q) {
-#pragma unroll
-            for (int k = 0; k < PARTS; ++k) ring[q % AHEAD][k] = lds_unit[((q + AHEAD) * PARTS + k) * 64 + lane];
-        }
-        f32x16 acc = acc0[q >> 1];
-        H3_MFMA3(acc, a, f2[q & 1]);
-        acc0[q >> 1] = acc;
-        __builtin_amdgcn_sched_barrier(0);
-    }
-}
 
 // elements r, r + 1 (r even) of an output tile -> dword (r & 7) / 2 of the fragments of chunk r >> 3 (out2 = the tile's chunk pair)
 __device__ __forceinline__ void split_into(Split2* out2, int r, float v0, float v1) {
@@ -172,21 +95,6 @@ __device__ __forceinline__ void film_pair_store(const f32x16& q, const f32x16& p
     split_into(out2, r, sn[0], sn[1]);
 }
 
-struct TilePoint {
-    int b;
-    long long nn;      // point inside the image (clamped to the last one for idle waves / padded lanes)
-    bool valid;
-};
-// group g of 4 consecutive tiles of one image, tile `wave` of the group (as field_h3.hip)
-__device__ __forceinline__ TilePoint tile_of_group(const FieldArgs& a, long long g, long long G, int wave, int j) {
-    TilePoint p;
-    p.b = (int)(g / G);
-    const long long n = ((g - (long long)p.b * G) * 4 + wave) * 32 + j;
-    p.valid = n < a.n_per_image;
-    p.nn = p.valid ? n : (a.n_per_image - 1);
-    return p;
-}
-
 struct FirstLayer { static constexpr bool value = true; };
 struct LaterLayer { static constexpr bool value = false; };
 
@@ -215,14 +123,10 @@ __global__ __launch_bounds__(256) void field_pw16_kernel(FieldArgs a) {
     const int wave_u = __builtin_amdgcn_readfirstlane(wave);
     const int j = lane & 31, h = lane >> 5;
 
-    // groups of 4 consecutive tiles of one image, XCD-aware ownership as in field_h3.hip / tile_range()
     const long long G = (a.tiles_per_image + 3) / 4;
     const long long total_groups = (a.total_tiles / a.tiles_per_image) * G;
-    const int nblk = gridDim.x;
-    const int cls = blockIdx.x & 7, idx_in_cls = blockIdx.x >> 3;
-    const int blk_per_cls = (nblk + 7 - cls) / 8;
-    const long long g_begin = total_groups * cls / 8 + idx_in_cls, g_end = total_groups * (cls + 1) / 8;
-    if (g_begin >= g_end) return;                                    // block-uniform
+    const GroupRange gr = group_range(total_groups, gridDim.x, blockIdx.x);
+    if (gr.begin >= gr.end) return;                                  // block-uniform
 
     // the flat unit sequence of a tile; the copy runs one unit ahead of the MFMAs, across tile boundaries
     const int n_units = 2 + 2 * NT + (L - 1) * 3 * NT + 1;
@@ -270,7 +174,7 @@ __global__ __launch_bounds__(256) void field_pw16_kernel(FieldArgs a) {
     dma_next();
     __syncthreads();             // the constants are plain LDS stores: published here, once (the unit barriers order LDS-DMA data only)
 
-    for (long long g = g_begin; g < g_end; g += blk_per_cls) {
+    for (long long g = gr.begin; g < gr.end; g += gr.blk_per_cls) {
         const TilePoint tp = tile_of_group(a, g, G, wave, j);
         float px, py, pz;
         tile_point(a, tp.b, tp.nn, tp.valid, h, true, px, py, pz);
@@ -488,11 +392,8 @@ __global__ __launch_bounds__(256) void pw_deriv_kernel(FieldArgs a) {
     const int j = lane & 31, h = lane >> 5;
     const long long G = (a.tiles_per_image + 3) / 4;
     const long long total_groups = (a.total_tiles / a.tiles_per_image) * G;
-    const int nblk = gridDim.x;
-    const int cls = blockIdx.x & 7, idx_in_cls = blockIdx.x >> 3;
-    const int blk_per_cls = (nblk + 7 - cls) / 8;
-    const long long g_begin = total_groups * cls / 8 + idx_in_cls, g_end = total_groups * (cls + 1) / 8;
-    if (g_begin >= g_end) return;
+    const GroupRange gr = group_range(total_groups, gridDim.x, blockIdx.x);
+    if (gr.begin >= gr.end) return;
 
     // the used units of a tile and where their hi pieces start in the two-part stream (1-KiB pieces; a unit of n k-chunk fragments is 2 n pieces)
     const int n_used = 1 + NT + (L - 1) * 2 * NT;
@@ -547,7 +448,7 @@ __global__ __launch_bounds__(256) void pw_deriv_kernel(FieldArgs a) {
     dma_next();
     __syncthreads();             // the constants are plain LDS stores: published here, once (the unit barriers order LDS-DMA data only)
 
-    for (long long g = g_begin; g < g_end; g += blk_per_cls) {
+    for (long long g = gr.begin; g < gr.end; g += gr.blk_per_cls) {
         const int b = (int)(g / G);
         const long long tile_in_image = (g - (long long)b * G) * 4 + wave;
         const bool live = tile_in_image < a.tiles_per_image;
@@ -664,51 +565,29 @@ __global__ __launch_bounds__(256) void pw_deriv_kernel(FieldArgs a) {
 }
 #endif
 
-constexpr size_t LDS_LIMIT = 160 * 1024;
-
 template <int NT, bool STORE>
 static hipError_t launch_inst(const FieldArgs& a, hipStream_t stream) {
-    int dev = 0, cus = 256;
-    if (hipGetDevice(&dev) != hipSuccess) dev = 0;
-    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) cus = 256;
     const size_t lds_bytes = 3 * (size_t)KCM * PARTS * 1024 + (size_t)a.bias_floats * 4;
     if (lds_bytes > LDS_LIMIT) return hipErrorInvalidValue;
-    if (hipError_t e = hipFuncSetAttribute((const void*)field_pw16_kernel<NT, STORE>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_LIMIT)) return e;
-    const long long want = (a.total_tiles / a.tiles_per_image) * ((a.tiles_per_image + 3) / 4);
-    int blocks = (int)(want < cus ? want : cus);        // one block of four waves per CU (512 registers per wave)
-    if (blocks < 8) blocks = 8;
-    blocks = (blocks + 7) / 8 * 8;
-    hipLaunchKernelGGL((field_pw16_kernel<NT, STORE>), dim3(blocks), dim3(256), lds_bytes, stream, a);
-    return hipGetLastError();
+    return launch_per_cu(field_pw16_kernel<NT, STORE>, a, lds_bytes, LDS_LIMIT, a, stream);
 }
 
 static hipError_t field_impl(const FieldArgs& a, int H, hipStream_t stream) {
     if (a.n_in != 1 || a.in_level[0] < 0 || a.L < 1) return hipErrorInvalidValue;      // one 32-channel volume tile
     const bool store = a.act_h != nullptr;             // activation-storing forward of the half-precision backward (fp16 tile blocks)
     if (store && (PARTS != 2 || !a.act_tb16 || !a.act_feat || !a.act_c || !a.act_amax)) return hipErrorInvalidValue;
-    switch (H / 32) {
-        case 2: return store ? launch_inst<2, true>(a, stream) : launch_inst<2, false>(a, stream);
-        case 4: return store ? launch_inst<4, true>(a, stream) : launch_inst<4, false>(a, stream);
-        case 8: return store ? launch_inst<8, true>(a, stream) : launch_inst<8, false>(a, stream);
-        default: return hipErrorInvalidValue;
-    }
+    return dispatch_nt(H, [&](auto nt) {
+        constexpr int NT = decltype(nt)::value;
+        return store ? launch_inst<NT, true>(a, stream) : launch_inst<NT, false>(a, stream);
+    });
 }
 
 #if CNERF_H3_PARTS == 2
 template <int NT>
 static hipError_t launch_deriv_inst(const FieldArgs& a, hipStream_t stream) {
-    int dev = 0, cus = 256;
-    if (hipGetDevice(&dev) != hipSuccess) dev = 0;
-    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) cus = 256;
     const size_t lds_bytes = 3 * (size_t)KCM * 1024 + (size_t)a.bias_floats * 4;
     if (lds_bytes > LDS_LIMIT) return hipErrorInvalidValue;
-    if (hipError_t e = hipFuncSetAttribute((const void*)pw_deriv_kernel<NT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_LIMIT)) return e;
-    const long long want = (a.total_tiles / a.tiles_per_image) * ((a.tiles_per_image + 3) / 4);
-    int blocks = (int)(want < cus ? want : cus);
-    if (blocks < 8) blocks = 8;
-    blocks = (blocks + 7) / 8 * 8;
-    hipLaunchKernelGGL((pw_deriv_kernel<NT>), dim3(blocks), dim3(256), lds_bytes, stream, a);
-    return hipGetLastError();
+    return launch_per_cu(pw_deriv_kernel<NT>, a, lds_bytes, LDS_LIMIT, a, stream);
 }
 #endif
 
@@ -718,13 +597,8 @@ static hipError_t launch_deriv_inst(const FieldArgs& a, hipStream_t stream) {
 hipError_t PW_LAUNCH_FIELD(const FieldArgs& a, int H, hipStream_t stream) {
     if (hipError_t e = H3_NS::pw::field_impl(a, H, stream)) return e;
 #if CNERF_H3_PARTS == 2
-    if (a.act_h) {      // activation-storing forward: the derivative rows the field kernel leaves out (same stream: ordered behind it)
-        switch (H / 32) {
-            case 2: return H3_NS::pw::launch_deriv_inst<2>(a, stream);
-            case 4: return H3_NS::pw::launch_deriv_inst<4>(a, stream);
-            case 8: return H3_NS::pw::launch_deriv_inst<8>(a, stream);
-        }
-    }
+    if (a.act_h)        // activation-storing forward: the derivative rows the field kernel leaves out (same stream: ordered behind it)
+        return dispatch_nt(H, [&](auto nt) { return H3_NS::pw::launch_deriv_inst<decltype(nt)::value>(a, stream); });
 #endif
     return hipSuccess;
 }

@@ -148,9 +148,7 @@ static hipError_t launch_wg(const WeightGradArgs& a, hipStream_t stream) {
 hipError_t launch_weight_grad(int cnt, long long npi, int H, int K, const float* G, const float* X, float* dW, float* colsum,
                               hipStream_t stream) {
     if (cnt < 1 || npi < 1 || (H != 64 && H != 128 && H != 256) || K < 32 || K > 256 || K % 32) return hipErrorInvalidValue;
-    int dev = 0, cus = 256;
-    if (hipGetDevice(&dev) != hipSuccess) dev = 0;
-    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) cus = 256;
+    const int cus = cu_count();
     WeightGradArgs a{G, X, dW, colsum, npi, cnt, H, K, 1};
     const long long stages = (npi + WG_P - 1) / WG_P;
     const int groups = (H + 127) / 128;

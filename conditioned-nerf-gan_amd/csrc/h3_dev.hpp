@@ -64,18 +64,6 @@ __device__ __forceinline__ Split2 split8_clamped(const float* v) {
     return s;
 }
 
-// the two fp16 halves of a packed pair, widened (exact)
-__device__ __forceinline__ float half_lo(uint32_t u) { return (float)__builtin_bit_cast(_Float16, (unsigned short)(u & 0xffffu)); }
-__device__ __forceinline__ float half_hi(uint32_t u) { return (float)__builtin_bit_cast(_Float16, (unsigned short)(u >> 16)); }
-
-// One wave instruction moves 1 KiB: lane i's 16 bytes from src_lane land at lds_dst + OFF + 16 i (the instruction offset
-// applies to the global and to the LDS address alike).
-template <int OFF>
-__device__ __forceinline__ void dma_piece(const f16x8* src_lane, f16x8* lds_dst) {
-    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src_lane,
-                                     (__attribute__((address_space(3))) void*)lds_dst, 16, OFF, 0);
-}
-
 #if CNERF_H3_PARTS == 1
 #define H3_MFMA3(acc, a, xs) acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(a[0], (xs).frag(0), acc, 0, 0, 0)
 #else
@@ -86,6 +74,67 @@ __device__ __forceinline__ void dma_piece(const f16x8* src_lane, f16x8* lds_dst)
         acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(a[0], (xs).frag(0), acc, 0, 0, 0);        \
     } while (0)
 #endif
+
+// A weight unit read back from its LDS slot (the weight-unit ring: bwd16.hpp), fragment (chunk, part) at (chunk * PARTS + part) * 64 + lane.
+// acc (one 32-row output tile) += W_unit x over KC k-chunks; the caller's functor runs once per k-chunk (vector work that rides under
+// the MFMAs, e.g. the pipelined epilogue of the previous output tile: VPM vector instructions are scheduled behind each of them)
+template <int KC, int VPM, typename PerChunk>
+__device__ __forceinline__ f32x16 tile_kc(const f16x8* lds_tile, const Split2* x, f32x16 acc, int lane, PerChunk per_chunk) {
+    constexpr int AHEAD = 2;
+    f16x8 ring[AHEAD][PARTS];
+#pragma unroll
+    for (int i = 0; i < AHEAD; ++i)
+#pragma unroll
+        for (int k = 0; k < PARTS; ++k) ring[i][k] = lds_tile[(i * PARTS + k) * 64 + lane];
+#pragma unroll
+    for (int c = 0; c < KC; ++c) {
+        f16x8 a[PARTS];
+#pragma unroll
+        for (int k = 0; k < PARTS; ++k) a[k] = ring[c % AHEAD][k];
+        if (c + AHEAD < KC) {
+#pragma unroll
+            for (int k = 0; k < PARTS; ++k) ring[c % AHEAD][k] = lds_tile[((c + AHEAD) * PARTS + k) * 64 + lane];
+        }
+        H3_MFMA3(acc, a, x[c]);          // small terms first, the leading product last
+        per_chunk(c);
+        if (VPM > 0) {
+#pragma unroll
+            for (int m = 0; m < (PARTS == 1 ? 1 : 3); ++m) {
+                __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
+                __builtin_amdgcn_sched_group_barrier(0x002, PARTS == 1 ? 3 * VPM : VPM, 0);
+            }
+        }
+        __builtin_amdgcn_sched_barrier(0);
+    }
+    return acc;
+}
+
+// a unit of OT output tiles x 2 k-chunks (one 32-wide input tile; pack_h3_kernel's k_outer order), one ring across the tiles:
+// acc0[t] += W[t] f
+template <int OT>
+__device__ __forceinline__ void input_unit(const f16x8* lds_unit, const Split2* f2, f32x16* acc0, int lane) {
+    constexpr int Q = 2 * OT;
+    constexpr int AHEAD = 2;
+    f16x8 ring[AHEAD][PARTS];
+#pragma unroll
+    for (int i = 0; i < AHEAD; ++i)
+#pragma unroll
+        for (int k = 0; k < PARTS; ++k) ring[i][k] = lds_unit[(i * PARTS + k) * 64 + lane];
+#pragma unroll
+    for (int q = 0; q < Q; ++q) {
+        f16x8 a[PARTS];
+#pragma unroll
+        for (int k = 0; k < PARTS; ++k) a[k] = ring[q % AHEAD][k];
+        if (q + AHEAD < Q) {
+#pragma unroll
+            for (int k = 0; k < PARTS; ++k) ring[q % AHEAD][k] = lds_unit[((q + AHEAD) * PARTS + k) * 64 + lane];
+        }
+        f32x16 acc = acc0[q >> 1];
+        H3_MFMA3(acc, a, f2[q & 1]);
+        acc0[q >> 1] = acc;
+        __builtin_amdgcn_sched_barrier(0);
+    }
+}
 
 }  // namespace H3_NS
 }  // namespace cnerf
