@@ -106,6 +106,40 @@ __device__ __forceinline__ f32x16 input_tile_reduce(const InputTile& it, float p
     return feat;
 }
 
+// The lean form for a kernel that keeps the lookups of its NEXT tile in flight under the current one: only the 32 loaded
+// float4 are carried; the corner weights are recomputed from the same position by the same function at the reduce, so
+// the tile is bit-identical to input_tile()'s.  tk must be a volume tile.
+struct LookupTile {
+    f32x4 q[8][4];
+};
+__device__ __forceinline__ void lookup_tile_issue(const FieldArgs& a, int b, int tk, float px, float py, float pz, int h, LookupTile& lt) {
+    const int lvl = a.in_level[tk];
+    const int V = a.lvl_V[lvl], C = a.lvl_C[lvl];
+    Corner8 cr;
+    trilinear_corners(px, py, pz, a.half_voxel, V, cr);
+    const float* vol = a.lvl_vol[lvl] + (size_t)b * V * V * V * C + a.in_chan[tk] + 4 * h;
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+        const float* cp = vol + (size_t)cr.base[k] * C;
+#pragma unroll
+        for (int g = 0; g < 4; ++g) lt.q[k][g] = *reinterpret_cast<const f32x4*>(cp + 8 * g);
+    }
+}
+__device__ __forceinline__ f32x16 lookup_tile_reduce(const FieldArgs& a, int tk, const LookupTile& lt, float px, float py, float pz) {
+    Corner8 cr;
+    trilinear_corners(px, py, pz, a.half_voxel, a.lvl_V[a.in_level[tk]], cr);
+    f32x16 feat;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) feat[r] = 0.0f;
+#pragma unroll
+    for (int k = 0; k < 8; ++k)     // ATen order: corners sequentially, product and sum rounded separately
+#pragma unroll
+        for (int g = 0; g < 4; ++g)
+#pragma unroll
+            for (int e = 0; e < 4; ++e) feat[4 * g + e] = feat[4 * g + e] + lt.q[k][g][e] * cr.w[k];
+    return feat;
+}
+
 // LDS-DMA form of the lookups of a volume tile (in_level[tk] >= 0): 32 wave instructions park the 8 corner lines of every
 // point of the tile in the wave's own 32 KiB of LDS -- piece (k, g) at lds_wave + (4k + g) * 64 float4, lane-linear -- with
 // no VGPRs and no wait, so they can be issued a whole tile ahead.  input_tile_from_lds() finishes the job: it waits for

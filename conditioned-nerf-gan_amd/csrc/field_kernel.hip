@@ -295,8 +295,11 @@ __device__ __forceinline__ void film_all(const f32x16* y, f32x16* x, const float
 
 // Measured on one MI355X (bench.py, batch 8): parking the next tile's lookups in LDS by DMA removes 7.4 k cycles of wait
 // from layer 0 but the 32 scattered global_load_lds instructions cost 8.6 k cycles to issue in the head (~200 cycles each:
-// M0 rewrite + 32 distinct lines per instruction), a net loss of 0.5 %; only the one-tile-ahead fetch of the raw sample
-// coordinate is kept by default.
+// M0 rewrite + 32 distinct lines per instruction), a net loss of 0.5 %.  What is kept: the one-tile-ahead fetch of the raw
+// sample coordinate everywhere, and, in the plain forwards on folded weights (AHEAD below), the next tile's lookups in
+// flight in registers from the head of the current tile on: +0.9 % rays/s on the same shape, results bit-identical
+// (profiles/field32_tile_phases.md, which also records what was measured and NOT kept: a weight ring carried across
+// matrices and tiles, with the 32 loads pinned in front of the head).
 
 template <int NT, bool HAS_RES, bool STORE, bool DROP, bool FOLD = false, int WFOLD = 0>
 __global__ __launch_bounds__(256) void field_tile_kernel(FieldArgs a) {
@@ -325,9 +328,17 @@ __global__ __launch_bounds__(256) void field_tile_kernel(FieldArgs a) {
     long long nn = 0;
     bool valid = false;
     float px = 0.f, py = 0.f, pz = 0.f;
+    // AHEAD (the plain forwards on per-image folded weights): the 32 lookups of a tile's first input tile (a volume tile:
+    // launch_field_tile) are issued one tile ahead, before the head of the previous tile, and stay in flight in registers
+    // that are free there (`y` is dead behind the last hidden matrix); layer 0 reduces them without having waited.
+    // Not for NT = 2: those instantiations run two waves per SIMD, which hide each other's lookups, and the 128 registers
+    // of the tile in flight would cost the second wave.
+    constexpr bool AHEAD = WFOLD != 0 && !HAS_RES && NT >= 4;
+    LookupTile ahead;
     if (tr.begin < tr.end) {
         point_of(tr.begin, b, nn, valid);
         tile_point(a, b, nn, valid, h, true, px, py, pz);
+        if (AHEAD) lookup_tile_issue(a, b, 0, px, py, pz, h, ahead);
     }
     for (long long tile = tr.begin; tile < tr.end; tile += tr.stride) {
         // raw sample coordinate of the next tile of this wave (this tile again at the end of the range)
@@ -362,7 +373,7 @@ __global__ __launch_bounds__(256) void field_tile_kernel(FieldArgs a) {
 #pragma unroll
         for (int t = 0; t < NT; ++t) y.v[t] = load_chan16(bias, t, h);
         for (int tk = 0; tk < a.n_in; ++tk) {
-            const f32x16 feat = input_tile(a, b, tk, px, py, pz, h);
+            const f32x16 feat = (AHEAD && tk == 0) ? lookup_tile_reduce(a, 0, ahead, px, py, pz) : input_tile(a, b, tk, px, py, pz, h);
             if (STORE) {
                 float* fo = a.act_feat + gpt * (32 * a.n_in) + 32 * tk + 4 * h;
 #pragma unroll
@@ -443,9 +454,11 @@ __global__ __launch_bounds__(256) void field_tile_kernel(FieldArgs a) {
             }
         }
 
-        // ---- next tile: finish its position, send its lookups off; they land under the head and the loop overhead ----------
+        // ---- next tile: finish its position; AHEAD: send its lookups off (image nb), they land under the head, the loop
+        // overhead and the start of layer 0.  At the end of the range (nb, nnn) is this tile again: loads in bounds, never used.
         float nx, ny, nz;
         tile_point_finish(a, nb, nnn, raw_next, nvalid, h, has_next, nx, ny, nz);
+        if (AHEAD) lookup_tile_issue(a, nb, 0, nx, ny, nz, h, ahead);
 
         // ---- head: 4 outputs on the 4x4x1 MFMA (16 blocks of 4 points), see pack_head_kernel -------------------------------
         {
