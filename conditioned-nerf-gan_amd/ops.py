@@ -556,6 +556,22 @@ def _backward_setup(net, cfg, levels, B, dev):
                            sat=torch.zeros(1, dtype=torch.int32, device=dev) if bprec == "fp16" else None)
 
 
+def merge_composite_backward(cfg, coarse_rgb_sigma, coarse_z, fine_rgb_sigma, fine_z, eps_final, grad_pixels, grad_depth):
+    """Step 1 of the backward on its own (cnerf_merge_composite_backward): d loss / d pixels (B,3,R,R) and d loss / d depth (B,R,R), or
+    None -> d loss / d rgb_sigma of the coarse and of the fine samples, each (B,P,S,4); the fine one is None when cfg is not hierarchical
+    (the fine tensors are then ignored).  eps_final (B,P,n): the injected density noise of the final composite, None for none."""
+    hier = bool(cfg.flags & L.F_HIERARCHICAL)
+    c_rs, c_z, grad_pixels = _f32(coarse_rgb_sigma), _f32(coarse_z), _f32(grad_pixels)
+    f_rs, f_z = (_f32(fine_rgb_sigma), _f32(fine_z)) if hier else (None, None)
+    eps_final, grad_depth = _f32(eps_final), _f32(grad_depth)
+    gc = torch.empty_like(c_rs)
+    gf = torch.empty_like(f_rs) if hier else None
+    L.check(L.lib().cnerf_merge_composite_backward(C.byref(cfg), L.ptr(c_rs), L.ptr(c_z), L.ptr(f_rs), L.ptr(f_z), L.ptr(eps_final),
+                                                   L.ptr(grad_pixels), L.ptr(grad_depth), L.ptr(gc), L.ptr(gf), _stream()),
+            "cnerf_merge_composite_backward")
+    return gc, gf
+
+
 def render_backward(net, o, levels, freq, phase, cam2world, rng, saved, grad_pixels, grad_depth, act16=None):
     """Gradients of one render w.r.t. (channel-last feature volumes, freq, phase, [field parameters]): ONE call into the library
     (cnerf_render_backward); the exact fp32 backward of the per-point FiLM family finishes its mapping-MLP gradients with library
@@ -574,13 +590,8 @@ def render_backward(net, o, levels, freq, phase, cam2world, rng, saved, grad_pix
     grad_pixels = _f32(grad_pixels)
     grad_depth = _f32(grad_depth) if grad_depth is not None else None
     if pfilm32:
-        gc = torch.empty_like(c_rs)
-        gf = torch.empty_like(f_rs) if hier else None
-        eps_final = _f32(rng.get("eps_final")) if o["noise_std"] != 0 else None
-        L.check(L.lib().cnerf_merge_composite_backward(C.byref(cfg), L.ptr(c_rs), L.ptr(c_z), L.ptr(f_rs) if hier else None,
-                                                       L.ptr(f_z) if hier else None, L.ptr(eps_final), L.ptr(grad_pixels),
-                                                       L.ptr(grad_depth), L.ptr(gc), L.ptr(gf) if hier else None, _stream()),
-                "cnerf_merge_composite_backward")
+        eps_final = rng.get("eps_final") if o["noise_std"] != 0 else None
+        gc, gf = merge_composite_backward(cfg, c_rs, c_z, f_rs if hier else None, f_z if hier else None, eps_final, grad_pixels, grad_depth)
         return _pfilm_backward(net, o, cfg, levels, cam2world, rng, saved, gc, gf)
     w = _backward_setup(net, cfg, levels, B, dev)
     nb, ws_bytes = backward_chunk(cfg, w.code, B, act16 is not None, dev)

@@ -135,3 +135,54 @@ def accuracy_vs_fp64(hip_rgb_sigma, ref_rgb_sigma, exact_rgb_sigma) -> Dict[str,
     ex = _np(exact_rgb_sigma).reshape(_np(ref_rgb_sigma).shape)
     h, r = rgb_sigma_err(hip_rgb_sigma, ex), rgb_sigma_err(ref_rgb_sigma, ex)
     return {"hip_vs_fp64": h, "ref_vs_fp64": r, "ratio": h / max(r, 1e-30)}
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# inverse-CDF resampling: decisions next to a cdf entry, conditioning of a bin
+# ---------------------------------------------------------------------------------------------------------------------
+def flips_outside_band(cdf, u, mine, ref, band):
+    """(number of draws whose bin index differs from the reference's although u is further than `band` from every cdf entry,
+    fraction of all draws whose index differs)."""
+    bad = mine != ref
+    robust = (np.abs(u[..., :, None] - cdf[..., None, :]) > band).all(-1)
+    return int((bad & robust).sum()), float(bad.mean())
+
+
+def bin_mass(cdf, inds):
+    """cdf[above] - cdf[below] of each draw: the denominator of the inverse-CDF interpolation.  Where it is tiny the
+    interpolated depth is ill-conditioned: a 1-ulp change of a cdf entry (the reference's own fp32 `sum` changes by
+    that much between AVX2 and AVX-512 hosts) moves the depth by ulp/den of a bin width."""
+    S = cdf.shape[-1] + 1
+    below = np.clip(inds.astype(np.int64) - 1, 0, None)
+    above = np.clip(inds.astype(np.int64), None, S - 2)
+    return np.take_along_axis(cdf, above, -1) - np.take_along_axis(cdf, below, -1)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# backward tests: an upstream gradient of its own for every output, concentrated fine depths
+# ---------------------------------------------------------------------------------------------------------------------
+def random_weight_loss(B, R, seed=7):
+    """(pixels * Wp).sum() / Wp.numel() + (depth * Wd).sum() / Wd.numel() with seeded Wp, Wd ~ N(0,1): every pixel and every ray's depth
+    gets an upstream gradient of its own (pixels.square().mean() + depth.mean() gives all depths the same one and ties d/d pixels to the
+    image)."""
+    gen = torch.Generator().manual_seed(seed)
+    Wp, Wd = torch.randn(B, 3, R, R, generator=gen), torch.randn(B, R, R, generator=gen)
+
+    def loss(px, dp):
+        return (px * Wp.to(px)).sum() / Wp.numel() + (dp * Wd.to(dp)).sum() / Wd.numel()
+    return loss
+
+
+def slab_depths(B, P, S, seed=5):
+    """Fine depths as importance sampling on a trained surface leaves them: every ray's S samples inside [1.00, 1.02], i.e. all 64 x S
+    samples of a pixel patch in one or two depth bins of the sorted scatter (dozens of back-to-back 256-point batches, the 512-entry
+    ring index wrapping many times); one ray with all depths equal, one ray 0.2 in front of ray_start and one 0.2 behind ray_end
+    (depth_bin clamps them to the first and the last bin)."""
+    def forced(resampled):
+        assert resampled.shape == (B, P, S)
+        z = 1.00 + 0.02 * torch.rand(B, P, S, generator=torch.Generator().manual_seed(seed))
+        z[0, 1] = z[0, 1, 0]
+        z[0, 2] = 0.25 - 0.2
+        z[B - 1, P - 2] = 1.95 + 0.2
+        return z
+    return forced

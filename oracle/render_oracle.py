@@ -294,11 +294,12 @@ def importance_depths(z: torch.Tensor, weights: torch.Tensor, u_fine: torch.Tens
 # ---------------------------------------------------------------------------------------
 # a13  merge by depth                     (generators.py:162-167)
 # ---------------------------------------------------------------------------------------
-def merge_by_depth(fine_out, coarse_out, fine_z, coarse_z):
-    """Concatenate [fine, coarse] and sort ascending by z.  Returns (all_out, all_z, sort_idx)."""
+def merge_by_depth(fine_out, coarse_out, fine_z, coarse_z, stable=False):
+    """Concatenate [fine, coarse] and sort ascending by z.  Returns (all_out, all_z, sort_idx).  stable=True (tests that plant equal
+    depths): ties keep their order in cat[fine, coarse]; the reference's own sort leaves it open."""
     all_out = torch.cat([fine_out, coarse_out], -2)
     all_z = torch.cat([fine_z, coarse_z], -1)
-    all_z_sorted, idx = torch.sort(all_z, dim=-1)
+    all_z_sorted, idx = torch.sort(all_z, dim=-1, stable=stable)
     all_out = torch.gather(all_out, -2, idx.unsqueeze(-1).expand(-1, -1, -1, 4))
     return all_out, all_z_sorted, idx
 

@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 import torch
 
+from oracle.checks import bin_mass, flips_outside_band, random_weight_loss, slab_depths
 from conftest import GOLDEN_NAMES as ALL_GOLDEN, SMALL_GOLDEN as ALL_SMALL, DROP_GOLDEN, NOT_ON_GPU_YET, NO_BACKWARD_YET, scaled_err
 
 GOLDEN_NAMES = [n for n in ALL_GOLDEN if n not in NOT_ON_GPU_YET]
@@ -212,22 +213,6 @@ def test_composite_stage(golden, dev, name):
                                            G(eps, dev).reshape(B * P, S) if eps is not None else None, m["noise"], m["clamp"])
     assert scaled_err(w.cpu().numpy().reshape(B, P, S), g["coarse_weights"]) < 1e-5
     assert torch.all(w.sum(-1) <= 1 + 1e-5)
-
-
-def flips_outside_band(cdf, u, mine, ref, band):
-    bad = mine != ref
-    robust = (np.abs(u[..., :, None] - cdf[..., None, :]) > band).all(-1)
-    return int((bad & robust).sum()), float(bad.mean())
-
-
-def bin_mass(cdf, inds):
-    """cdf[above] - cdf[below] of each draw: the denominator of the inverse-CDF interpolation.  Where it is tiny the
-    interpolated depth is ill-conditioned: a 1-ulp change of a cdf entry (the reference's own fp32 `sum` changes by
-    that much between AVX2 and AVX-512 hosts) moves the depth by ulp/den of a bin width."""
-    S = cdf.shape[-1] + 1
-    below = np.clip(inds.astype(np.int64) - 1, 0, None)
-    above = np.clip(inds.astype(np.int64), None, S - 2)
-    return np.take_along_axis(cdf, above, -1) - np.take_along_axis(cdf, below, -1)
 
 
 @pytest.mark.parametrize("name", SMALL_GOLDEN)
@@ -1049,7 +1034,9 @@ def test_benchmarked_shape_backward_vs_oracle_autograd(dev):
     _ragged_backward_case(dev, dict(B=1, R=128, S=64, V=64, H=256), "SHORTSIREN_FG", ("fp32", "fp16"))
 
 
-def _ragged_backward_case(dev, shape, variant, backward_precisions, drop_p=0.0):
+def _ragged_backward_case(dev, shape, variant, backward_precisions, drop_p=0.0, loss=None, fine_z=None):
+    """loss(pixels, depth) -> scalar, applied on both sides (default: pixels.square().mean() + depth.mean()); fine_z(resampled depths
+    (B,P,S) of the oracle) -> the fine depths forced on both sides instead of the oracle's own resampled ones."""
     import cnerf_amd
     from cnerf_amd.generators import ImplicitGenerator3d
     from cnerf_amd.generators.volumetric_rendering import sample_camera_positions, create_cam2world_matrix
@@ -1080,16 +1067,22 @@ def _ragged_backward_case(dev, shape, variant, backward_precisions, drop_p=0.0):
         try:
             ref = O.render(variant, params, fv_r, gl_r, c(cam), R, 49.13, 0.25, 1.95, S, True, "softplus", 0.3, True, False,
                            c(rng["u_strat"]), c(rng["eps_coarse"]), c(rng["u_fine"]), c(rng["eps_final"]),
-                           forced_fine_z=None if dtype == torch.float32 else forced, drop_p=drop_p, **drop)
+                           forced_fine_z=None if forced is None else forced.to(dtype), drop_p=drop_p, **drop)
         finally:
             torch.set_default_dtype(torch.float32)
         leaves = [fv_r] + ([gl_r] if has_glob else []) + list(params.values())
-        grads = torch.autograd.grad(ref.pixels.square().mean() + ref.depth.mean(), leaves)
+        grads = torch.autograd.grad(loss(ref.pixels, ref.depth), leaves)
         names = ["feature_volume"] + (["global_feature"] if has_glob else []) + list(params.keys())
         return ref, {k: v.float().numpy() for k, v in zip(names, grads)}
 
+    if loss is None:
+        loss = lambda px, dp: px.square().mean() + dp.mean()
     forced = None
     ref, want = oracle_grads(torch.float32)
+    if fine_z is not None:                                 # the fp32 reference at the forced depths as well
+        forced = fine_z(ref.aux["fine_z"].detach()).float()
+        assert not (forced.unsqueeze(-1) == ref.aux["coarse_z"].unsqueeze(-2)).any()      # a fine depth never equals a coarse one
+        ref, want = oracle_grads(torch.float32)
     forced = ref.aux["fine_z"].detach().double()
     _, exact = oracle_grads(torch.float64)                 # same sample positions, exact arithmetic: the reference's own noise floor
     gen.to(dev)
@@ -1104,7 +1097,7 @@ def _ragged_backward_case(dev, shape, variant, backward_precisions, drop_p=0.0):
         fv, gl = fvol.to(dev).requires_grad_(True), (glob.to(dev).requires_grad_(True) if has_glob else None)
         px, dp = gen((fv, gl) if has_glob else fv, cam.to(dev), R, 49.13, 0.25, 1.95, S, True, clamp_mode="softplus", nerf_noise=0.3,
                      white_back=True, _rng=r)
-        (px.square().mean() + dp.mean()).backward()
+        loss(px, dp).backward()
         got = {"feature_volume": fv.grad}
         if has_glob:
             got["global_feature"] = gl.grad
@@ -1116,6 +1109,34 @@ def _ragged_backward_case(dev, shape, variant, backward_precisions, drop_p=0.0):
                 assert e < max(2e-3, 2.5 * floor), (backward_precision, k, e, floor)
             else:
                 assert l2 < max(2e-3, 2.5 * rel_l2(w, exact[k])) and e < max(5e-2, 2.5 * floor), (backward_precision, k, e, l2, floor)
+
+
+@pytest.mark.parametrize("backward_precision", ["fp32", "fp16"])
+@pytest.mark.parametrize("shape", [dict(B=2, R=9, S=65, V=8, H=64), dict(B=1, R=9, S=97, V=8, H=64), dict(B=1, R=8, S=128, V=8, H=64)])
+def test_backward_above_64_samples_vs_oracle_autograd(dev, shape, backward_precision):
+    """Gradients with more than 64 samples per ray -- n = 130, 194, 256 merged samples: the third and fourth 64-lane chunk of
+    merge_composite_backward_kernel (suffix sum carried backwards across chunks, the last sample's gradient taken from the chunk that
+    holds it), and NQ = 17, 25, 32 depth quads: the second 16-quad round of scatter_sorted_kernel's fine pass (one quad holding a single
+    sample; clamped depth loads; two full rounds) on 2 x 2 patches with one-pixel slivers and on exactly one patch -- with an upstream
+    gradient of its own for every pixel and depth, against autograd through the CPU oracle; the gates of _ragged_backward_case."""
+    _ragged_backward_case(dev, shape, "SHORTSIREN_FG", backward_precision, loss=random_weight_loss(shape["B"], shape["R"]))
+
+
+@pytest.mark.parametrize("variant,shape", [("TALLSIREN", dict(B=1, R=4, S=65, V=8, H=64)), ("SHORTSIREN_FRes", dict(B=1, R=4, S=65, V=8, H=64))])
+def test_backward_above_64_samples_other_families(dev, variant, shape):
+    """The same at S = 65 for the per-point FiLM family (its exact backward calls cnerf_merge_composite_backward from Python) and for a
+    residual-block network, both backward precisions."""
+    _ragged_backward_case(dev, shape, variant, ("fp32", "fp16"), loss=random_weight_loss(shape["B"], shape["R"]))
+
+
+@pytest.mark.parametrize("backward_precision", ["fp16", "fp32"])
+@pytest.mark.parametrize("shape", [dict(B=1, R=8, S=128, V=8, H=64), dict(B=2, R=9, S=65, V=8, H=64)])
+def test_backward_concentrated_fine_depths_vs_oracle_autograd(dev, shape, backward_precision):
+    """Fine depths forced into a 0.02-deep slab (slab_depths): the fine pass of scatter_sorted_kernel (the fp16 backward) queues nearly all
+    of a patch's 64 x S samples in one or two depth bins; the fp32 backward on the same inputs; random upstream gradients; the gates of
+    _ragged_backward_case against the oracle's fp32 and float64 autograd at the same forced depths."""
+    B, R, S = shape["B"], shape["R"], shape["S"]
+    _ragged_backward_case(dev, shape, "SHORTSIREN_FG", backward_precision, loss=random_weight_loss(B, R), fine_z=slab_depths(B, R * R, S))
 
 
 def test_fancy_integration_fill_modes(dev):
@@ -1384,7 +1405,8 @@ def test_forward_replays_from_a_hip_graph(dev, precision):
     assert not torch.equal(replayed[0], eager[0])
 
 
-@pytest.mark.parametrize("shape", [dict(B=2, R=11, S=10, V=40), dict(B=3, R=37, S=23, V=12), dict(B=1, R=64, S=24, V=64)])
+@pytest.mark.parametrize("shape", [dict(B=2, R=11, S=10, V=40), dict(B=3, R=37, S=23, V=12), dict(B=1, R=64, S=24, V=64),
+                                   dict(B=1, R=11, S=72, V=40), dict(B=2, R=9, S=128, V=12)])
 @pytest.mark.parametrize("variant", ["SHORTSIREN_FG", "SHORTSIREN_FG_Pyrmd"])
 def test_sorted_patch_scatter_matches_the_chain_scatter(dev, monkeypatch, shape, variant):
     """The feature-volume gradient of the half-precision backward is added to the volume by scatter_sorted_kernel (scatter_patch.hip:
@@ -1392,7 +1414,9 @@ def test_sorted_patch_scatter_matches_the_chain_scatter(dev, monkeypatch, shape,
     stores.  CNERF_SCATTER=chain makes the chain add its tiles itself: the same addends in another
     order, so the volumes agree to fp32 summation noise.  Shapes: pixels ~3 voxels apart in a 40-voxel volume (most patches outgrow the
     8-voxel window: the direct path), ragged patches / a ragged last quad / several images in a 12-voxel volume (everything inside one
-    window, long runs), and a 64-voxel volume at 64 x 64 rays; oblique cameras; a single level and the three-level pyramid."""
+    window, long runs), and a 64-voxel volume at 64 x 64 rays; with more than 64 samples per ray (the fine pass walks its depth quads in
+    rounds of 16: a second round from S = 65 on) the direct path at 18 quads and everything inside one window at 32; oblique cameras; a
+    single level and the three-level pyramid."""
     import cnerf_amd
     from cnerf_amd.generators import ImplicitGenerator3d
     from cnerf_amd.generators.volumetric_rendering import sample_camera_positions, create_cam2world_matrix
