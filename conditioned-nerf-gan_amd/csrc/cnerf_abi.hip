@@ -28,10 +28,18 @@ int hip_fail(hipError_t e, const char* what) {
 
 size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
 
+// CNERF_F_NO_VOLUME: no feature volume, layer 0 reads the sample position
+bool no_volume(const cnerf_cfg* c) { return (c->flags & CNERF_F_NO_VOLUME) != 0; }
+
 int check_cfg(const cnerf_cfg* c, bool need_render) {
     if (!c) return fail(CNERF_EINVAL, "cfg is NULL");
     if (c->B < 1) return fail(CNERF_EINVAL, "B=%d must be >= 1", c->B);
-    if (c->C < 32 || c->C % 32 != 0 || c->C > 224) return fail(CNERF_EINVAL, "C=%d must be a multiple of 32 in [32,224]", c->C);
+    if (no_volume(c)) {
+        if (c->C != 0 || c->n_levels != 0) return fail(CNERF_EINVAL, "CNERF_F_NO_VOLUME needs C = 0 and n_levels = 0 (C=%d, n_levels=%d)", c->C, c->n_levels);
+        if (c->flags & CNERF_F_INPUT_XYZ) return fail(CNERF_EINVAL, "CNERF_F_NO_VOLUME and CNERF_F_INPUT_XYZ exclude each other");
+        if (c->L >= 1 && c->layer_kind[0] == CNERF_LAYER_PFILM)
+            return fail(CNERF_EINVAL, "CNERF_F_NO_VOLUME: per-point FiLM layers take their frequencies from a looked-up feature");
+    } else if (c->C < 32 || c->C % 32 != 0 || c->C > 224) return fail(CNERF_EINVAL, "C=%d must be a multiple of 32 in [32,224]", c->C);
     if (c->n_levels < 0 || c->n_levels > CNERF_MAX_LEVELS) return fail(CNERF_EINVAL, "n_levels=%d out of range", c->n_levels);
     if (c->n_levels > 1 || (c->n_levels == 1 && (c->level_V[0] != c->V || c->level_C[0] != c->C))) {
         int sum = 0;
@@ -43,7 +51,7 @@ int check_cfg(const cnerf_cfg* c, bool need_render) {
         if (sum != c->C) return fail(CNERF_EINVAL, "sum of level_C (%d) != C (%d)", sum, c->C);
     }
     if (c->H != 64 && c->H != 128 && c->H != 256) return fail(CNERF_EINVAL, "H=%d must be 64, 128 or 256", c->H);
-    if (c->V < 2 || c->V > 1024) return fail(CNERF_EINVAL, "V=%d out of range [2,1024]", c->V);
+    if (!no_volume(c) && (c->V < 2 || c->V > 1024)) return fail(CNERF_EINVAL, "V=%d out of range [2,1024]", c->V);
     if (c->L < 1 || c->L > CNERF_MAX_LAYERS) return fail(CNERF_EINVAL, "L=%d out of range [1,%d]", c->L, CNERF_MAX_LAYERS);
     for (int l = 0; l < c->L; ++l) {
         const int k = c->layer_kind[l];
@@ -66,7 +74,7 @@ int check_cfg(const cnerf_cfg* c, bool need_render) {
     return CNERF_OK;
 }
 
-int n_levels_of(const cnerf_cfg* c) { return c->n_levels > 0 ? c->n_levels : 1; }
+int n_levels_of(const cnerf_cfg* c) { return c->n_levels > 0 ? c->n_levels : (no_volume(c) ? 0 : 1); }
 int level_V_of(const cnerf_cfg* c, int i) { return c->n_levels > 0 ? c->level_V[i] : c->V; }
 int level_C_of(const cnerf_cfg* c, int i) { return c->n_levels > 0 ? c->level_C[i] : c->C; }
 // floats of one image's volume level i (V^3 C, channel-last)
@@ -89,7 +97,7 @@ NetCounts counts_of(const cnerf_cfg* c) {
         n.n_film += c->layer_kind[l] == CNERF_LAYER_FILM;
         n.n_drop += c->layer_kind[l] != CNERF_LAYER_RES;
     }
-    if (c->layer_kind[0] != CNERF_LAYER_PFILM) {      // (per-point FiLM: layer 0 reads the sample position)
+    if (c->layer_kind[0] != CNERF_LAYER_PFILM && !no_volume(c)) {      // (per-point FiLM, no volume: layer 0 reads the sample position)
         n.n_in = c->C / 32 + ((c->flags & CNERF_F_INPUT_XYZ) ? 1 : 0);
         n.k0 = c->C + ((c->flags & CNERF_F_INPUT_XYZ) ? 3 : 0);
     }
@@ -167,7 +175,7 @@ int fill_field_args(FieldArgs& a, const cnerf_cfg* c, const cnerf_volumes* vols,
     memset(&a, 0, sizeof(a));
     const PackedLayout pl = packed_layout(c);
     const NetCounts nc = counts_of(c);
-    if (!vols) return fail(CNERF_EINVAL, "volumes are NULL");
+    if (!vols && !no_volume(c)) return fail(CNERF_EINVAL, "volumes are NULL");
     int tk = 0;
     for (int i = 0; i < n_levels_of(c); ++i) {
         const int C = level_C_of(c, i);
@@ -183,7 +191,7 @@ int fill_field_args(FieldArgs& a, const cnerf_cfg* c, const cnerf_volumes* vols,
             a.in_chan[tk] = cc;
         }
     }
-    if (c->flags & CNERF_F_INPUT_XYZ) {
+    if (c->flags & (CNERF_F_INPUT_XYZ | CNERF_F_NO_VOLUME)) {      // (no volume: the xyz tile is the only one)
         if (tk >= 8) return fail(CNERF_EINVAL, "more than 8 input tiles");
         a.in_level[tk] = -1;
         a.in_chan[tk] = 0;
@@ -538,6 +546,7 @@ int cnerf_gather_features(const cnerf_cfg* cfg, const float* fvol_cl, const floa
                           float* feat, void* stream) {
     g_err[0] = 0;
     if (int rc = check_cfg(cfg, false)) return rc;
+    if (no_volume(cfg)) return fail(CNERF_EINVAL, "gather_features: CNERF_F_NO_VOLUME networks look nothing up");
     if (!fvol_cl || !points || !feat || n_per_image < 1) return fail(CNERF_EINVAL, "gather_features: bad argument");
     if (cfg->C != 32 || cfg->n_levels > 1) return fail(CNERF_EINVAL, "gather_features: single 32-channel volume only");
     GatherArgs a{fvol_cl, points, feat, (long long)n_per_image, cfg->B, cfg->V, cfg->C, cfg->voxel_length / 2.0f};
@@ -561,6 +570,7 @@ int cnerf_scatter_features(const cnerf_cfg* cfg, const float* points, int64_t n_
                            float* grad_fvol_cl, void* stream) {
     g_err[0] = 0;
     if (int rc = check_cfg(cfg, false)) return rc;
+    if (no_volume(cfg)) return fail(CNERF_EINVAL, "scatter_features: CNERF_F_NO_VOLUME networks have no volume to scatter into");
     if (!grad_fvol_cl || !points || !grad_feat || n_per_image < 1) return fail(CNERF_EINVAL, "scatter_features: bad argument");
     if (cfg->C != 32 || cfg->n_levels > 1) return fail(CNERF_EINVAL, "scatter_features: single 32-channel volume only");
     GatherArgs a{nullptr, points, nullptr, (long long)n_per_image, cfg->B, cfg->V, cfg->C, cfg->voxel_length / 2.0f};
@@ -572,7 +582,7 @@ int cnerf_field_forward(const cnerf_cfg* cfg, const cnerf_volumes* vols, const f
                         const float* phase, const float* points, int64_t n_per_image, float* rgb_sigma, void* stream) {
     g_err[0] = 0;
     if (int rc = check_cfg(cfg, false)) return rc;
-    if (!vols || !packed || !points || !rgb_sigma || n_per_image < 1) return fail(CNERF_EINVAL, "field_forward: bad argument");
+    if ((!vols && !no_volume(cfg)) || !packed || !points || !rgb_sigma || n_per_image < 1) return fail(CNERF_EINVAL, "field_forward: bad argument");
     if (counts_of(cfg).n_film && (!freq || !phase)) return fail(CNERF_EINVAL, "field_forward: FiLM layers need freq and phase");
     FieldArgs a;
     if (int rc = points_args(a, cfg, vols, nullptr, packed, freq, phase, points, 0, cfg->B, n_per_image, nullptr)) return rc;
@@ -604,7 +614,7 @@ int cnerf_render_forward(const cnerf_cfg* cfg, const cnerf_volumes* vols, const 
                          float* depth, const cnerf_aux* aux, void* workspace, void* stream_) {
     g_err[0] = 0;
     if (int rc = check_cfg(cfg, true)) return rc;
-    if (!vols || !packed || !cam2world || !pixels || !depth || !workspace) return fail(CNERF_EINVAL, "render_forward: NULL argument");
+    if ((!vols && !no_volume(cfg)) || !packed || !cam2world || !pixels || !depth || !workspace) return fail(CNERF_EINVAL, "render_forward: NULL argument");
     if (counts_of(cfg).n_film && (!freq || !phase)) return fail(CNERF_EINVAL, "render_forward: FiLM layers need freq and phase");
     const bool hier = cfg->flags & CNERF_F_HIERARCHICAL;
     rng = rng_or_none(rng);
@@ -725,7 +735,7 @@ int cnerf_backward_bytes(const cnerf_cfg* cfg, size_t* packed_t) {
     const NetCounts nc = counts_of(cfg);
     const size_t NT = cfg->H / 32, tile = 4 * 64 * 4;
     size_t fl = NT * 2 * 64 + (size_t)(nc.n_mats - 1) * NT * NT * tile;     // head^T, the matrices after layer 0
-    if (cfg->layer_kind[0] != CNERF_LAYER_PFILM)             // (per-point FiLM: layer 0 reads the sample position, no gradient)
+    if (cfg->layer_kind[0] != CNERF_LAYER_PFILM && !no_volume(cfg))   // (per-point FiLM, no volume: the chain stops at layer 0's pre-activation)
         fl += (size_t)nc.n_in * NT * tile;                   // layer 0 transposed: one 32-row output tile per input tile
     if (packed_t) *packed_t = align256(fl * sizeof(float));
     return CNERF_OK;
@@ -752,7 +762,7 @@ int cnerf_pack_field_transposed(const cnerf_cfg* cfg, const cnerf_field_params* 
         if (hipError_t e = launch_pack_matrix_t(p->w[l], H, H, NT, dst, stream)) return hip_fail(e, "pack_matrix_t");
         dst += (size_t)NT * NT * tile;
     }
-    if (cfg->layer_kind[0] == CNERF_LAYER_PFILM) return CNERF_OK;      // head^T and W_l^T of layers L-1..1 only
+    if (cfg->layer_kind[0] == CNERF_LAYER_PFILM || no_volume(cfg)) return CNERF_OK;      // head^T and W_l^T of layers L-1..1 only
     if (!p->w[0]) return fail(CNERF_EINVAL, "pack_field_transposed: layer 0 weight is NULL");
     const NetCounts nc = counts_of(cfg);
     if (hipError_t e = launch_pack_matrix_t(p->w[0], H, nc.k0, nc.n_in, dst, stream)) return hip_fail(e, "pack_matrix_t");
@@ -787,8 +797,9 @@ int cnerf_field_backward(const cnerf_cfg* cfg, int32_t pass, int32_t image0, int
     if (pass < 0 || pass > 2) return fail(CNERF_EINVAL, "field_backward: pass must be 0 (coarse), 1 (fine) or 2 (explicit points)");
     if (cfg->layer_kind[0] == CNERF_LAYER_PFILM && cfg->precision != CNERF_PREC_FP32)
         return fail(CNERF_EINVAL, "field_backward: the per-point FiLM family's fp32 chain needs a cfg (and packed weights) of precision fp32");
-    if (!vols || !packed || !packed_t || !cam2world || !grad_rgb_sigma || !saved_rgb_sigma || !act_feat || !act_h || !act_c ||
-        !act_g || !act_go || !grad_vols)
+    const bool nv = no_volume(cfg);
+    if ((!vols && !nv) || !packed || !packed_t || !cam2world || !grad_rgb_sigma || !saved_rgb_sigma || !act_feat || !act_h || !act_c ||
+        !act_g || !act_go || (!grad_vols && !nv))
         return fail(CNERF_EINVAL, "field_backward: NULL argument");
     if (int rc = check_grad_vols(cfg, grad_vols, "field_backward")) return rc;
     if (pass == 1 && !fine_z) return fail(CNERF_EINVAL, "field_backward: the fine pass needs fine_z");
@@ -811,8 +822,9 @@ int cnerf_field_backward_points(const cnerf_cfg* cfg, const cnerf_volumes* vols,
     if (int rc = check_cfg(cfg, false)) return rc;
     if (cfg->layer_kind[0] == CNERF_LAYER_PFILM && cfg->precision != CNERF_PREC_FP32)
         return fail(CNERF_EINVAL, "field_backward_points: the per-point FiLM family's fp32 chain needs a cfg (and packed weights) of precision fp32");
-    if (!vols || !packed || !packed_t || !points || n_per_image < 1 || !grad_rgb_sigma || !saved_rgb_sigma || !act_feat || !act_h || !act_c || !act_g ||
-        !act_go || !grad_vols)
+    const bool nv = no_volume(cfg);
+    if ((!vols && !nv) || !packed || !packed_t || !points || n_per_image < 1 || !grad_rgb_sigma || !saved_rgb_sigma || !act_feat || !act_h || !act_c || !act_g ||
+        !act_go || (!grad_vols && !nv))
         return fail(CNERF_EINVAL, "field_backward_points: NULL argument");
     if (int rc = check_grad_vols(cfg, grad_vols, "field_backward_points")) return rc;
     if (counts_of(cfg).n_film && (!freq || !phase)) return fail(CNERF_EINVAL, "field_backward_points: FiLM layers need freq and phase");
@@ -1013,7 +1025,7 @@ int chunk_layout(const cnerf_cfg* c, int bprec, int cnt, size_t npi, size_t N_ou
         L.a_c = take(have_act16 ? 0 : (size_t)L.n_mats * T * NT * 2048);
         L.a_g = take((size_t)L.n_mats * T * NT * 2048);
         L.a_go = take(T * 2048);
-        L.a_gin = take(gin ? (size_t)L.n_in * n * 32 * sizeof(float) : 0);
+        L.a_gin = take(gin && !no_volume(c) ? (size_t)L.n_in * n * 32 * sizeof(float) : 0);   // (no feature tile: no rows, no patch scatter)
     } else {
         L.a_gin = 0;
         L.a_feat = take(n * 32 * L.n_in * sizeof(float));
@@ -1255,7 +1267,8 @@ int cnerf_render_backward(const cnerf_cfg* cfg, int32_t bprec, int32_t cnt_max, 
     const bool have_act16 = kept && kept->act16[0].h;
     BackwardLayout L;
     if (int rc = backward_layout(cfg, bprec, cnt_max, have_act16, L)) return rc;
-    if (!vols || !P || !packed || !packed_bwd || !cam2world || !saved || !grad_pixels || !G || !grad_vols || !workspace)
+    const bool nv = no_volume(cfg);
+    if ((!vols && !nv) || !P || !packed || !packed_bwd || !cam2world || !saved || !grad_pixels || !G || (!grad_vols && !nv) || !workspace)
         return fail(CNERF_EINVAL, "render_backward: NULL argument");
     if (int rc = check_grad_vols(cfg, grad_vols, "render_backward")) return rc;
     const bool hier = cfg->flags & CNERF_F_HIERARCHICAL;
@@ -1310,7 +1323,7 @@ int cnerf_render_backward(const cnerf_cfg* cfg, int32_t bprec, int32_t cnt_max, 
         // 128 B per point) and scatter_sorted_kernel adds them to the volume pre-reduced per pixel patch (scatter_patch.hip), or the chain
         // adds them itself (CNERF_SCATTER=chain)
         float* gin = (float*)(ws + L.a_gin);
-        const bool patch = !scatter_by_chain();
+        const bool patch = !scatter_by_chain() && !nv;      // (a network without a volume has nothing to scatter)
         // only channels 0..3 of a row are ever written: the rest must read as zero
         if (hipError_t e = hipMemsetAsync(a_go, 0, (size_t)cnt_max * tpi * 2048, stream)) return hip_fail(e, "memset");
         for (int pass = 0; pass < (hier ? 2 : 1); ++pass) {
@@ -1392,7 +1405,8 @@ int cnerf_field_query_backward(const cnerf_cfg* cfg, int32_t bprec, int64_t poin
     QueryLayout Q;
     if (int rc = query_layout(cfg, bprec, (long long)points_per_chunk, Q)) return rc;
     const BackwardLayout& L = Q.L;
-    if (!vols || !P || !packed || !packed_bwd || !points || !saved_rgb_sigma || !grad_rgb_sigma || !G || !grad_vols || !workspace || n_per_image < 1)
+    const bool nv = no_volume(cfg);
+    if ((!vols && !nv) || !P || !packed || !packed_bwd || !points || !saved_rgb_sigma || !grad_rgb_sigma || !G || (!grad_vols && !nv) || !workspace || n_per_image < 1)
         return fail(CNERF_EINVAL, "field_query_backward: NULL argument or no points");
     if (int rc = check_grad_vols(cfg, grad_vols, "field_query_backward")) return rc;
     if (counts_of(cfg).n_film && (!freq || !phase || !grad_freq || !grad_phase))
@@ -1489,7 +1503,7 @@ int cnerf_field_query_backward(const cnerf_cfg* cfg, int32_t bprec, int64_t poin
             PointsGradArgs pg = points_grad_args(cfg, vols, b, pts, grad_points + row0 * 3, np);
             pg.gfeat = rows;
             pg.ldf = 256;
-            pg.gxyz = (pfilm || (cfg->flags & CNERF_F_INPUT_XYZ)) ? rows + cfg->C : nullptr;
+            pg.gxyz = (pfilm || (cfg->flags & (CNERF_F_INPUT_XYZ | CNERF_F_NO_VOLUME))) ? rows + cfg->C : nullptr;   // (no volume: C = 0, the xyz term alone)
             pg.ldx = 256;
             if (hipError_t e = launch_points_lookup_grad(pg, stream)) return hip_fail(e, "points_lookup_grad");
         }
@@ -1501,6 +1515,7 @@ int cnerf_feature_points_grad(const cnerf_cfg* cfg, const cnerf_volumes* vols, c
                               float* grad_points, void* stream) {
     g_err[0] = 0;
     if (int rc = check_cfg(cfg, false)) return rc;
+    if (no_volume(cfg)) return fail(CNERF_EINVAL, "feature_points_grad: CNERF_F_NO_VOLUME networks look nothing up");
     if (!vols || !points || !grad_feat || !grad_points || n_per_image < 1) return fail(CNERF_EINVAL, "feature_points_grad: bad argument");
     for (int i = 0; i < n_levels_of(cfg); ++i)
         if (!vols->level[i]) return fail(CNERF_EINVAL, "feature_points_grad: volume level %d is NULL", i);

@@ -392,7 +392,7 @@ struct ResidYes { static constexpr bool value = true; };
 // One block of four waves per CU (512 registers per wave), two weight units in LDS, one barrier per unit.  (Measured in round 2
 // and not kept: four slots with a barrier per two units -- no change; two waves per SIMD by a register cap -- spills, slower; a
 // two-waves-per-tile variant of this kernel -- 11.7 vs 10.9 ms)
-template <int NT, int STORE, bool HAS_RES, int WF>
+template <int NT, int STORE, bool HAS_RES, int WF, bool NOVOL = false>
 __global__ __launch_bounds__(256) void field_h3_kernel(FieldArgs a) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     constexpr int UNIT_FR = H3Lds<NT>::FRAGS;
@@ -480,8 +480,8 @@ __global__ __launch_bounds__(256) void field_h3_kernel(FieldArgs a) {
     dma_next();
     float px, py, pz;
     tile_point(a, tp.b, tp.nn, tp.valid, h, true, px, py, pz);
-    InputTile it;
-    input_tile_issue_volume(a, tp.b, 0, px, py, pz, h, it);      // input tile 0 is a volume tile (checked by the launcher)
+    InputTile it;                                                // NOVOL: never touched -- nothing to look up, nothing in flight across tiles
+    if constexpr (!NOVOL) input_tile_issue_volume(a, tp.b, 0, px, py, pz, h, it);   // input tile 0 is a volume tile (checked by the launcher)
 
     for (long long g = gr.begin; g < gr.end; g += gr.blk_per_cls) {
         const int b = tp.b;
@@ -556,6 +556,36 @@ __global__ __launch_bounds__(256) void field_h3_kernel(FieldArgs a) {
 #pragma unroll
                     for (int r = 0; r < 16; ++r) acc0[t][r] = 0.0f;
             }
+            if constexpr (NOVOL) {
+                // The xyz tile alone, built from the position: no InputTile, no tile loop.  Columns 3..31 are compile-time zeros, so
+                // the row stores write constants and only the first K = 16 half of the weight unit is multiplied.
+                const f16x8* unit = unit_begin(Younger<0>{});
+                float fv[8];
+#pragma unroll
+                for (int r = 0; r < 8; ++r) fv[r] = 0.0f;
+                if (h == 0) {
+                    fv[0] = px;
+                    fv[1] = py;
+                    fv[2] = pz;
+                }
+                const f32x4 zero4 = f32x4{0.f, 0.f, 0.f, 0.f};
+                if (STORE == STORE_F32) {
+                    float* fo = a.act_feat + gpt * 32 + 4 * h;
+                    *reinterpret_cast<f32x4*>(fo) = f32x4{fv[0], fv[1], fv[2], 0.f};
+#pragma unroll
+                    for (int g = 1; g < 4; ++g) *reinterpret_cast<f32x4*>(fo + 8 * g) = zero4;
+                }
+                if (STORE == STORE_TB16 && st.live) {        // clamped to fp16's range like the MFMA operand
+                    _Float16* fo = reinterpret_cast<_Float16*>(a.act_feat) + ((size_t)tile_T * 32 + j) * 32 + 4 * h;
+                    float c3[3];
+#pragma unroll
+                    for (int e = 0; e < 3; ++e) c3[e] = __builtin_amdgcn_fmed3f(fv[e], -65504.0f, 65504.0f);
+                    *reinterpret_cast<u32x2_*>(fo) = u32x2_{pk_f16(c3[0], c3[1]), pk_f16(c3[2], 0.0f)};
+#pragma unroll
+                    for (int g = 1; g < 4; ++g) *reinterpret_cast<u32x2_*>(fo + 8 * g) = u32x2_{0u, 0u};
+                }
+                input_unit_k16<NT>(unit, split8_clamped(fv), acc0, lane);
+            } else
             for (int tk = 0; tk < a.n_in; ++tk) {
                 if (tk > 0) input_tile_issue(a, b, tk, px, py, pz, h, it);   // tile 0 was issued during the previous head
                 const f16x8* unit = unit_begin(Younger<0>{});      // (behind the head: the next tile's lookups are in flight and needed now)
@@ -683,7 +713,7 @@ __global__ __launch_bounds__(256) void field_h3_kernel(FieldArgs a) {
             const f16x8* unit = unit_begin(Younger<16>{});      // the last matrix' tiles NT-2 and NT-1
             float nx, ny, nz;                                   // without a next group: this tile again (harmless, keeps `it` dead above)
             tile_point_finish(a, tn.b, tn.nn, raw_next, tn.valid, h, has_next, nx, ny, nz);
-            input_tile_issue_volume(a, tn.b, 0, nx, ny, nz, h, it);
+            if constexpr (!NOVOL) input_tile_issue_volume(a, tn.b, 0, nx, ny, nz, h, it);
             f32x16 acc;
 #pragma unroll
             for (int r = 0; r < 16; ++r) acc[r] = 0.0f;
@@ -723,6 +753,7 @@ template <int NT, int STORE, bool HAS_RES, int WF>
 static hipError_t launch_h3_inst(const FieldArgs& a, hipStream_t stream) {
     const size_t lds_bytes = h3_lds_bytes<NT>(a, 2);
     if (lds_bytes > LDS_LIMIT) return hipErrorInvalidValue;
+    if (a.flags & CNERF_F_NO_VOLUME) return launch_per_cu(field_h3_kernel<NT, STORE, HAS_RES, WF, true>, a, lds_bytes, LDS_LIMIT, a, stream);
     return launch_per_cu(field_h3_kernel<NT, STORE, HAS_RES, WF>, a, lds_bytes, LDS_LIMIT, a, stream);
 }
 
@@ -743,7 +774,9 @@ static hipError_t launch_h3_nt(const FieldArgs& a, hipStream_t stream) {
 }
 
 static hipError_t field_impl(const FieldArgs& a, int H, hipStream_t stream) {
-    if (a.n_in < 1 || a.in_level[0] < 0) return hipErrorInvalidValue;      // the cross-tile lookup prefetch assumes a volume tile first
+    if (a.flags & CNERF_F_NO_VOLUME) {
+        if (a.n_in != 1 || a.in_level[0] >= 0) return hipErrorInvalidValue;   // the xyz tile alone (NOVOL instantiation: no lookup, no prefetch)
+    } else if (a.n_in < 1 || a.in_level[0] < 0) return hipErrorInvalidValue;  // the cross-tile lookup prefetch assumes a volume tile first
     // a.act_h set: activation-storing forward of the backward pass, fp32 rows or (a.act_tb16) fp16 tile blocks
     const int store = a.act_h == nullptr ? STORE_NONE : (a.act_tb16 ? STORE_TB16 : STORE_F32);
     return dispatch_nt(H, [&](auto nt) {

@@ -293,6 +293,31 @@ __device__ __forceinline__ void film_all(const f32x16* y, f32x16* x, const float
     }
 }
 
+// Layer 0 of a network without a feature volume (CNERF_F_NO_VOLUME): y[c] = acc0[c] + W0[c][0] x + W0[c][1] y + W0[c][2] z, three
+// exact fp32 fmas per channel on the vector units (3 H per point, against NT * 16 MFMAs = 32 H multiply-adds of a zero-padded
+// K = 32 tile).  The weights are read from the ordinary packed layer-0 matrix (one k-tile, so WFOLD's per-image row scaling
+// applies as it stands): row 32 t + i is the float4 of lane i (half 0), k-group 0 of output tile t -- {W[c][0], W[c][1], W[c][2], 0}.
+// A lane owns channels 32 t + 8 g + 4 h + e: sixteen 16-byte loads per tile, every lane of a half at the same address.
+template <int NT>
+__device__ __forceinline__ void layer0_xyz(const f32x4* __restrict__ wp, float px, float py, float pz, f32x16* y, int h) {
+    // The address is made opaque once per tile: on the shared weights (a.packed, the same for every tile) the 16 NT loads are
+    // loop-invariant and were hoisted out of the tile loop: weights held across the whole MLP, 512 registers and spills.
+    const f32x4* wl = wp + 4 * h;
+    asm volatile("" : "+v"(wl));
+#pragma unroll
+    for (int t = 0; t < NT; ++t) {
+#pragma unroll
+        for (int g = 0; g < 4; ++g) {
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                const f32x4 w = wl[(size_t)(t * 4) * 64 + 8 * g + e];
+                y[t][4 * g + e] = __builtin_fmaf(w[2], pz, __builtin_fmaf(w[1], py, __builtin_fmaf(w[0], px, y[t][4 * g + e])));
+            }
+            __builtin_amdgcn_sched_barrier(0);      // four loads in flight at a time: 16 registers, not 64 * NT
+        }
+    }
+}
+
 // Measured on one MI355X (bench.py, batch 8): parking the next tile's lookups in LDS by DMA removes 7.4 k cycles of wait
 // from layer 0 but the 32 scattered global_load_lds instructions cost 8.6 k cycles to issue in the head (~200 cycles each:
 // M0 rewrite + 32 distinct lines per instruction), a net loss of 0.5 %.  What is kept: the one-tile-ahead fetch of the raw
@@ -301,7 +326,9 @@ __device__ __forceinline__ void film_all(const f32x16* y, f32x16* x, const float
 // (profiles/field32_tile_phases.md, which also records what was measured and NOT kept: a weight ring carried across
 // matrices and tiles, with the 32 loads pinned in front of the head).
 
-template <int NT, bool HAS_RES, bool STORE, bool DROP, bool FOLD = false, int WFOLD = 0>
+// NOVOL (CNERF_F_NO_VOLUME): no lookup at all -- no corner addresses, nothing in flight across tiles; per tile the ray set-up, the
+// position, layer0_xyz and the MLP.
+template <int NT, bool HAS_RES, bool STORE, bool DROP, bool FOLD = false, int WFOLD = 0, bool NOVOL = false>
 __global__ __launch_bounds__(256) void field_tile_kernel(FieldArgs a) {
     const int lane = threadIdx.x & 63;
     const int j = lane & 31, h = lane >> 5;
@@ -333,12 +360,12 @@ __global__ __launch_bounds__(256) void field_tile_kernel(FieldArgs a) {
     // that are free there (`y` is dead behind the last hidden matrix); layer 0 reduces them without having waited.
     // Not for NT = 2: those instantiations run two waves per SIMD, which hide each other's lookups, and the 128 registers
     // of the tile in flight would cost the second wave.
-    constexpr bool AHEAD = WFOLD != 0 && !HAS_RES && NT >= 4;
+    constexpr bool AHEAD = WFOLD != 0 && !HAS_RES && NT >= 4 && !NOVOL;
     LookupTile ahead;
     if (tr.begin < tr.end) {
         point_of(tr.begin, b, nn, valid);
         tile_point(a, b, nn, valid, h, true, px, py, pz);
-        if (AHEAD) lookup_tile_issue(a, b, 0, px, py, pz, h, ahead);
+        if constexpr (AHEAD) lookup_tile_issue(a, b, 0, px, py, pz, h, ahead);
     }
     for (long long tile = tr.begin; tile < tr.end; tile += tr.stride) {
         // raw sample coordinate of the next tile of this wave (this tile again at the end of the range)
@@ -370,8 +397,17 @@ __global__ __launch_bounds__(256) void field_tile_kernel(FieldArgs a) {
         const float* freq = FOLD ? a.fold + (size_t)(b + a.image0) * fold_stride : (a.freq ? a.freq + (size_t)b * a.film_stride : nullptr);
         const float* phase = FOLD ? freq + 2 * fold_n : (a.phase ? a.phase + (size_t)b * a.film_stride : nullptr);
         const float* fml = FOLD ? freq + fold_n : nullptr;
+        if constexpr (NOVOL && STORE) {       // the zero-padded xyz tile (n, 32): layer 0's input as cnerf_weight_grad reads it
+            float* fo = a.act_feat + gpt * 32 + 4 * h;
+            *reinterpret_cast<f32x4*>(fo) = h == 0 ? f32x4{px, py, pz, 0.f} : f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+            for (int g = 1; g < 4; ++g) *reinterpret_cast<f32x4*>(fo + 8 * g) = f32x4{0.f, 0.f, 0.f, 0.f};
+        }
 #pragma unroll
         for (int t = 0; t < NT; ++t) y.v[t] = load_chan16(bias, t, h);
+        if constexpr (NOVOL) {
+            layer0_xyz<NT>(wp, px, py, pz, y.v, h);
+        } else
         for (int tk = 0; tk < a.n_in; ++tk) {
             const f32x16 feat = (AHEAD && tk == 0) ? lookup_tile_reduce(a, 0, ahead, px, py, pz) : input_tile(a, b, tk, px, py, pz, h);
             if (STORE) {
@@ -458,7 +494,7 @@ __global__ __launch_bounds__(256) void field_tile_kernel(FieldArgs a) {
         // overhead and the start of layer 0.  At the end of the range (nb, nnn) is this tile again: loads in bounds, never used.
         float nx, ny, nz;
         tile_point_finish(a, nb, nnn, raw_next, nvalid, h, has_next, nx, ny, nz);
-        if (AHEAD) lookup_tile_issue(a, nb, 0, nx, ny, nz, h, ahead);
+        if constexpr (AHEAD) lookup_tile_issue(a, nb, 0, nx, ny, nz, h, ahead);
 
         // ---- head: 4 outputs on the 4x4x1 MFMA (16 blocks of 4 points), see pack_head_kernel -------------------------------
         {
@@ -808,7 +844,9 @@ __global__ __launch_bounds__(256) void field_pw_backward_kernel(FieldArgs a) {
     }
 }
 
-template <int NT, bool HAS_RES>
+// NOVOL (CNERF_F_NO_VOLUME): the chain stops at layer 0's pre-activation gradient -- no transposed layer-0 product, no scatter, no LDS
+// (the three arrays below are not referenced and take no space).
+template <int NT, bool HAS_RES, bool NOVOL = false>
 __global__ __launch_bounds__(256) void field_backward_kernel(FieldArgs a) {
     __shared__ float s_g[4][32][33];     // per wave: g_feat [point][channel] (padded)
     __shared__ int s_base[4][32][8];
@@ -873,42 +911,44 @@ __global__ __launch_bounds__(256) void field_backward_kernel(FieldArgs a) {
             }
         }
         // ---- layer 0: one 32-channel gradient tile per input tile; feature tiles are scattered, the xyz tile is dropped ----
-        float px, py, pz;
-        tile_point(a, b, nn, valid, h, false, px, py, pz);
-        const int ch = lane & 31;
-        for (int tk = 0; tk < a.n_in; ++tk) {
-            const int lvl = a.in_level[tk];
-            if (lvl < 0) continue;                              // no gradient flows to the sample positions
-            f32x16 gfeat;
-            bwd_matrix<1, NT>(wp + (size_t)tk * NT * TILE4, g.v, &gfeat, lane);
-            const int V = a.lvl_V[lvl], C = a.lvl_C[lvl];
-            Corner8 cr;
-            trilinear_corners(px, py, pz, a.half_voxel, V, cr);
+        if constexpr (!NOVOL) {
+            float px, py, pz;
+            tile_point(a, b, nn, valid, h, false, px, py, pz);
+            const int ch = lane & 31;
+            for (int tk = 0; tk < a.n_in; ++tk) {
+                const int lvl = a.in_level[tk];
+                if (lvl < 0) continue;                              // no gradient flows to the sample positions
+                f32x16 gfeat;
+                bwd_matrix<1, NT>(wp + (size_t)tk * NT * TILE4, g.v, &gfeat, lane);
+                const int V = a.lvl_V[lvl], C = a.lvl_C[lvl];
+                Corner8 cr;
+                trilinear_corners(px, py, pz, a.half_voxel, V, cr);
 #pragma unroll
-            for (int gq = 0; gq < 4; ++gq)
+                for (int gq = 0; gq < 4; ++gq)
 #pragma unroll
-                for (int e = 0; e < 4; ++e) s_g[wv][j][8 * gq + 4 * h + e] = gfeat[4 * gq + e];
-            if (h == 0) {
+                    for (int e = 0; e < 4; ++e) s_g[wv][j][8 * gq + 4 * h + e] = gfeat[4 * gq + e];
+                if (h == 0) {
 #pragma unroll
-                for (int k = 0; k < 8; ++k) {
-                    s_base[wv][j][k] = cr.base[k];
-                    s_w[wv][j][k] = valid ? cr.w[k] : 0.0f;
+                    for (int k = 0; k < 8; ++k) {
+                        s_base[wv][j][k] = cr.base[k];
+                        s_w[wv][j][k] = valid ? cr.w[k] : 0.0f;
+                    }
                 }
-            }
-            __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-            __builtin_amdgcn_wave_barrier();
-            float* gv = a.lvl_grad[lvl] + (size_t)b * V * V * V * C + a.in_chan[tk];
-            for (int pp = 0; pp < 16; ++pp) {
-                const int p = 2 * pp + h;                      // two points per wave instruction, 32 channels each
-                const float gval = s_g[wv][p][ch];
+                __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+                __builtin_amdgcn_wave_barrier();
+                float* gv = a.lvl_grad[lvl] + (size_t)b * V * V * V * C + a.in_chan[tk];
+                for (int pp = 0; pp < 16; ++pp) {
+                    const int p = 2 * pp + h;                      // two points per wave instruction, 32 channels each
+                    const float gval = s_g[wv][p][ch];
 #pragma unroll
-                for (int k = 0; k < 8; ++k) {
-                    const float wk = s_w[wv][p][k];
-                    if (wk != 0.0f) atomicAdd(gv + (size_t)s_base[wv][p][k] * C + ch, gval * wk);
+                    for (int k = 0; k < 8; ++k) {
+                        const float wk = s_w[wv][p][k];
+                        if (wk != 0.0f) atomicAdd(gv + (size_t)s_base[wv][p][k] * C + ch, gval * wk);
+                    }
                 }
+                __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+                __builtin_amdgcn_wave_barrier();
             }
-            __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-            __builtin_amdgcn_wave_barrier();
         }
     }
 }
@@ -1069,17 +1109,26 @@ static int field_grid(const void* kernel, long long total_tiles) {
     return (blocks + 7) / 8 * 8;
 }
 
-template <int NT, bool HAS_RES>
-static hipError_t launch_field_backward_nt(const FieldArgs& a, hipStream_t stream) {
-    const int blocks = field_grid((const void*)field_backward_kernel<NT, HAS_RES>, a.total_tiles);
-    hipLaunchKernelGGL((field_backward_kernel<NT, HAS_RES>), dim3(blocks), dim3(256), 0, stream, a);
-    return hipGetLastError();
-}
-
 static bool has_res(const FieldArgs& a) {
     bool res = false;
     for (int l = 0; l < a.L; ++l) res |= a.layer_kind[l] == CNERF_LAYER_RES;
     return res;
+}
+
+template <int NT, bool HAS_RES, bool NOVOL = false>
+static hipError_t launch_field_backward_nt(const FieldArgs& a, hipStream_t stream) {
+    const int blocks = field_grid((const void*)field_backward_kernel<NT, HAS_RES, NOVOL>, a.total_tiles);
+    hipLaunchKernelGGL((field_backward_kernel<NT, HAS_RES, NOVOL>), dim3(blocks), dim3(256), 0, stream, a);
+    return hipGetLastError();
+}
+
+// a network without a feature volume (CNERF_F_NO_VOLUME): the xyz tile is its only input tile
+static bool no_volume(const FieldArgs& a) { return (a.flags & CNERF_F_NO_VOLUME) != 0; }
+
+template <int NT>
+static hipError_t launch_field_backward_res(const FieldArgs& a, hipStream_t stream) {
+    if (no_volume(a)) return has_res(a) ? launch_field_backward_nt<NT, true, true>(a, stream) : launch_field_backward_nt<NT, false, true>(a, stream);
+    return has_res(a) ? launch_field_backward_nt<NT, true>(a, stream) : launch_field_backward_nt<NT, false>(a, stream);
 }
 
 template <int NT>
@@ -1098,34 +1147,42 @@ hipError_t launch_field_backward(const FieldArgs& a, int H, hipStream_t stream) 
             default: return hipErrorInvalidValue;
         }
     }
-    const bool res = has_res(a);
     switch (H / 32) {
-        case 2: return res ? launch_field_backward_nt<2, true>(a, stream) : launch_field_backward_nt<2, false>(a, stream);
-        case 4: return res ? launch_field_backward_nt<4, true>(a, stream) : launch_field_backward_nt<4, false>(a, stream);
-        case 8: return res ? launch_field_backward_nt<8, true>(a, stream) : launch_field_backward_nt<8, false>(a, stream);
+        case 2: return launch_field_backward_res<2>(a, stream);
+        case 4: return launch_field_backward_res<4>(a, stream);
+        case 8: return launch_field_backward_res<8>(a, stream);
         default: return hipErrorInvalidValue;
     }
 }
 
-template <int NT, bool HAS_RES, bool STORE, bool DROP, bool FOLD = false, int WFOLD = 0>
+template <int NT, bool HAS_RES, bool STORE, bool DROP, bool FOLD = false, int WFOLD = 0, bool NOVOL = false>
 static hipError_t launch_field_tile(const FieldArgs& a, hipStream_t stream) {
-    if (a.n_in < 1 || a.in_level[0] < 0) return hipErrorInvalidValue;      // the lookup prefetch assumes a volume tile first
-    const int blocks = field_grid((const void*)field_tile_kernel<NT, HAS_RES, STORE, DROP, FOLD, WFOLD>, a.total_tiles);
-    hipLaunchKernelGGL((field_tile_kernel<NT, HAS_RES, STORE, DROP, FOLD, WFOLD>), dim3(blocks), dim3(256), 0, stream, a);
+    if (NOVOL) {
+        if (a.n_in != 1 || a.in_level[0] >= 0) return hipErrorInvalidValue;   // the xyz tile alone
+    } else if (a.n_in < 1 || a.in_level[0] < 0) return hipErrorInvalidValue;  // the lookup prefetch assumes a volume tile first
+    const int blocks = field_grid((const void*)field_tile_kernel<NT, HAS_RES, STORE, DROP, FOLD, WFOLD, NOVOL>, a.total_tiles);
+    hipLaunchKernelGGL((field_tile_kernel<NT, HAS_RES, STORE, DROP, FOLD, WFOLD, NOVOL>), dim3(blocks), dim3(256), 0, stream, a);
     return hipGetLastError();
 }
 
-template <int NT, bool HAS_RES>
+template <int NT, bool HAS_RES, bool NOVOL = false>
 static hipError_t launch_field_nt(const FieldArgs& a, hipStream_t stream) {
     // a.act_h set: activation-storing forward of the backward pass; a.drop_scale != 0: dropout (training mode)
     if (a.drop_scale != 0.0f)
-        return a.act_h ? launch_field_tile<NT, HAS_RES, true, true>(a, stream) : launch_field_tile<NT, HAS_RES, false, true>(a, stream);
+        return a.act_h ? launch_field_tile<NT, HAS_RES, true, true, false, 0, NOVOL>(a, stream) : launch_field_tile<NT, HAS_RES, false, true, false, 0, NOVOL>(a, stream);
     if (a.fold && a.packed_img && !a.act_h) {      // (which reduction in front of v_sin: wfolded_sine above)
-        if constexpr (HAS_RES) return launch_field_tile<NT, true, false, false, true, 2>(a, stream);
-        else return a.freq ? launch_field_tile<NT, false, false, false, true, 1>(a, stream) : launch_field_tile<NT, false, false, false, true, 2>(a, stream);
+        if constexpr (HAS_RES) return launch_field_tile<NT, true, false, false, true, 2, NOVOL>(a, stream);
+        else return a.freq ? launch_field_tile<NT, false, false, false, true, 1, NOVOL>(a, stream) : launch_field_tile<NT, false, false, false, true, 2, NOVOL>(a, stream);
     }
-    if (a.fold && !a.act_h) return launch_field_tile<NT, HAS_RES, false, false, true>(a, stream);
-    return a.act_h ? launch_field_tile<NT, HAS_RES, true, false>(a, stream) : launch_field_tile<NT, HAS_RES, false, false>(a, stream);
+    if constexpr (!NOVOL)      // (folded constants without folded weights: no host path of a network without a volume asks for it)
+        if (a.fold && !a.act_h) return launch_field_tile<NT, HAS_RES, false, false, true>(a, stream);
+    return a.act_h ? launch_field_tile<NT, HAS_RES, true, false, false, 0, NOVOL>(a, stream) : launch_field_tile<NT, HAS_RES, false, false, false, 0, NOVOL>(a, stream);
+}
+
+template <int NT>
+static hipError_t launch_field_res(const FieldArgs& a, hipStream_t stream) {
+    if (no_volume(a)) return has_res(a) ? launch_field_nt<NT, true, true>(a, stream) : launch_field_nt<NT, false, true>(a, stream);
+    return has_res(a) ? launch_field_nt<NT, true>(a, stream) : launch_field_nt<NT, false>(a, stream);
 }
 
 template <int NT, bool STORE, bool DROP>
@@ -1150,11 +1207,10 @@ hipError_t launch_field(const FieldArgs& a, int H, hipStream_t stream) {
             default: return hipErrorInvalidValue;
         }
     }
-    const bool res = has_res(a);
     switch (H / 32) {
-        case 2: return res ? launch_field_nt<2, true>(a, stream) : launch_field_nt<2, false>(a, stream);
-        case 4: return res ? launch_field_nt<4, true>(a, stream) : launch_field_nt<4, false>(a, stream);
-        case 8: return res ? launch_field_nt<8, true>(a, stream) : launch_field_nt<8, false>(a, stream);
+        case 2: return launch_field_res<2>(a, stream);
+        case 4: return launch_field_res<4>(a, stream);
+        case 8: return launch_field_res<8>(a, stream);
         default: return hipErrorInvalidValue;
     }
 }

@@ -136,5 +136,28 @@ __device__ __forceinline__ void input_unit(const f16x8* lds_unit, const Split2* 
     }
 }
 
+// The same for an input tile whose columns 16..31 are zero (the xyz tile of a network without a volume): only the first K = 16
+// half of every output tile's weights is read and multiplied -- the other half would add exact zeros.
+template <int OT>
+__device__ __forceinline__ void input_unit_k16(const f16x8* lds_unit, const Split2& f, f32x16* acc0, int lane) {
+    f16x8 nxt[PARTS];
+#pragma unroll
+    for (int k = 0; k < PARTS; ++k) nxt[k] = lds_unit[k * 64 + lane];
+#pragma unroll
+    for (int t = 0; t < OT; ++t) {
+        f16x8 a[PARTS];
+#pragma unroll
+        for (int k = 0; k < PARTS; ++k) a[k] = nxt[k];
+        if (t + 1 < OT) {
+#pragma unroll
+            for (int k = 0; k < PARTS; ++k) nxt[k] = lds_unit[(2 * (t + 1) * PARTS + k) * 64 + lane];
+        }
+        f32x16 acc = acc0[t];
+        H3_MFMA3(acc, a, f);
+        acc0[t] = acc;
+        __builtin_amdgcn_sched_barrier(0);
+    }
+}
+
 }  // namespace H3_NS
 }  // namespace cnerf

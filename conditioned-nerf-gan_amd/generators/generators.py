@@ -69,7 +69,7 @@ class ImplicitGenerator3d(nn.Module):
         self.siren.device = device
 
     def forward(self, z, cam2worlds, img_size, fov, ray_start, ray_end, num_steps, hierarchical_sample, **kwargs):
-        """z: feature volume (B,C,V,V,V) or (feature volume, global feature (B,z_dim)).
+        """z: feature volume (B,C,V,V,V) or (feature volume, global feature (B,z_dim)); SHORTSIREN: the latent (B,z_dim) alone.
         kwargs read: clamp_mode, nerf_noise (required, like the reference), white_back, last_back; every other key
         of the splatted metadata dict is ignored.  `_rng` (dict of tensors) injects the four random draws and
         `_aux` (dict) receives intermediates, `_field_events` (4 hipEvent_t handles) times the field kernel -- test and
@@ -108,7 +108,11 @@ class ImplicitGenerator3d(nn.Module):
         zs = torch.randn((10000, self.z_dim), device=self.siren.device)
         with torch.no_grad():
             fo = self.siren.mapping_network(zs)
-        half = fo.shape[-1] // 2
-        self.avg_frequencies = fo[..., :half].mean(0, keepdim=True)
-        self.avg_phase_shifts = fo[..., half:].mean(0, keepdim=True)
+        if isinstance(fo, tuple):       # a mapping MLP returns (frequencies, phase_shifts) itself
+            fr, ph = fo
+        else:
+            half = fo.shape[-1] // 2
+            fr, ph = fo[..., :half], fo[..., half:]
+        self.avg_frequencies = fr.mean(0, keepdim=True)
+        self.avg_phase_shifts = ph.mean(0, keepdim=True)
         return self.avg_frequencies, self.avg_phase_shifts

@@ -23,7 +23,8 @@ class FieldSpec:
     sigmoid_rgb: bool           # _sigmoid_rgb on the head                      (siren.py:1227-1234)
     has_global: bool            # z = (feature_volume, global_feature)
     input_is_zdim: bool = False  # the dRes family overrides input_dim = z_dim  (siren.py:349)
-    input: str = "feat"         # "feat" | "feat_xyz" (siren.py:1158) | "pyramid" (siren.py:1444-1473)
+    input: str = "feat"         # "feat" | "feat_xyz" (siren.py:1158) | "pyramid" (siren.py:1444-1473) | "xyz" (per-point FiLM,
+                                # siren.py:232-331) | "position" (no feature volume at all, siren.py:1172-1224)
 
 
 FIELD_SPECS = {
@@ -206,6 +207,70 @@ class TALLSIREN(FieldNetwork):
         super().check_supported()
         if self.input_dim != 3:
             raise NotImplementedError("TALLSIREN reads the world position: input_dim must be 3")
+
+
+class CustomMappingNetwork(nn.Module):
+    """Global latent -> FiLM frequencies and phase shifts of every layer: three times Linear, LeakyReLU(0.2), then a Linear;
+    kaiming-leaky init, last weight scaled by 0.25 (siren.py:47-78).  Plain PyTorch: a few tiny GEMMs per image."""
+
+    def __init__(self, z_dim, map_hidden_dim, map_output_dim):
+        super().__init__()
+        widths = [z_dim, map_hidden_dim, map_hidden_dim, map_hidden_dim]
+        layers = []
+        for n_in, n_out in zip(widths[:-1], widths[1:]):
+            layers += [nn.Linear(n_in, n_out), nn.LeakyReLU(0.2, inplace=True)]
+        self.network = nn.Sequential(*layers, nn.Linear(map_hidden_dim, map_output_dim))
+        for m in self.network:
+            if isinstance(m, nn.Linear):
+                torch.nn.init.kaiming_normal_(m.weight, a=0.2, mode="fan_in", nonlinearity="leaky_relu")
+        with torch.no_grad():
+            self.network[-1].weight *= 0.25
+
+    def forward(self, z):
+        fo = self.network(z)
+        half = fo.shape[-1] // 2
+        return fo[..., :half], fo[..., half:]
+
+
+MAPPING_NETWORKS = {"CustomMappingNetwork": CustomMappingNetwork}
+
+
+class SHORTSIREN(FieldNetwork):
+    """The field of the point-cloud configuration (siren.py:1172-1224): four FiLM layers on the WORLD POSITION of the sample -- no
+    feature volume, no lookup -- whose frequencies / phases come per image from a mapping MLP of one global latent z (B, z_dim);
+    sigmoid on rgb.  Constructor, construction order, initialisation and state-dict keys are the reference's.  Runs on the no-volume
+    instantiations of the field kernels (CNERF_F_NO_VOLUME; all three forward and both backward precisions); the mapping MLP stays in PyTorch and receives its gradients
+    through grad_freq / grad_phase."""
+    variant = "SHORTSIREN"
+    spec = FieldSpec(("film",) * 4, 25, True, True, False, "position")
+
+    def __init__(self, input_dim=2, z_dim=100, hidden_dim=256, output_dim=1, drop_out=0, mapping_network="CustomMappingNetwork", device=None):
+        nn.Module.__init__(self)
+        self.device = device
+        self.input_dim, self.z_dim, self.hidden_dim, self.output_dim = input_dim, z_dim, hidden_dim, output_dim
+        self.drop_out = drop_out
+        self.network = nn.ModuleList([FiLMLayer(input_dim if i == 0 else hidden_dim, hidden_dim, drop_out) for i in range(4)])
+        self.final_layer = nn.Linear(hidden_dim, 4)
+        self.mapping_network = MAPPING_NETWORKS[mapping_network](z_dim, 256, len(self.network) * hidden_dim * 2)
+        _uniform_weights(self.network, lambda n: math.sqrt(6 / n) / 25)
+        _uniform_weights(self.final_layer, lambda n: math.sqrt(6 / n) / 25)
+        _uniform_weights(self.network[0], lambda n: 1 / n)
+
+    def split_z(self, z):
+        """z is the bare latent (B, z_dim): no volume levels."""
+        return [], z
+
+    def film(self, z):
+        freq, phase = self.mapping_network(z)
+        return (freq * 15 + 30).contiguous(), phase.contiguous()
+
+    def check_supported(self):
+        super().check_supported()
+        if self.input_dim != 3:
+            raise NotImplementedError("SHORTSIREN reads the world position: input_dim must be 3")
+
+    def forward(self, input, z, *args):
+        return super().forward(input, z)
 
 
 def _make(name):

@@ -58,20 +58,25 @@ def precision_of(net):
 def make_cfg(net, B, vols, R=1, S=2, fov=30.0, ray_start=0.0, ray_end=1.0, noise_std=0.0, hierarchical=False,
              white_back=False, last_back=False, clamp_mode="relu", precision=None, philox=None, drop=None):
     """cnerf_cfg for a field network `net` (generators.siren.FieldNetwork); vols: channel-last volume(s) or, for calls
-    that touch no volume, the side V of a single 32-channel one."""
+    that touch no volume, the side V of a single 32-channel one; a network without a volume (SHORTSIREN) takes an empty list."""
     cfg = L.Cfg()
-    if isinstance(vols, int):
+    no_volume = net.spec.input == "position"      # layer 0 reads the sample position and nothing else: CNERF_F_NO_VOLUME
+    if no_volume:
+        if not isinstance(vols, int) and len(as_levels(vols)):
+            raise L.CnerfError(f"{net.variant} reads no feature volume")
+        shapes = []
+    elif isinstance(vols, int):
         shapes = [(vols, 32)]
     else:
         shapes = [(int(t.shape[1]), int(t.shape[-1])) for t in as_levels(vols)]
     if len(shapes) > L.MAX_LEVELS:
         raise L.CnerfError(f"at most {L.MAX_LEVELS} feature volumes")
-    cfg.B, cfg.R, cfg.S, cfg.V = int(B), int(R), int(S), shapes[0][0]
+    cfg.B, cfg.R, cfg.S, cfg.V = int(B), int(R), int(S), shapes[0][0] if shapes else 0
     cfg.C, cfg.H = sum(c for _, c in shapes), int(net.hidden_dim)
     cfg.n_levels = len(shapes)
     for i, (v, c) in enumerate(shapes):
         cfg.level_V[i], cfg.level_C[i] = v, c
-    k0 = 3 if net.spec.input == "xyz" else cfg.C + (3 if net.spec.input == "feat_xyz" else 0)
+    k0 = 3 if net.spec.input in ("xyz", "position") else cfg.C + (3 if net.spec.input == "feat_xyz" else 0)
     if not isinstance(vols, int) and k0 != int(net.input_dim):
         raise L.CnerfError(f"{net.variant}: layer 0 expects {net.input_dim} inputs, the feature volumes provide {k0}")
     kinds = [L.LAYER_CODE[k] for k in net.spec.layers]
@@ -85,6 +90,7 @@ def make_cfg(net, B, vols, R=1, S=2, fov=30.0, ray_start=0.0, ray_end=1.0, noise
     flags |= L.F_HIERARCHICAL if hierarchical else 0
     flags |= L.F_SIGMOID_RGB if net.spec.sigmoid_rgb else 0
     flags |= L.F_INPUT_XYZ if net.spec.input == "feat_xyz" else 0
+    flags |= L.F_NO_VOLUME if no_volume else 0
     cfg.flags = flags
     cfg.precision = L.PREC_CODE[precision if precision is not None else precision_of(net)]
     if philox is not None:            # (seed, offset): draws without a tensor are generated in the kernels
@@ -494,7 +500,7 @@ def resident_act16(net, levels, B, R, S, hier, dev):
     """fp16 tile-block buffers that keep the activations of the forward's field passes for the half-precision backward (one
     set per pass: x0, sin, cos), or None when they would not fit the budget -- the backward then re-computes them chunk-wise."""
     H, NT = int(net.hidden_dim), int(net.hidden_dim) // 32
-    n_in = sum(int(t.shape[-1]) for t in levels) // 32 + (1 if net.spec.input == "feat_xyz" else 0)
+    n_in = sum(int(t.shape[-1]) for t in levels) // 32 + (1 if net.spec.input in ("feat_xyz", "position") else 0)
     nslab = n_matrices(net)
     T = B * ((R * R * S + 31) // 32)
     n_pass = 2 if hier else 1

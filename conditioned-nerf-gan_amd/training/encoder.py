@@ -81,3 +81,61 @@ class UNet3D(nn.Module):
         w = self.final_conv.weight.reshape(self.final_conv.out_channels, C)
         y = torch.baddbmm(self.final_conv.bias.view(1, 1, -1), x.flatten(2).transpose(1, 2), w.t().unsqueeze(0).expand(B, -1, -1))
         return y.view(B, *x.shape[2:], -1).permute(0, 4, 1, 2, 3)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# Point-cloud encoder of the reference's default configuration (generators/pointnet.py:59-180; dataset.load_pcl): a PointNet with
+# fully connected residual blocks turns a cloud (B, T, dim) -- xyz and rgb: dim = 6 -- into one latent per object, which drives
+# the FiLM mapping network of SHORTSIREN.  Stock PyTorch: a dozen small GEMMs.  Module names are the reference's, so the
+# `encoder_state_dict` of its checkpoints loads.
+# ---------------------------------------------------------------------------------------------------------------------
+class ResnetBlockFC(nn.Module):
+    """x -> shortcut(x) + fc_1(relu(fc_0(relu(x)))); the shortcut is a bias-free Linear when the widths differ; fc_1 starts at zero."""
+
+    def __init__(self, size_in, size_out=None, size_h=None):
+        super().__init__()
+        size_out = size_in if size_out is None else size_out
+        size_h = min(size_in, size_out) if size_h is None else size_h
+        self.size_in, self.size_h, self.size_out = size_in, size_h, size_out
+        self.fc_0 = nn.Linear(size_in, size_h)
+        self.fc_1 = nn.Linear(size_h, size_out)
+        self.actvn = nn.ReLU()
+        self.shortcut = None if size_in == size_out else nn.Linear(size_in, size_out, bias=False)
+        nn.init.zeros_(self.fc_1.weight)
+
+    def forward(self, x):
+        dx = self.fc_1(self.actvn(self.fc_0(self.actvn(x))))
+        return (x if self.shortcut is None else self.shortcut(x)) + dx
+
+
+class ResnetPointnet(nn.Module):
+    """(B, T, dim) -> (B, c_dim).  Five residual blocks of width 2 h -> h; between them every point's features are joined with
+    the maximum over the cloud's points; the last block's output is max-pooled over the points and projected by fc_c."""
+
+    def __init__(self, c_dim=512, dim=3, hidden_dim=512):
+        super().__init__()
+        self.c_dim = c_dim
+        self.fc_pos = nn.Linear(dim, 2 * hidden_dim)
+        for i in range(5):
+            setattr(self, f"block_{i}", ResnetBlockFC(2 * hidden_dim, hidden_dim))
+        self.fc_c = nn.Linear(hidden_dim, c_dim)
+        self.actvn = nn.ReLU()
+
+    def forward(self, p):
+        net = self.block_0(self.fc_pos(p))
+        for i in range(1, 5):
+            pooled = net.max(dim=1, keepdim=True)[0].expand_as(net)
+            net = getattr(self, f"block_{i}")(torch.cat([net, pooled], dim=2))
+        return self.fc_c(self.actvn(net.max(dim=1)[0]))
+
+
+def encode_pcl(encoder, pcl, device, noise_weight=0):
+    """-> (z, l_reg): the encoder's latents, each row normalised to zero mean and unit (unbiased) standard deviation and mixed
+    with Gaussian noise, z = noise_weight * randn + (1 - noise_weight) * normalised; l_reg is the mean row norm of the latents
+    BEFORE the normalisation (the G step's regulariser, utils.py:694-706)."""
+    codes = encoder(pcl.to(device))
+    l_reg = codes.norm(dim=1).mean()
+    normalised = codes - codes.mean(dim=1, keepdim=True)
+    normalised = normalised / normalised.std(dim=1, keepdim=True)
+    noise = torch.randn(normalised.shape, device=device)
+    return noise_weight * noise + (1 - noise_weight) * normalised, l_reg

@@ -18,7 +18,7 @@ import time
 from ..generators import ImplicitGenerator3d
 from ..generators.volumetric_rendering import create_cam2world_matrix, sample_camera_positions
 from . import discriminator as discriminators
-from .encoder import UNet3D
+from .encoder import ResnetPointnet, UNet3D, encode_pcl
 
 
 class PhaseTimer:
@@ -76,13 +76,21 @@ def default_metadata(img_size=128, num_steps=64, batch_size=8, batch_split=4, si
     """The render / optimisation hyper-parameters of configs/thousand/{default,special}.py for the direct-feature-volume
     setting (unet3d encoder -> (feature volume, global feature) -> FG field networks).  Field networks without a global feature
     (TALLSIREN -- per-point FiLM from the looked-up feature, input = world position --, the plain-sine / residual families) take the bare
-    feature volume: the encoder then returns it alone and z_dim is its channel count (siren.py:232-331, 333-488)."""
+    feature volume: the encoder then returns it alone and z_dim is its channel count (siren.py:232-331, 333-488).
+    SHORTSIREN is the point-cloud setting of configs/thousand/special.py: the reference's generator dictionary, dataset.load_pcl,
+    a PointNet encoder entry (utils.py:373-374), noise_weight and the first stage's z_reg_weight."""
     from ..generators import siren as _siren
     spec = getattr(_siren, siren_type).spec
     gen = {"siren_type": siren_type, "z_dim": 256, "input_dim": 32, "output_dim": 4, "hidden_dim": hidden_dim}
     if not spec.has_global:
         gen.update(z_dim=32, input_dim=3 if spec.input == "xyz" else 32)
+    extra = {}
+    if spec.input == "position":
+        gen.update(z_dim=512, input_dim=3)
+        extra = {"dataset": {"load_voxel": False, "load_pcl": True}, "pointnet": {"c_dim": 512, "dim": 6, "hidden_dim": 512},
+                 "noise_weight": 0, "z_reg_weight": 0.01}
     return {
+        **extra,
         "img_size": img_size, "num_steps": num_steps, "batch_size": batch_size, "batch_split": batch_split,
         "fov": 49.134342641202636, "ray_start": 0.25, "ray_end": 1.95, "cam_r_start": 0.7, "cam_r_end": 1.5,
         "white_back": True, "last_back": False, "clamp_mode": "relu", "hierarchical_sample": True, "nerf_noise": 1.0,
@@ -120,7 +128,16 @@ class GanTrainer:
             # reference's own autocast training, 2x faster; with render_precision "fp16x3" the forward's activations are kept
             # for it instead of being re-computed)
             self.generator.siren.backward_precision = metadata.get("backward_precision", "fp32")
-        self.encoder = (modules["encoder"] if "encoder" in modules else UNet3D(**metadata["unet"])).to(device)
+        # the point-cloud setting (metadata["dataset"]["load_pcl"], utils.py:373-374): a PointNet encodes sample["pcl"] (B, T, 6) into
+        # one latent per object instead of the U-Net encoding sample["voxel"]
+        self.load_pcl = bool(metadata.get("dataset", {}).get("load_pcl", False))
+        self.input_key = "pcl" if self.load_pcl else "voxel"
+        if "encoder" in modules:
+            self.encoder = modules["encoder"].to(device)
+        elif self.load_pcl:
+            self.encoder = ResnetPointnet(**metadata.get("pointnet", {"c_dim": metadata["generator"]["z_dim"], "dim": 6})).to(device)
+        else:
+            self.encoder = UNet3D(**metadata["unet"]).to(device)
         if metadata.get("encoder_channels_last", False):     # NDHWC convolutions (MIOpen); off by default: measured below
             self.encoder = self.encoder.to(memory_format=torch.channels_last_3d)
         if "discriminator" in modules:
@@ -139,6 +156,7 @@ class GanTrainer:
         self.alpha = 1.0
         self.losses = {"d": [], "g": [], "photo": []}
         self._z = {}            # chunk index -> encoder output kept between the D and the G pass of one step
+        self._z_reg = None      # point-cloud setting: l_reg of the latents the most recent render used (encode_pcl)
         self.last = {}          # diagnostics of the most recent step: loss terms and pre-clip gradient norms
         self.render_rng = None  # test hook: callable(chunk_index, phase) -> dict of injected draws for that render
         self.timer = None       # a PhaseTimer while a caller wants the step split into phases (bench.py), else None
@@ -183,7 +201,9 @@ class GanTrainer:
     def _encode(self, voxels):
         """The 3D U-Net.  metadata["encoder_autocast"] = "bf16" / "fp16" runs its convolutions under torch.autocast, as the
         reference's GPU training does with the whole step (utils.py:327,643: autocast + GradScaler; bf16 needs no scaler); the
-        render path takes fp32 volumes either way."""
+        render path takes fp32 volumes either way.  Point-cloud setting: (z, l_reg) of encode_pcl."""
+        if self.load_pcl:
+            return encode_pcl(self.encoder_ddp, voxels, self.device, noise_weight=self.metadata.get("noise_weight", 0))
         amp = self.metadata.get("encoder_autocast")
         if not amp:
             return self.encoder_ddp(voxels)
@@ -195,6 +215,8 @@ class GanTrainer:
         z = self._z.get(chunk) if phase == "d" else self._z.pop(chunk, None)      # encoder output kept by step() (see there)
         if z is None:
             z = self._encode(voxels)
+        if self.load_pcl:
+            z, self._z_reg = z
         extra = {"_rng": self.render_rng(chunk, phase)} if self.render_rng is not None else {}
         return self.generator_ddp(z, cams, **self.metadata, **extra)
 
@@ -206,7 +228,7 @@ class GanTrainer:
     def train_discriminator(self, sample):
         md = self.metadata
         real = sample["img"].to(self.device).requires_grad_(True)
-        voxels = sample["voxel"].to(self.device)
+        voxels = sample[self.input_key].to(self.device)
         n = real.shape[0]
         with torch.no_grad():
             if md.get("random_gen_img", True):
@@ -235,9 +257,9 @@ class GanTrainer:
     # utils.py:621-741
     def train_generator(self, sample):
         md = self.metadata
-        imgs, cams, voxels = (sample[k].to(self.device) for k in ("img", "cam2world", "voxel"))
+        imgs, cams, voxels = (sample[k].to(self.device) for k in ("img", "cam2world", self.input_key))
         chunks = self._chunks(imgs.shape[0])
-        g_acc = p_acc = 0.0
+        g_acc = p_acc = r_acc = 0.0
         d_params = [p for p in self.discriminator.parameters() if p.requires_grad]
         for p in d_params:                  # see _disc(frozen=True)
             p.requires_grad_(False)
@@ -257,8 +279,12 @@ class GanTrainer:
                         else:
                             loss_g = gen_imgs.new_zeros(())
                         photo = F.mse_loss(gen_imgs, imgs[c]) if md["photo_loss"] else gen_imgs.new_zeros(())
+                    loss = loss_g + photo
+                    if self.load_pcl:      # utils.py:694-706: the latents' mean norm, weighted
+                        loss = loss + md["z_reg_weight"] * self._z_reg
+                        r_acc += self._z_reg.item()
                     with self._phase("g_backward"):
-                        (loss_g + photo).backward()
+                        loss.backward()
                 g_acc += loss_g.item()
                 p_acc += photo.item()
         finally:
@@ -272,6 +298,8 @@ class GanTrainer:
         self.losses["g"].append(g_acc / len(chunks))
         self.losses["photo"].append(p_acc / len(chunks))
         self.last.update(g_loss=g_acc / len(chunks), photo_loss=p_acc / len(chunks))
+        if self.load_pcl:
+            self.last.update(z_reg=r_acc / len(chunks), z_reg_loss=md["z_reg_weight"] * r_acc / len(chunks))
         # half-precision render backward: (tile, matrix) blocks whose stored gradients left fp16's range and were clamped -- the
         # per-matrix scale comes from a sampled maximum (include/cnerf.h, cnerf_render_backward).  Non-zero: outlier gradients were
         # cut; train with backward_precision "fp32" if that matters.
@@ -289,9 +317,10 @@ class GanTrainer:
         md = self.metadata
         n = sample["img"].shape[0]
         c = self._chunks(n)[0]
-        vox = sample["voxel"][c].to(self.device)
-        fv, glob = self.encoder(vox)
-        (fv.square().mean() + glob.square().mean()).backward()
+        if not self.load_pcl:      # (a PointNet has no convolutions)
+            vox = sample["voxel"][c].to(self.device)
+            fv, glob = self.encoder(vox)
+            (fv.square().mean() + glob.square().mean()).backward()
         real = sample["img"].to(self.device).requires_grad_(True)
         out = self.discriminator(real, self.alpha, **md)
         pred = out[0] if isinstance(out, tuple) else out
@@ -312,7 +341,7 @@ class GanTrainer:
         self.set_alpha()
         self._z = {}
         if self.metadata["enable_discriminator"] and self.metadata.get("reuse_encoder_output", True):
-            voxels = sample["voxel"].to(self.device)
+            voxels = sample[self.input_key].to(self.device)
             chunks = self._chunks(voxels.shape[0])
             for i, c in enumerate(chunks):
                 last = i == len(chunks) - 1
@@ -328,10 +357,16 @@ class GanTrainer:
         self.discriminator.step += 1
 
 
-def synthetic_sample(batch, img_size, voxel_res, device, generator=None):
+def synthetic_sample(batch, img_size, voxel_res, device, generator=None, pcl_points=0):
     """ShapeNetCar-shaped random batch: voxels (B,4,V,V,V) = [occupancy, r, g, b] (datasets.py:105-110), images in [-1,1],
-    cameras on the training shell."""
+    cameras on the training shell.  pcl_points > 0: the point-cloud setting instead of voxels -- "pcl" (B, T, 6) = [xyz in the
+    1.2 cube, rgb] (datasets.py:159)."""
     g = generator
+    if pcl_points:
+        xyz = (torch.rand(batch, pcl_points, 3, generator=g) - 0.5) * 1.2
+        pcl = torch.cat([xyz, torch.rand(batch, pcl_points, 3, generator=g)], 2)
+        cams = create_cam2world_matrix(sample_camera_positions("cpu", "y", 0.7, 1.5, batch), "y")
+        return {"pcl": pcl.to(device), "img": (torch.rand(batch, 3, img_size, img_size, generator=g) * 2 - 1).to(device), "cam2world": cams.to(device)}
     occ = (torch.rand(batch, 1, voxel_res, voxel_res, voxel_res, generator=g) > 0.9).float()
     rgb = torch.rand(batch, 3, voxel_res, voxel_res, voxel_res, generator=g) * occ
     cams = create_cam2world_matrix(sample_camera_positions("cpu", "y", 0.7, 1.5, batch), "y")

@@ -22,7 +22,7 @@
 extern "C" {
 #endif
 
-#define CNERF_ABI_VERSION 9
+#define CNERF_ABI_VERSION 10
 
 #define CNERF_OK 0
 #define CNERF_EINVAL (-22)  /* bad argument / unsupported shape (message via cnerf_last_error) */
@@ -41,6 +41,17 @@ extern "C" {
 #define CNERF_F_INPUT_XYZ (1u << 5)    /* siren.py:1158  layer 0 sees features || world xyz (TALLSIREN_dgx) */
 #define CNERF_F_RESERVED6 (1u << 6)    /* reserved (ABI v4-v5: selected an experimental kernel variant that was measured slower and
                                           removed in v6); ignored */
+#define CNERF_F_NO_VOLUME (1u << 7)    /* siren.py:1172-1224 (SHORTSIREN, ABI v10): the network reads no feature volume -- layer 0 sees the sample's
+                                          world xyz (K = 3), FiLM frequencies / phases come per image from the caller.  Requires C == 0 and
+                                          n_levels == 0 (V is not read); layer kinds FILM / SINE / RES (PFILM: CNERF_EINVAL); not together with
+                                          CNERF_F_INPUT_XYZ (CNERF_EINVAL).  `vols` / `grad_vols` arguments may be NULL and are never dereferenced,
+                                          cnerf_workspace_bytes reports fvol_cl = 0, no backward scatters anything, and the position gradient of
+                                          cnerf_field_query_backward is the xyz term alone (no clamp: it is non-zero outside the 1.2 cube).
+                                          All three precisions and both backward precisions (dropout: fp32 only, as everywhere).  fp32: layer 0 runs
+                                          as three fp32 fmas per output channel on the vector units, no K = 32 MFMA tile; fp16x3 / fp16: as the
+                                          first weight unit on the zero-padded xyz tile.  No kernel looks anything up or keeps loads in flight
+                                          across tiles; the half-precision backward reserves no input-gradient rows and launches no patch scatter.
+                                          cnerf_gather_features / cnerf_scatter_features / cnerf_feature_points_grad refuse the flag. */
 
 /* cnerf_cfg.precision */
 #define CNERF_PREC_FP32 0   /* v_mfma_f32_32x32x2_f32: exact fp32 fmaf chains */
@@ -67,7 +78,8 @@ typedef struct cnerf_cfg {
     int32_t R;            /* img_size */
     int32_t S;            /* num_steps (coarse samples per ray) */
     int32_t V;            /* feature volume side (level 0) */
-    int32_t C;            /* feature channels over all levels; input width of layer 0 = C (+3 with CNERF_F_INPUT_XYZ) */
+    int32_t C;            /* feature channels over all levels; input width of layer 0 = C (+3 with CNERF_F_INPUT_XYZ);
+                             0 with CNERF_F_NO_VOLUME (input width 3) */
     int32_t H;            /* hidden width (multiple of 32, <= 256) */
     int32_t L;            /* number of entries in layer_kind */
     int32_t layer_kind[CNERF_MAX_LAYERS];
@@ -104,7 +116,8 @@ typedef struct cnerf_cfg {
 } cnerf_cfg;
 
 /* Feature volumes, channel-last: level[i] is (B, V_i, V_i, V_i, C_i).  HOST struct of device pointers.  The gradient
- * twin of the backward has the same shapes and is accumulated into. */
+ * twin of the backward has the same shapes and is accumulated into.  CNERF_F_NO_VOLUME: there are none; every `vols` /
+ * `grad_vols` argument below may then be NULL. */
 typedef struct cnerf_volumes {
     const float* level[CNERF_MAX_LEVELS];
 } cnerf_volumes;
@@ -194,7 +207,7 @@ const char* cnerf_last_error(void);
 
 /* Validates cfg and returns the byte sizes the caller must provide:
  *   packed   : packed field weights written by cnerf_pack_field
- *   fvol_cl  : channel-last copy of the feature volume written by cnerf_fvol_channel_last
+ *   fvol_cl  : channel-last copy of the feature volume written by cnerf_fvol_channel_last (0 with CNERF_F_NO_VOLUME)
  *   fwd_ws   : scratch of cnerf_render_forward (coarse / fine rgb_sigma and depths, and the folded FiLM constants of the call:
  *              per image, matrix and channel  freq / 2 pi  and  (freq * bias + phase) / 2 pi, and the layer weights with their rows scaled
  *              by freq / 2 pi per image, prepared once for both field passes in fp32 precision) */

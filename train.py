@@ -30,6 +30,7 @@ def main():
                     help="gradient-accumulation chunks per step; the reference's configs use 4-6 to fit 48 GB GPUs, 288 GB of HBM take the "
                          "whole batch at once (0.218 s/step against 0.267 with 4 chunks at batch 8)")
     ap.add_argument("--voxel-res", type=int, default=64)
+    ap.add_argument("--pcl-points", type=int, default=2048, help="points per synthetic cloud (B, T, 6) of the point-cloud setting (--siren-type SHORTSIREN)")
     ap.add_argument("--siren-type", default="SHORTSIREN_FG")
     ap.add_argument("--hidden", type=int, default=256)
     ap.add_argument("--precision", default="fp16x3", choices=["fp32", "fp16x3"],
@@ -74,6 +75,7 @@ def main():
     md = default_metadata(args.img_size, args.num_steps, args.batch, args.batch_split, args.siren_type, args.hidden)
     md["render_precision"] = args.precision
     md["backward_precision"] = args.backward_precision
+    pcl_points = args.pcl_points if md.get("dataset", {}).get("load_pcl") else 0
     md["encoder_autocast"] = args.encoder_autocast
     md["enable_discriminator"] = not args.no_discriminator
     for k in ("gen_lr", "disc_lr", "enc_lr"):
@@ -92,6 +94,8 @@ def main():
         from cnerf_amd.generators import ImplicitGenerator3d
         from cnerf_amd.training.encoder import UNet3D
         torch.manual_seed(4321)                       # the same teacher on every rank
+        if pcl_points:
+            raise SystemExit("--teacher renders voxel grids: not available with the point-cloud setting")
         t_enc = UNet3D(**md["unet"]).to(dev).eval()
         t_gen = ImplicitGenerator3d(**md["generator"]).to(dev).eval()
         t_gen.set_device(dev)
@@ -126,7 +130,7 @@ def main():
         from cnerf_amd.training.miopen_db import use_shipped_db
         rank0_first(rank, "miopen_db", use_shipped_db)
         use_shipped_db(merge=False)
-        warm = synthetic_sample(args.batch, args.img_size, args.voxel_res, dev, torch.Generator().manual_seed(1))
+        warm = synthetic_sample(args.batch, args.img_size, args.voxel_res, dev, torch.Generator().manual_seed(1), pcl_points)
         def search():
             t0 = time.perf_counter()
             trainer.warm_convolutions(warm)
@@ -142,7 +146,7 @@ def main():
                 torch.cuda.synchronize()
             dist.barrier()
     for step in range(args.steps):
-        sample = synthetic_sample(args.batch, args.img_size, args.voxel_res, dev, gen)
+        sample = synthetic_sample(args.batch, args.img_size, args.voxel_res, dev, gen, pcl_points)
         if teacher is not None:
             sample = teacher(sample)
         torch.cuda.synchronize()
