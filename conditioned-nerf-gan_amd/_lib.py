@@ -105,6 +105,10 @@ PROTOTYPES = {
                                               C.c_int64] + [C.c_void_p] * 7 + [C.POINTER(Volumes), C.c_void_p, C.c_void_p]),
     "cnerf_feature_points_grad": (C.c_int, [C.POINTER(Cfg), C.POINTER(Volumes), C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
     "cnerf_dropout_keep": (C.c_int, [C.POINTER(Cfg), C.c_uint32, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p]),
+    "cnerf_pfilm_finish_bytes": (C.c_int, [C.POINTER(Cfg), C.c_int32, C.c_int64, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]),
+    "cnerf_pack_pfilm_map_transposed": (C.c_int, [C.POINTER(Cfg), C.POINTER(FieldParams), C.c_void_p, C.c_void_p]),
+    "cnerf_pfilm_backward_finish": (C.c_int, [C.POINTER(Cfg), C.POINTER(FieldParams), C.c_void_p, C.c_int32, C.c_int64] + [C.c_void_p] * 5 +
+                                    [C.POINTER(FieldParamGrads), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
 }
 
 _lib = None

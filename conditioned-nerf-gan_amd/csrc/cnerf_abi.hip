@@ -975,8 +975,8 @@ int chunk_layout(const cnerf_cfg* c, int bprec, int cnt, size_t npi, size_t N_ou
                  BackwardLayout& L) {
     if (bprec != CNERF_PREC_FP32 && bprec != CNERF_PREC_FP16) return fail(CNERF_EINVAL, "%s: backward_precision must be CNERF_PREC_FP32 or CNERF_PREC_FP16", who);
     if (c->layer_kind[0] == CNERF_LAYER_PFILM && bprec != CNERF_PREC_FP16)
-        return fail(CNERF_ENOSYS, "%s: the per-point FiLM family's exact fp32 backward finishes its mapping-MLP gradients with library "
-                                  "GEMMs on the host (cnerf_field_backward + cnerf_weight_grad + cnerf_scatter_features); backward_precision fp16 runs here", who);
+        return fail(CNERF_ENOSYS, "%s: the per-point FiLM family's exact fp32 backward is spelled with stage calls (per pass and chunk "
+                                  "cnerf_field_backward, then cnerf_pfilm_backward_finish); backward_precision fp16 runs here", who);
     if (cnt < 1 || cnt > c->B) return fail(CNERF_EINVAL, "%s: images_per_chunk=%d out of [1,B]", who, cnt);
     if (c->layer_kind[0] == CNERF_LAYER_PFILM) {      // chain_pw16.hip: three stored derivatives and three gradient slabs per layer, m and g_mpre
         if (have_act16 && cnt != c->B) return fail(CNERF_EINVAL, "%s: kept activations need images_per_chunk = B", who);
@@ -1538,6 +1538,97 @@ int cnerf_dropout_keep(const cnerf_cfg* cfg, uint32_t stream_id, int64_t point0,
     if (hipError_t e = launch_drop_keep(philox_of(cfg), stream_id, nc.drop_thresh, nc.n_drop, cfg->H, (unsigned long long)point0, (long long)n_points, mask,
                                         (hipStream_t)stream))
         return hip_fail(e, "drop_keep");
+    return CNERF_OK;
+}
+
+}  // extern "C"
+
+namespace {
+// Buffers of cnerf_pfilm_backward_finish (n = n_images * n_per_image rows), every piece 256-byte aligned:
+//   packed_map = [Wm2 in pfilm_gm32_kernel's A-operand order: 2 L H * 256 floats][Wm1 in its chained product's: 256 * 32 floats]
+//   workspace  = [g_mpre (n, 256)][d feat (n, 32): the rows the scatter reads when the caller passes no grad_feat]
+struct PfilmFinishLayout {
+    size_t packed_map, g_mpre, d_feat, total;
+    int K2;
+};
+int pfilm_finish_layout(const cnerf_cfg* c, int n_images, long long npi, const char* who, PfilmFinishLayout& F) {
+    if (int rc = check_cfg(c, false)) return rc;
+    if (c->layer_kind[0] != CNERF_LAYER_PFILM) return fail(CNERF_EINVAL, "%s: per-point FiLM networks only (layer 0 is of kind %d)", who, c->layer_kind[0]);
+    if (c->precision != CNERF_PREC_FP32)
+        return fail(CNERF_EINVAL, "%s: a stage of the exact fp32 backward: cfg->precision must be CNERF_PREC_FP32 (the fp16 backward runs in cnerf_render_backward)", who);
+    if (c->C != 32 || c->n_levels > 1) return fail(CNERF_EINVAL, "%s: single 32-channel volume only", who);
+    if (n_images < 1 || npi < 1) return fail(CNERF_EINVAL, "%s: empty chunk (n_images=%d, n_per_image=%lld)", who, n_images, npi);
+    const size_t n = (size_t)n_images * (size_t)npi;
+    F.K2 = 2 * c->L * c->H;
+    F.packed_map = align256(((size_t)F.K2 * 256 + 256 * 32) * sizeof(float));
+    F.g_mpre = 0;
+    F.d_feat = align256(n * 256 * sizeof(float));
+    F.total = F.d_feat + align256(n * 32 * sizeof(float));
+    return CNERF_OK;
+}
+bool misaligned16(const void* p) { return ((uintptr_t)p & 15) != 0; }
+}  // namespace
+
+extern "C" {
+
+int cnerf_pfilm_finish_bytes(const cnerf_cfg* cfg, int32_t n_images, int64_t n_per_image, size_t* packed_map, size_t* workspace) {
+    g_err[0] = 0;
+    PfilmFinishLayout F;
+    if (int rc = pfilm_finish_layout(cfg, n_images, (long long)n_per_image, "pfilm_finish_bytes", F)) return rc;
+    if (packed_map) *packed_map = F.packed_map;
+    if (workspace) *workspace = F.total;
+    return CNERF_OK;
+}
+
+int cnerf_pack_pfilm_map_transposed(const cnerf_cfg* cfg, const cnerf_field_params* p, void* packed_map, void* stream) {
+    g_err[0] = 0;
+    PfilmFinishLayout F;
+    if (int rc = pfilm_finish_layout(cfg, 1, 1, "pack_pfilm_map_transposed", F)) return rc;
+    if (!p || !packed_map || !p->map_w1 || !p->map_w2) return fail(CNERF_EINVAL, "pack_pfilm_map_transposed: NULL argument (map_w1, map_w2, packed_map)");
+    if (misaligned16(packed_map)) return fail(CNERF_EINVAL, "pack_pfilm_map_transposed: packed_map must be 16-byte aligned");
+    if (hipError_t e = launch_pack_pfilm_map(p->map_w1, p->map_w2, F.K2, (float*)packed_map, (hipStream_t)stream)) return hip_fail(e, "pack_pfilm_map");
+    return CNERF_OK;
+}
+
+int cnerf_pfilm_backward_finish(const cnerf_cfg* cfg, const cnerf_field_params* params, const void* packed_map, int32_t n_images, int64_t n_per_image,
+                                const float* points, const float* act_feat, const float* act_h, const float* act_g, const float* act_go,
+                                const cnerf_field_param_grads* G, float* grad_fvol_cl, float* grad_feat, void* workspace, void* stream_) {
+    g_err[0] = 0;
+    (void)params;      // the stage reads both mapping matrices from packed_map
+    PfilmFinishLayout F;
+    if (int rc = pfilm_finish_layout(cfg, n_images, (long long)n_per_image, "pfilm_backward_finish", F)) return rc;
+    if (!packed_map || !points || !act_feat || !act_h || !act_g || !act_go || !G || !workspace)
+        return fail(CNERF_EINVAL, "pfilm_backward_finish: NULL argument (packed_map, points, act_feat, act_h, act_g, act_go, grads, workspace)");
+    if (misaligned16(packed_map) || misaligned16(act_feat) || misaligned16(act_h) || misaligned16(act_g) || misaligned16(act_go) || misaligned16(grad_feat) ||
+        misaligned16(workspace))
+        return fail(CNERF_EINVAL, "pfilm_backward_finish: packed_map, act_*, grad_feat and workspace must be 16-byte aligned");
+    hipStream_t stream = (hipStream_t)stream_;
+    const int H = cfg->H, Lc = cfg->L;
+    const long long n = (long long)n_images * n_per_image;
+    const size_t slab = (size_t)n * H;
+    const float* m = act_h + (size_t)Lc * slab;
+    const float* Gm = act_g + (size_t)Lc * slab;
+    float* g_mpre = (float*)((char*)workspace + F.g_mpre);
+    float* d_feat = grad_feat ? grad_feat : (float*)((char*)workspace + F.d_feat);
+    // the reductions over the chunk's rows run over all n of them at once and add to the caller's buffers themselves: no per-image partials
+    if (G->w[0] || G->b[0])
+        if (hipError_t e = launch_layer0_grad32(act_g, points, n, H, G->w[0], G->b[0], stream)) return hip_fail(e, "layer0_grad32");
+    for (int l = 1; l < Lc; ++l)
+        if (G->w[l] || G->b[l])
+            if (hipError_t e = launch_weight_grad(1, n, H, H, act_g + (size_t)l * slab, act_h + (size_t)(l - 1) * slab, G->w[l], G->b[l], stream))
+                return hip_fail(e, "weight_grad");
+    if (G->w_final || G->b_final)
+        if (hipError_t e = launch_head_grad32(act_go, act_h + (size_t)(Lc - 1) * slab, n, H, G->w_final, G->b_final, stream)) return hip_fail(e, "head_grad32");
+    if (G->map_w2 || G->map_b2)
+        if (hipError_t e = launch_weight_grad(1, n, F.K2, 256, Gm, m, G->map_w2, G->map_b2, stream)) return hip_fail(e, "weight_grad (Wm2)");
+    if (!G->map_w1 && !G->map_b1 && !grad_fvol_cl && !grad_feat) return CNERF_OK;
+    if (hipError_t e = launch_pfilm_gm32((const float*)packed_map, Gm, m, n, F.K2, g_mpre, d_feat, stream)) return hip_fail(e, "pfilm_gm32");
+    if (G->map_w1 || G->map_b1)
+        if (hipError_t e = launch_weight_grad(1, n, 256, 32, g_mpre, act_feat, G->map_w1, G->map_b1, stream)) return hip_fail(e, "weight_grad (Wm1)");
+    if (grad_fvol_cl) {
+        GatherArgs a{nullptr, points, nullptr, (long long)n_per_image, n_images, cfg->V, cfg->C, cfg->voxel_length / 2.0f};
+        if (hipError_t e = launch_scatter(a, d_feat, grad_fvol_cl, stream)) return hip_fail(e, "scatter");
+    }
     return CNERF_OK;
 }
 

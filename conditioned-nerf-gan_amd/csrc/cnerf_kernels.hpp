@@ -273,6 +273,12 @@ hipError_t launch_head_grad32(const float* go, const float* x, long long n, int 
 hipError_t launch_absmax_bits(const float* v, long long n, uint32_t* slot, hipStream_t stream);
 hipError_t launch_pow2_scales(const uint32_t* gmax_bits, int n, float* scales, hipStream_t stream);
 
+// pfilm_finish.hip: mapping-network stage of the per-point FiLM family's exact fp32 backward (cnerf_pfilm_backward_finish)
+hipError_t launch_pack_pfilm_map(const float* wm1, const float* wm2, int K2, float* dst, hipStream_t stream);
+hipError_t launch_pfilm_gm32(const float* packed_map, const float* G, const float* m, long long n, int K2, float* g_mpre, float* d_feat,
+                             hipStream_t stream);
+hipError_t launch_layer0_grad32(const float* g, const float* pts, long long n, int H, float* dW, float* db, hipStream_t stream);
+
 // bwd16.hip
 hipError_t launch_pack_t16(const float* w, int n_rows_w, int n_cols_w, int n_cols_real, int OT_padded, void* dst, float* winv_slot, uint32_t* wmax_slot,
                            hipStream_t stream);

@@ -696,8 +696,8 @@ __global__ __launch_bounds__(256) void field_pw_kernel(FieldArgs a) {
 //   go' = d loss / d head pre-activation (sigmoid' applied)                          -> act_go (n,4)
 //   g_h_L = W_head^T go'            (MFMA, K = 4 outputs in two k-steps)
 //   for l = L..1:  g_arg_l = g_h_l * cos(arg_l)   -> act_g[l] (n,H)   (the weight / FiLM gradients are GEMMs and column
-//                  g_pre_l = g_arg_l * freq_l                           sums over these buffers: done by the caller with
-//                  g_h_{l-1} = W_l^T g_pre_l   (MFMA, transposed pack)  rocBLAS, they are plain library GEMMs)
+//                  g_pre_l = g_arg_l * freq_l                           sums over these buffers: weight_grad_kernel and
+//                  g_h_{l-1} = W_l^T g_pre_l   (MFMA, transposed pack)  param_reduce_kernel, grad_kernels.hip)
 //   g_feat (32 ch) -> trilinear scatter-add into the channel-last gradient volume with fp32 atomics; the tile is
 //   transposed through LDS so that one wave instruction adds two whole 128-byte corner lines (the shape the memory-side
 //   atomic units run at full rate for: MI355X_MICROARCH.md "Global float atomics").
@@ -787,7 +787,7 @@ __device__ __forceinline__ const float* head_backward(const FieldArgs& a, size_t
 // column sums: cnerf_weight_grad -- followed by G (n, 2 L H) = [g_rawfreq of layers 0..L-1 | g_phase of layers 0..L-1], i.e.
 // d loss / d (output of the mapping network's second Linear) row by row in that Linear's own output order: its weight
 // gradient G^T m and the gradient G Wm2 that continues into the mapping MLP, the looked-up feature and the volume are
-// plain GEMMs over this buffer, left to the caller (library GEMMs + cnerf_scatter_features).  The sample positions carry
+// plain GEMMs over this buffer: the mapping-network stage (pfilm_finish.hip, cnerf_pfilm_backward_finish).  The sample positions carry
 // no gradient (generators.py:57,111), so the chain stops at layer 0.
 // ---------------------------------------------------------------------------------------------------------------
 template <int NT>

@@ -124,16 +124,18 @@ __global__ __launch_bounds__(256) void weight_grad_kernel(WeightGradArgs a) {
     }
     if (!active) return;
     // D[i][j]: register 4g + e of lane (c, p) is row 8g + 4p + e, column c of the tile
-    float* dWb = a.dW + (size_t)b * a.H * K;
+    if (a.dW) {                                        // (either output may be null: the mapping-network stage skips gradients nobody asked for)
+        float* dWb = a.dW + (size_t)b * a.H * K;
 #pragma unroll
-    for (int j = 0; j < NJ; ++j)
+        for (int j = 0; j < NJ; ++j)
 #pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            const int row = col0 + 32 * wave + 8 * (r >> 2) + 4 * p + (r & 3);
-            atomicAdd(dWb + (size_t)row * K + 32 * j + c, acc[j][r]);
-        }
+            for (int r = 0; r < 16; ++r) {
+                const int row = col0 + 32 * wave + 8 * (r >> 2) + 4 * p + (r & 3);
+                atomicAdd(dWb + (size_t)row * K + 32 * j + c, acc[j][r]);
+            }
+    }
     const float tot = cs + __shfl_xor(cs, 32, WAVE);
-    if (p == 0) atomicAdd(a.colsum + (size_t)b * a.H + col0 + 32 * wave + c, tot);
+    if (a.colsum && p == 0) atomicAdd(a.colsum + (size_t)b * a.H + col0 + 32 * wave + c, tot);
 }
 
 template <int NJ>
@@ -147,7 +149,8 @@ static hipError_t launch_wg(const WeightGradArgs& a, hipStream_t stream) {
 
 hipError_t launch_weight_grad(int cnt, long long npi, int H, int K, const float* G, const float* X, float* dW, float* colsum,
                               hipStream_t stream) {
-    if (cnt < 1 || npi < 1 || (H != 64 && H != 128 && H != 256) || K < 32 || K > 256 || K % 32) return hipErrorInvalidValue;
+    // H: any multiple of 32 from 64 up (dWm2 of the per-point FiLM family has 2 L H rows: blockIdx.y row groups); cnerf_weight_grad keeps its own limits
+    if (cnt < 1 || npi < 1 || H < 64 || H % 32 || K < 32 || K > 256 || K % 32) return hipErrorInvalidValue;
     const int cus = cu_count();
     WeightGradArgs a{G, X, dW, colsum, npi, cnt, H, K, 1};
     const long long stages = (npi + WG_P - 1) / WG_P;
@@ -252,10 +255,10 @@ __global__ __launch_bounds__(256) void head_grad32_kernel(const float* __restric
             cs[r] += g[r];
         }
     }
-    if (c < H)
+    if (dW && c < H)
 #pragma unroll
         for (int r = 0; r < 4; ++r) atomicAdd(dW + (size_t)r * H + c, acc[r]);
-    if (c == 0)
+    if (db && c == 0)
 #pragma unroll
         for (int r = 0; r < 4; ++r) atomicAdd(db + r, cs[r]);
 }

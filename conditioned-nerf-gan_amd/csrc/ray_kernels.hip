@@ -567,8 +567,8 @@ __global__ __launch_bounds__(256) void gather_kernel(GatherArgs a) {
 // at 255 cycles average L2 round trip, the L1 stalled on pending misses for 42 % of its active cycles.
 
 // Adjoint of gather_kernel: grad_fvol[corner k of point] += w_k * grad_feat[point] (8 lanes per point, 4 channels each, so
-// the 8 lanes of a point add one whole 128-B corner line per atomic instruction).  Used by the backward of the per-point
-// FiLM family, whose MLP gradients are evaluated by library GEMMs on the host side (ops._pfilm_backward).
+// the 8 lanes of a point add one whole 128-B corner line per atomic instruction).  Used by the exact backward of the per-point
+// FiLM family on the d feat rows of its mapping-network stage (cnerf_pfilm_backward_finish) and by cnerf_scatter_features.
 __global__ __launch_bounds__(256) void scatter_kernel(GatherArgs a, const float* __restrict__ grad_feat, float* __restrict__ grad_fvol) {
     const int sub = threadIdx.x & 7;
     const PointRange pr = point_range((long long)a.B * a.n_per_image);

@@ -357,6 +357,19 @@ def pack_field_transposed(net, cfg):
     return _cached_pack(net, cfg, "transposed", lambda: _abi_bytes("cnerf_backward_bytes", cfg), "cnerf_pack_field_transposed", torch.float32)
 
 
+def pfilm_finish_bytes(cfg, n_images, n_per_image):
+    """(packed_map bytes, workspace bytes) of cnerf_pfilm_backward_finish on a chunk of n_images x n_per_image rows."""
+    pm, ws = C.c_size_t(0), C.c_size_t(0)
+    L.check(L.lib().cnerf_pfilm_finish_bytes(C.byref(cfg), int(n_images), int(n_per_image), C.byref(pm), C.byref(ws)), "cnerf_pfilm_finish_bytes")
+    return pm.value, ws.value
+
+
+def pack_pfilm_map(net, cfg):
+    """Both matrices of the per-point FiLM family's mapping network in the operand order of its exact backward's stage
+    (cnerf_pack_pfilm_map_transposed)."""
+    return _cached_pack(net, cfg, "pfilm_map", lambda: pfilm_finish_bytes(cfg, 1, 1)[0], "cnerf_pack_pfilm_map_transposed", torch.float32)
+
+
 PHASE_TIMER = None              # an object with begin() / end(name, start) (training.gan_step.PhaseTimer): RenderFunction.backward
                                 # reports its span as "render_bwd" so that a caller can split an autograd pass (bench.py gan_step)
 ACT_BUDGET_BYTES = 128 << 30    # chunk buffers of the per-point FiLM backward: at most this much, and MEMORY_FRACTION of what is free
@@ -366,8 +379,8 @@ def _pfilm_backward(net, o, cfg, levels, cam2world, rng, saved, gc, gf, query=No
     """Field gradients of the per-point FiLM family (TALLSIREN, siren.py:232-331).  Per pass and chunk of images
     cnerf_field_backward re-runs the forward storing its rows, runs the gradient chain of the eight FiLM layers on the MFMA
     units and leaves g_pre_l = d/d(W_l y_{l-1} + b_l) and G = d/d(output of the mapping network's second Linear) in the
-    chunk buffers (include/cnerf.h); what remains are reductions over those matrices: cnerf_weight_grad for the (H,H) layer
-    matrices, library GEMMs for the (2LH, 256) mapping Linear and the two thin ones, cnerf_scatter_features for the volume.
+    chunk buffers (include/cnerf.h); everything that remains -- the parameter gradients of the layers, the head and the mapping
+    network, d feat and its scatter into the volume's gradient -- is ONE more call per chunk, cnerf_pfilm_backward_finish.
     query = dict(points (B,n,3), g_out / saved_out (B,n,4), drop, grad_points (B,n,3) or None): the same for a field query, per
     image and range of points (query_chunk) through cnerf_field_backward_points, with the forward's dropout decisions of that
     range (cnerf_dropout_keep); grad_points receives g_pre_0 W_0 plus the lookup term of d feat (cnerf_feature_points_grad)."""
@@ -377,54 +390,41 @@ def _pfilm_backward(net, o, cfg, levels, cam2world, rng, saved, gc, gf, query=No
     vs = volumes_struct(levels)
     packed = pack_field(net, cfg)
     packed_t = pack_field_transposed(net, cfg)
+    packed_map = pack_pfilm_map(net, cfg)
     ps = [_f32(p.detach()) for p in net.field_params()]       # Wm1, bm1, Wm2, bm2, (W_l, b_l) x L, W_head, b_head
     grads = [torch.zeros_like(p) for p in ps]
+    fps, gs = _params_struct(L.FieldParams, net, ps), _params_struct(L.FieldParamGrads, net, grads)
     g_level = torch.zeros_like(fvol)
     gvs = volumes_struct([g_level])
-    per_point = (32 + 256 + 7 * nl * H + 4) * 4
+    per_point = (32 + 256 + 7 * nl * H + 4) * 4      # the chunk matrices of cnerf_field_backward; the stage's workspace: pfilm_finish_bytes
+    want_points = query is not None and query["grad_points"] is not None
+    if want_points:
+        per_point += 32 * 4
     act = None
 
-    def chunk_buffers(n):
+    def chunk_buffers(cnt, npi):
         nonlocal act
+        n = cnt * npi
         if act is None or act[0].shape[0] != n:
             act = None          # release the previous chunk before allocating a differently sized one
             act = (torch.empty((n, 32), dtype=torch.float32, device=dev),
                    torch.empty(nl * n * H + n * 256, dtype=torch.float32, device=dev),
                    torch.empty((3 * nl, n, H), dtype=torch.float32, device=dev),
                    torch.empty(3 * nl * n * H, dtype=torch.float32, device=dev),
-                   torch.empty((n, 4), dtype=torch.float32, device=dev))
-        return act
+                   torch.empty((n, 4), dtype=torch.float32, device=dev),
+                   torch.empty(pfilm_finish_bytes(cfg, cnt, npi)[1], dtype=torch.uint8, device=dev),
+                   torch.empty((n, 32), dtype=torch.float32, device=dev) if want_points else None)   # d feat rows for cnerf_feature_points_grad
+        return act[:5]
 
     def finish(b0, cnt, npi, pts, g_pts):
         """The reductions of one chunk (cnt images of npi points from image b0, positions pts (cnt*npi, 3)) and, with g_pts, its position gradient."""
-        n = cnt * npi
-        a_feat, a_h, a_c, a_g, a_go = act
-        y, m = a_h[:nl * n * H].view(nl, n, H), a_h[nl * n * H:].view(n, 256)
-        gp, G = a_g[:nl * n * H].view(nl, n, H), a_g[nl * n * H:].view(n, 2 * nl * H)
-        grads[4] += gp[0].t() @ pts                                   # layer 0 reads the sample position: (H, 3)
-        grads[5] += gp[0].sum(0)
-        for l in range(1, nl):
-            dWl = torch.zeros((cnt, H, H), dtype=torch.float32, device=dev)
-            cs = torch.zeros((cnt, H), dtype=torch.float32, device=dev)
-            L.check(L.lib().cnerf_weight_grad(cnt, npi, H, H, L.ptr(gp[l]), L.ptr(y[l - 1]), L.ptr(dWl), L.ptr(cs), _stream()),
-                    "cnerf_weight_grad")
-            grads[4 + 2 * l] += dWl.sum(0)
-            grads[5 + 2 * l] += cs.sum(0)
-        grads[4 + 2 * nl] += a_go.t() @ y[nl - 1]
-        grads[5 + 2 * nl] += a_go.sum(0)
-        # mapping network: Linear(C, 256) -> LeakyReLU(0.2) -> Linear(256, 2 L H)
-        grads[2] += G.t() @ m
-        grads[3] += G.sum(0)
-        g_m = G @ ps[2]
-        g_m *= torch.where(m > 0, 1.0, 0.2)
-        grads[0] += g_m.t() @ a_feat
-        grads[1] += g_m.sum(0)
-        d_feat = (g_m @ ps[0]).contiguous()
-        cfgc = make_cfg(net, cnt, int(fvol.shape[1]))
-        L.check(L.lib().cnerf_scatter_features(C.byref(cfgc), L.ptr(pts), npi, L.ptr(d_feat), L.ptr(g_level[b0:b0 + cnt]), _stream()),
-                "cnerf_scatter_features")
+        a_feat, a_h, a_c, a_g, a_go, ws, d_feat = act
+        L.check(L.lib().cnerf_pfilm_backward_finish(C.byref(cfg), C.byref(fps), L.ptr(packed_map), cnt, npi, L.ptr(pts), L.ptr(a_feat), L.ptr(a_h),
+                                                    L.ptr(a_g), L.ptr(a_go), C.byref(gs), L.ptr(g_level[b0:b0 + cnt]), L.ptr(d_feat), L.ptr(ws),
+                                                    _stream()), "cnerf_pfilm_backward_finish")
         if g_pts is not None:            # position: the xyz input of layer 0, then the lookup term of d feat
-            g_pts += (gp[0] @ ps[4]).view(g_pts.shape)
+            g_pts += (a_g[:cnt * npi * H].view(cnt * npi, H) @ ps[4]).view(g_pts.shape)
+            cfgc = make_cfg(net, cnt, int(fvol.shape[1]))
             L.check(L.lib().cnerf_feature_points_grad(C.byref(cfgc), C.byref(volumes_struct([fvol[b0:b0 + cnt]])), L.ptr(pts), npi, L.ptr(d_feat),
                                                       L.ptr(g_pts), _stream()), "cnerf_feature_points_grad")
 
@@ -433,13 +433,13 @@ def _pfilm_backward(net, o, cfg, levels, cam2world, rng, saved, gc, gf, query=No
         B, n = pts_all.shape[0], pts_all.shape[1]
         drop = query["drop"]
         mask_bytes = len(net.spec.layers) * H if drop is not None else 0
-        ppc, _ = query_chunk(n, lambda k: k * (per_point + mask_bytes), dev)
+        ppc, _ = query_chunk(n, lambda k: k * (per_point + mask_bytes) + pfilm_finish_bytes(cfg, 1, k)[1], dev)
         for b in range(B):
             cfgb = make_cfg(net, 1, [fvol[b:b + 1]], precision="fp32", drop=drop)
             vsb, gvsb = volumes_struct([fvol[b:b + 1]]), volumes_struct([g_level[b:b + 1]])
             for p0 in range(0, n, ppc):
                 k = min(ppc, n - p0)
-                a_feat, a_h, a_c, a_g, a_go = chunk_buffers(k)
+                a_feat, a_h, a_c, a_g, a_go = chunk_buffers(1, k)
                 mask = None
                 if drop is not None:     # the forward's keep decisions of these points (their index in the whole call)
                     mask = torch.empty((nl, k, H), dtype=torch.uint8, device=dev)
@@ -455,14 +455,14 @@ def _pfilm_backward(net, o, cfg, levels, cam2world, rng, saved, gc, gf, query=No
     B, R, S, hier = o["B"], o["R"], o["S"], o["hier"]
     npi = R * R * S
     c_rs, c_z, f_rs, f_z, c_pts, f_pts = saved[:6]
-    nb = max(1, min(B, int(min(ACT_BUDGET_BYTES, MEMORY_FRACTION * free_device_bytes(dev))) // (npi * per_point)))
+    nb = max(1, min(B, int(min(ACT_BUDGET_BYTES, MEMORY_FRACTION * free_device_bytes(dev))) // (npi * per_point + pfilm_finish_bytes(cfg, 1, npi)[1])))
     u_strat = _f32(rng.get("u_strat"))
     passes = [(0, gc, c_rs, c_pts)] + ([(1, gf, f_rs, f_pts)] if hier else [])
     for pss, g_out, saved_out, pts_all in passes:
         pts_all = pts_all.reshape(B, npi, 3)
         for b0 in range(0, B, nb):
             cnt = min(nb, B - b0)
-            a_feat, a_h, a_c, a_g, a_go = chunk_buffers(cnt * npi)
+            a_feat, a_h, a_c, a_g, a_go = chunk_buffers(cnt, npi)
             L.check(L.lib().cnerf_field_backward(C.byref(cfg), pss, b0, cnt, C.byref(vs), L.ptr(packed), L.ptr(packed_t), None, None,
                                                  L.ptr(cam2world), L.ptr(u_strat), L.ptr(f_z) if hier else None, L.ptr(g_out),
                                                  L.ptr(saved_out), L.ptr(a_feat), L.ptr(a_h), L.ptr(a_c), L.ptr(a_g), L.ptr(a_go),
@@ -580,8 +580,8 @@ def merge_composite_backward(cfg, coarse_rgb_sigma, coarse_z, fine_rgb_sigma, fi
 
 def render_backward(net, o, levels, freq, phase, cam2world, rng, saved, grad_pixels, grad_depth, act16=None):
     """Gradients of one render w.r.t. (channel-last feature volumes, freq, phase, [field parameters]): ONE call into the library
-    (cnerf_render_backward); the exact fp32 backward of the per-point FiLM family finishes its mapping-MLP gradients with library
-    GEMMs (_pfilm_backward)."""
+    (cnerf_render_backward); the exact fp32 backward of the per-point FiLM family is spelled with the library's stage calls, per pass
+    and chunk cnerf_field_backward + cnerf_pfilm_backward_finish (_pfilm_backward)."""
     global LAST_SATURATED
     B, R, S, hier = o["B"], o["R"], o["S"], o["hier"]
     dev = cam2world.device
@@ -721,8 +721,8 @@ def query_workspace_bytes(cfg, bprec_code, points_per_chunk):
 
 def query_backward(net, levels, freq, phase, points, out, grad_out, drop, want_points):
     """Gradients of one field query w.r.t. (channel-last volume levels, freq, phase, field parameters, points or None): ONE call into
-    the library (cnerf_field_query_backward); the exact fp32 backward of the per-point FiLM family finishes its mapping-MLP gradients
-    with library GEMMs (_pfilm_backward).  The backward precision and the re-run's precision follow render_backward."""
+    the library (cnerf_field_query_backward); the exact fp32 backward of the per-point FiLM family is spelled with the library's stage
+    calls (_pfilm_backward).  The backward precision and the re-run's precision follow render_backward."""
     global LAST_SATURATED
     B, n = points.shape[0], points.shape[1]
     dev = points.device

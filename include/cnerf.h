@@ -276,10 +276,11 @@ int cnerf_render_forward(const cnerf_cfg* cfg, const cnerf_volumes* vols, const 
  *             act_c  3L (n,H) slabs: per layer cos(arg), cos*freq, cos*15*pre   (private to the call)
  *             act_g  L (n,H) slabs of g_pre_l = d/d (W_l y_{l-1} + b_l), then G (n, 2*L*H) = d/d (Wm2 m + bm2), row by row in
  *                    that Linear's output order [f of layers 0..L-1 | p of layers 0..L-1]           (3*L*n*H floats)
- *         and no volume scatter (grad_vols is not touched).  The caller finishes with plain GEMMs:
- *             dW_l = act_g[l]^T y_{l-1} (cnerf_weight_grad; layer 0: y_-1 = the sample positions), db_l = colsum(act_g[l]),
+ *         and no volume scatter (grad_vols is not touched).  What remains are products over those matrices, all of them behind ONE
+ *         further call per chunk, cnerf_pfilm_backward_finish (csrc/pfilm_finish.hip; below):
+ *             dW_l = act_g[l]^T y_{l-1} (layer 0: y_-1 = the sample positions, K = 3), db_l = colsum(act_g[l]), the head's dW / db,
  *             dWm2 = G^T m, dbm2 = colsum(G), g_m = (G Wm2) * (m > 0 ? 1 : 0.2), dWm1 = g_m^T feat, dbm1 = colsum(g_m),
- *             d feat = g_m Wm1 -> cnerf_scatter_features. */
+ *             d feat = g_m Wm1, scattered into the feature volume's gradient with the trilinear weights of the sample positions. */
 
 /* packed_t: transposed packed weights for the backward; bytes via cnerf_backward_bytes. */
 int cnerf_backward_bytes(const cnerf_cfg* cfg, size_t* packed_t);
@@ -356,8 +357,8 @@ int cnerf_pack_field_chain16(const cnerf_cfg* cfg, const cnerf_field_params* par
  *   backward_precision  CNERF_PREC_FP32: exact fp32 chain and weight reductions (re-run in cfg->precision);
  *                       CNERF_PREC_FP16: fp16 operands, fp32 sums (csrc/bwd16.hip, cnerf_weight_grad16; cfg->precision must
  *                       be CNERF_PREC_FP16X3).  Per-point FiLM networks (ABI v7): CNERF_PREC_FP16 runs here (csrc/chain_pw16.hip; grads->map_*
- *                       receive the mapping network's gradients); CNERF_PREC_FP32 answers CNERF_ENOSYS -- the exact path finishes its
- *                       mapping-MLP reductions with library GEMMs on the host (cnerf_field_backward + cnerf_weight_grad + cnerf_scatter_features).
+ *                       receive the mapping network's gradients); CNERF_PREC_FP32 answers CNERF_ENOSYS -- the exact path is spelled with
+ *                       stage calls: cnerf_merge_composite_backward, then per pass and chunk cnerf_field_backward + cnerf_pfilm_backward_finish.
  *   params              the raw parameters (dfreq needs W_l and b_l);  packed: cnerf_pack_field in cfg->precision;
  *   packed_bwd          cnerf_pack_field_transposed (fp32 backward) or cnerf_pack_field_chain16 (fp16 backward).
  *   saved               the forward's coarse / fine rgb_sigma and z (cnerf_aux of that call; fine_* NULL when not hierarchical).
@@ -414,7 +415,7 @@ int cnerf_render_backward(const cnerf_cfg* cfg, int32_t backward_precision, int3
  * sits at or beyond the clamp) plus the xyz columns of TALLSIREN_dgx / TALLSIREN's layer 0.
  *   backward_precision  as cnerf_render_backward, with the same coverage: CNERF_PREC_FP32 re-runs the forward in cfg->precision,
  *                       CNERF_PREC_FP16 needs cfg->precision = CNERF_PREC_FP16X3; per-point FiLM + CNERF_PREC_FP32 answers CNERF_ENOSYS
- *                       (the host finishes that one: cnerf_field_backward_points + cnerf_feature_points_grad).
+ *                       (stage calls there: cnerf_field_backward_points, cnerf_pfilm_backward_finish, cnerf_feature_points_grad).
  *   packed / packed_bwd as cnerf_render_backward.  cfg->R, S, fov are not read (check as for cnerf_field_forward).
  *   grads, grad_freq, grad_phase, grad_vols, grad_points (B,n,3) or NULL = skip: ACCUMULATED INTO (zero them first).
  *   dropout (cfg->drop_p > 0, fp32 only): the decisions of cnerf_field_forward (stream 6 at the point's index in the whole call),
@@ -429,8 +430,8 @@ int cnerf_field_query_backward(const cnerf_cfg* cfg, int32_t backward_precision,
                                const float* grad_rgb_sigma, const cnerf_field_param_grads* grads, float* grad_freq, float* grad_phase,
                                const cnerf_grad_volumes* grad_vols, float* grad_points, uint32_t* saturated, void* workspace, void* stream);
 
-/* Stage entries of the per-point FiLM family's exact fp32 query backward (the host finishes its mapping-MLP gradients like
- * ops._pfilm_backward does for the ray passes):
+/* Stage entries of the per-point FiLM family's exact fp32 query backward (followed per chunk by cnerf_pfilm_backward_finish, as
+ * cnerf_field_backward is for the ray passes):
  *   cnerf_field_backward_points  cnerf_field_backward (pass 2) for ANY point count: points / grad_rgb_sigma / saved_rgb_sigma are
  *                                (B, n_per_image, ...) of cfg->B images (cfg->R, S unused); act_* sized for B * n_per_image rows;
  *                                drop_mask (n_drop, B * n_per_image, H) or NULL (then Philox stream 6 at index b * n_per_image + p).
@@ -445,6 +446,31 @@ int cnerf_field_backward_points(const cnerf_cfg* cfg, const cnerf_volumes* vols,
 int cnerf_feature_points_grad(const cnerf_cfg* cfg, const cnerf_volumes* vols, const float* points, int64_t n_per_image, const float* grad_feat,
                               float* grad_points, void* stream);
 int cnerf_dropout_keep(const cnerf_cfg* cfg, uint32_t stream_id, int64_t point0, int64_t n_points, uint8_t* mask, void* stream);
+
+/* Everything of the per-point FiLM family's exact fp32 backward that follows cnerf_field_backward / cnerf_field_backward_points on
+ * one chunk (n = n_images * n_per_image rows): the parameter gradients of the L layers, the head and the mapping network, d feat and
+ * its scatter.  Autograd of the mapping network and the nn.Linear layers of TALLSIREN (siren.py:81-101, 232-331) for hosts without a
+ * GEMM library; added in ABI v10 without a version change (no struct changed).
+ * cfg: PFILM network, precision FP32, one 32-channel volume (else CNERF_EINVAL; cfg->B, R, S are not read).  Chunk inputs exactly as
+ * cnerf_field_backward left them:
+ *   points (n,3)  act_feat (n,32)  act_h: L slabs y_l (n,H) then m (n,256)  act_g: L slabs g_pre_l (n,H) then G (n,2LH)  act_go (n,4)
+ * Outputs, all ACCUMULATED INTO with float atomics (NULL = skip):
+ *   grads->w[l], b[l] (layer 0: (H,3) against points), w_final, b_final, map_w1, map_b1, map_w2, map_b2
+ *   grad_fvol_cl (n_images,V,V,V,32): scatter of d feat = g_mpre Wm1 with the trilinear weights of points (image = row / n_per_image)
+ *   grad_feat (n,32) or NULL: d feat itself, OVERWRITTEN -- the very rows the scatter read (the query path feeds them to
+ *                    cnerf_feature_points_grad)
+ * params is not read (both mapping matrices come from packed_map) and may be NULL.  packed_map: written by
+ * cnerf_pack_pfilm_map_transposed from params->map_w1 / map_w2, a buffer of its own -- cnerf_backward_bytes /
+ * cnerf_pack_field_transposed keep their contents for this family.  workspace: cnerf_pfilm_finish_bytes(cfg, n_images, n_per_image);
+ * it begins with g_mpre (n,256) = (G Wm2) * (m > 0 ? 1 : 0.2), which stays readable after the call.  packed_map, act_*, grad_feat and
+ * workspace must be 16-byte aligned.  Nothing is allocated or synchronised; a bad argument returns CNERF_EINVAL and launches nothing. */
+int cnerf_pfilm_finish_bytes(const cnerf_cfg* cfg, int32_t n_images, int64_t n_per_image, size_t* packed_map, size_t* workspace);
+int cnerf_pack_pfilm_map_transposed(const cnerf_cfg* cfg, const cnerf_field_params* params, void* packed_map, void* stream);
+int cnerf_pfilm_backward_finish(const cnerf_cfg* cfg, const cnerf_field_params* params, const void* packed_map,
+                                int32_t n_images, int64_t n_per_image, const float* points, const float* act_feat,
+                                const float* act_h, const float* act_g, const float* act_go,
+                                const cnerf_field_param_grads* grads, float* grad_fvol_cl, float* grad_feat,
+                                void* workspace, void* stream);
 
 #ifdef __cplusplus
 }
