@@ -953,6 +953,64 @@ int cnerf_pack_field_chain16(const cnerf_cfg* cfg, const cnerf_field_params* p, 
     return CNERF_OK;
 }
 
+namespace {
+// Buffers of cnerf_pfilm_backward_finish (n = n_images * n_per_image rows), every piece 256-byte aligned:
+//   packed_map = [Wm2 in pfilm_gm32_kernel's A-operand order: 2 L H * 256 floats][Wm1 in its chained product's: 256 * 32 floats]
+//   workspace  = [g_mpre (n, 256)][d feat (n, 32): the rows the scatter reads when the caller passes no grad_feat]
+struct PfilmFinishLayout {
+    size_t packed_map, g_mpre, d_feat, total;
+    int K2;
+};
+int pfilm_finish_layout(const cnerf_cfg* c, int n_images, long long npi, const char* who, PfilmFinishLayout& F) {
+    if (int rc = check_cfg(c, false)) return rc;
+    if (c->layer_kind[0] != CNERF_LAYER_PFILM) return fail(CNERF_EINVAL, "%s: per-point FiLM networks only (layer 0 is of kind %d)", who, c->layer_kind[0]);
+    if (c->precision != CNERF_PREC_FP32)
+        return fail(CNERF_EINVAL, "%s: a stage of the exact fp32 backward: cfg->precision must be CNERF_PREC_FP32 (the fp16 backward runs in cnerf_render_backward)", who);
+    if (c->C != 32 || c->n_levels > 1) return fail(CNERF_EINVAL, "%s: single 32-channel volume only", who);
+    if (n_images < 1 || npi < 1) return fail(CNERF_EINVAL, "%s: empty chunk (n_images=%d, n_per_image=%lld)", who, n_images, npi);
+    const size_t n = (size_t)n_images * (size_t)npi;
+    F.K2 = 2 * c->L * c->H;
+    F.packed_map = align256(((size_t)F.K2 * 256 + 256 * 32) * sizeof(float));
+    F.g_mpre = 0;
+    F.d_feat = align256(n * 256 * sizeof(float));
+    F.total = F.d_feat + align256(n * 32 * sizeof(float));
+    return CNERF_OK;
+}
+bool misaligned16(const void* p) { return ((uintptr_t)p & 15) != 0; }
+// The stage itself (pfilm_finish.hip) on validated arguments: cnerf_pfilm_backward_finish, and the chunk body of the one-call backward
+int pfilm_finish_run(const cnerf_cfg* cfg, const PfilmFinishLayout& F, const void* packed_map, int n_images, long long n_per_image, const float* points,
+                     const float* act_feat, const float* act_h, const float* act_g, const float* act_go, const cnerf_field_param_grads* G,
+                     float* grad_fvol_cl, float* grad_feat, void* workspace, hipStream_t stream) {
+    const int H = cfg->H, Lc = cfg->L;
+    const long long n = (long long)n_images * n_per_image;
+    const size_t slab = (size_t)n * H;
+    const float* m = act_h + (size_t)Lc * slab;
+    const float* Gm = act_g + (size_t)Lc * slab;
+    float* g_mpre = (float*)((char*)workspace + F.g_mpre);
+    float* d_feat = grad_feat ? grad_feat : (float*)((char*)workspace + F.d_feat);
+    // the reductions over the chunk's rows run over all n of them at once and add to the caller's buffers themselves: no per-image partials
+    if (G->w[0] || G->b[0])
+        if (hipError_t e = launch_layer0_grad32(act_g, points, n, H, G->w[0], G->b[0], stream)) return hip_fail(e, "layer0_grad32");
+    for (int l = 1; l < Lc; ++l)
+        if (G->w[l] || G->b[l])
+            if (hipError_t e = launch_weight_grad(1, n, H, H, act_g + (size_t)l * slab, act_h + (size_t)(l - 1) * slab, G->w[l], G->b[l], stream))
+                return hip_fail(e, "weight_grad");
+    if (G->w_final || G->b_final)
+        if (hipError_t e = launch_head_grad32(act_go, act_h + (size_t)(Lc - 1) * slab, n, H, G->w_final, G->b_final, stream)) return hip_fail(e, "head_grad32");
+    if (G->map_w2 || G->map_b2)
+        if (hipError_t e = launch_weight_grad(1, n, F.K2, 256, Gm, m, G->map_w2, G->map_b2, stream)) return hip_fail(e, "weight_grad (Wm2)");
+    if (!G->map_w1 && !G->map_b1 && !grad_fvol_cl && !grad_feat) return CNERF_OK;
+    if (hipError_t e = launch_pfilm_gm32((const float*)packed_map, Gm, m, n, F.K2, g_mpre, d_feat, stream)) return hip_fail(e, "pfilm_gm32");
+    if (G->map_w1 || G->map_b1)
+        if (hipError_t e = launch_weight_grad(1, n, 256, 32, g_mpre, act_feat, G->map_w1, G->map_b1, stream)) return hip_fail(e, "weight_grad (Wm1)");
+    if (grad_fvol_cl) {
+        GatherArgs a{nullptr, points, nullptr, (long long)n_per_image, n_images, cfg->V, cfg->C, cfg->voxel_length / 2.0f};
+        if (hipError_t e = launch_scatter(a, d_feat, grad_fvol_cl, stream)) return hip_fail(e, "scatter");
+    }
+    return CNERF_OK;
+}
+}  // namespace
+
 // ---------------------------------------------------------------------------------------------------------------------
 // the whole backward in one call
 // ---------------------------------------------------------------------------------------------------------------------
@@ -963,84 +1021,82 @@ namespace {
 struct BackwardLayout {
     size_t gc, gf;                                   // d loss / d rgb_sigma of the coarse / fine samples, whole call
     size_t a_feat, a_h, a_c, a_g, a_go;              // chunk buffers (a_feat / a_h / a_c absent when the forward kept its activations)
-    size_t a_amax;                                   // per-point FiLM family: (L, T * 32) floats
-    size_t a_gy;                                     // per-point FiLM family: L TB16 slabs of g_y
+    size_t a_amax;                                   // per-point FiLM family, fp16: (L, T * 32) floats
+    size_t a_gy;                                     // per-point FiLM family, fp16: L TB16 slabs of g_y
+    size_t pts, fin, map;                            // per-point FiLM family, fp32: a ray pass's sample positions (n, 3); workspace and packed_map of
+    PfilmFinishLayout F;                             // the mapping-network stage, laid out as F for a full chunk (a smaller last chunk keeps its offsets)
     size_t a_gin;                                    // fp16 chain: (feature input tiles, chunk points, 32) fp32 input-tile gradients for scatter_patch_kernel
     size_t gmax, scales;                             // fp16: sampled maxima (n_mats + 1 uint32), {S, 1/S} pairs (n_mats + 1)
     size_t dwarg, cs, dwh, csh;                      // per-image reductions of one matrix: (cnt, H, 32 * max tiles), (cnt, H), (cnt, 4, H), (cnt, 4)
     size_t total;
     int n_mats, n_in, k0;
 };
-int chunk_layout(const cnerf_cfg* c, int bprec, int cnt, size_t npi, size_t N_out, bool hier, bool have_act16, bool gin, const char* who,
+// render: the chunks are ray passes (else the point ranges of a query, which carries its positions and has no pixel patches)
+int chunk_layout(const cnerf_cfg* c, int bprec, int cnt, size_t npi, size_t N_out, bool hier, bool have_act16, bool render, const char* who,
                  BackwardLayout& L) {
     if (bprec != CNERF_PREC_FP32 && bprec != CNERF_PREC_FP16) return fail(CNERF_EINVAL, "%s: backward_precision must be CNERF_PREC_FP32 or CNERF_PREC_FP16", who);
-    if (c->layer_kind[0] == CNERF_LAYER_PFILM && bprec != CNERF_PREC_FP16)
-        return fail(CNERF_ENOSYS, "%s: the per-point FiLM family's exact fp32 backward is spelled with stage calls (per pass and chunk "
-                                  "cnerf_field_backward, then cnerf_pfilm_backward_finish); backward_precision fp16 runs here", who);
     if (cnt < 1 || cnt > c->B) return fail(CNERF_EINVAL, "%s: images_per_chunk=%d out of [1,B]", who, cnt);
-    if (c->layer_kind[0] == CNERF_LAYER_PFILM) {      // chain_pw16.hip: three stored derivatives and three gradient slabs per layer, m and g_mpre
-        if (have_act16 && cnt != c->B) return fail(CNERF_EINVAL, "%s: kept activations need images_per_chunk = B", who);
-        if (c->precision != CNERF_PREC_FP16X3) return fail(CNERF_EINVAL, "%s: the fp16 backward re-runs the fp16x3 forward (cfg->precision)", who);
-        const size_t H = c->H, NT = H / 32, Lc = c->L, tpi = (npi + 31) / 32;
-        const size_t T = (size_t)cnt * tpi;
-        L.n_in = 2;
-        L.k0 = 3;
-        L.n_mats = c->L;
-        size_t off = 0;
-        auto take = [&](size_t bytes) { const size_t o = off; off += align256(bytes); return o; };
-        L.gc = take(N_out * 4 * sizeof(float));
-        L.gf = take(hier ? N_out * 4 * sizeof(float) : 0);
+    const bool pfilm = c->layer_kind[0] == CNERF_LAYER_PFILM, half = bprec == CNERF_PREC_FP16;
+    if (have_act16 && (!half || cnt != c->B)) return fail(CNERF_EINVAL, "%s: kept activations need the fp16 backward and images_per_chunk = B", who);
+    if (half && c->precision != CNERF_PREC_FP16X3) return fail(CNERF_EINVAL, "%s: the fp16 backward re-runs the fp16x3 forward (cfg->precision)", who);
+    if (pfilm && !half && c->precision != CNERF_PREC_FP32)
+        return fail(CNERF_EINVAL, "%s: the per-point FiLM family's fp32 chain re-runs the fp32 kernel: cfg (and packed weights) of precision fp32", who);
+    const NetCounts nc = counts_of(c);
+    const size_t H = c->H, NT = H / 32, Lc = c->L, tpi = (npi + 31) / 32;
+    const size_t n = (size_t)cnt * npi, T = (size_t)cnt * tpi;
+    L = BackwardLayout{};
+    L.n_in = pfilm ? 2 : nc.n_in;         // (per-point FiLM: the feature tile and the position's)
+    L.k0 = nc.k0;
+    L.n_mats = nc.n_mats;
+    size_t off = 0;
+    auto take = [&](size_t bytes) { const size_t o = off; off += align256(bytes); return o; };
+    L.gc = take(N_out * 4 * sizeof(float));
+    L.gf = take(hier ? N_out * 4 * sizeof(float) : 0);
+    if (pfilm && !half) {       // the chunk matrices of cnerf_field_backward (include/cnerf.h), then what the mapping-network stage needs; it
+                                // accumulates straight into the caller's gradients: no per-image reductions
+        if (int rc = pfilm_finish_layout(c, cnt, (long long)npi, who, L.F)) return rc;
+        L.a_feat = take(n * 32 * sizeof(float));
+        L.a_h = take((Lc * n * H + n * 256) * sizeof(float));
+        L.a_c = take(3 * Lc * n * H * sizeof(float));
+        L.a_g = take(3 * Lc * n * H * sizeof(float));
+        L.a_go = take(n * 4 * sizeof(float));
+        L.pts = take(render ? n * 3 * sizeof(float) : 0);
+        L.fin = take(L.F.total);
+        L.map = take(L.F.packed_map);
+        L.total = off;
+        return CNERF_OK;
+    }
+    if (pfilm) {      // chain_pw16.hip: three stored derivatives and three gradient slabs per layer, m and g_mpre
         L.a_feat = take(have_act16 ? 0 : T * 2 * 2048);
         L.a_h = take(have_act16 ? 0 : (Lc * NT + 8) * T * 2048);
         L.a_c = take(have_act16 ? 0 : 3 * Lc * NT * T * 2048);
         L.a_amax = take(have_act16 ? 0 : Lc * T * 32 * sizeof(float));
         L.a_g = take((3 * Lc * NT + 8) * T * 2048);
         L.a_go = take(T * 2048);
-        L.a_gin = 0;
         L.a_gy = take(Lc * NT * T * 2048);                          // two-kernel chain: g_y slabs
         L.gmax = take((5 * Lc + 2) * sizeof(uint32_t));             // 3 L + 2 sampled maxima, L of g_y, L of the stored derivatives
         L.scales = take((2 * (4 * Lc + 2) + 2 * Lc) * sizeof(float));   // {S, 1 / S} x (4 L + 2), then per layer {r, To}
-        L.dwarg = take((size_t)cnt * 256 * 256 * sizeof(float));
-        L.cs = take((size_t)cnt * 256 * sizeof(float));
-        L.dwh = take((size_t)cnt * 4 * H * sizeof(float));
-        L.csh = take((size_t)cnt * 4 * sizeof(float));
-        L.total = off;
-        return CNERF_OK;
-    }
-    if (have_act16 && (bprec != CNERF_PREC_FP16 || cnt != c->B)) return fail(CNERF_EINVAL, "%s: kept activations need the fp16 backward and images_per_chunk = B", who);
-    if (bprec == CNERF_PREC_FP16 && c->precision != CNERF_PREC_FP16X3) return fail(CNERF_EINVAL, "%s: the fp16 backward re-runs the fp16x3 forward (cfg->precision)", who);
-    const NetCounts nc = counts_of(c);
-    L.n_in = nc.n_in;
-    L.k0 = nc.k0;
-    L.n_mats = nc.n_mats;
-    const size_t H = c->H, NT = H / 32, tpi = (npi + 31) / 32;
-    const size_t n = (size_t)cnt * npi, T = (size_t)cnt * tpi;
-    size_t off = 0;
-    auto take = [&](size_t bytes) { const size_t o = off; off += align256(bytes); return o; };
-    L.gc = take(N_out * 4 * sizeof(float));
-    L.gf = take(hier ? N_out * 4 * sizeof(float) : 0);
-    if (bprec == CNERF_PREC_FP16) {
+    } else if (half) {
         L.a_feat = take(have_act16 ? 0 : T * L.n_in * 2048);
         L.a_h = take(have_act16 ? 0 : (size_t)L.n_mats * T * NT * 2048);
         L.a_c = take(have_act16 ? 0 : (size_t)L.n_mats * T * NT * 2048);
         L.a_g = take((size_t)L.n_mats * T * NT * 2048);
         L.a_go = take(T * 2048);
-        L.a_gin = take(gin && !no_volume(c) ? (size_t)L.n_in * n * 32 * sizeof(float) : 0);   // (no feature tile: no rows, no patch scatter)
+        L.a_gin = take(render && !no_volume(c) ? (size_t)L.n_in * n * 32 * sizeof(float) : 0);   // (no feature tile: no rows, no patch scatter)
     } else {
-        L.a_gin = 0;
         L.a_feat = take(n * 32 * L.n_in * sizeof(float));
         L.a_h = take((size_t)L.n_mats * n * H * sizeof(float));
         L.a_c = take((size_t)L.n_mats * n * H * sizeof(float));
         L.a_g = take((size_t)L.n_mats * n * H * sizeof(float));
         L.a_go = take(n * 4 * sizeof(float));
     }
-    L.a_amax = 0;
-    L.a_gy = 0;
-    L.gmax = take((size_t)(L.n_mats + 2) * sizeof(uint32_t));
-    L.scales = take((size_t)2 * (L.n_mats + 1) * sizeof(float));
-    const size_t kmax = 32 * (size_t)(L.n_in > (int)NT ? L.n_in : (int)NT);
-    L.dwarg = take((size_t)cnt * H * kmax * sizeof(float));
-    L.cs = take((size_t)cnt * H * sizeof(float));
+    if (!pfilm) {
+        L.gmax = take((size_t)(L.n_mats + 2) * sizeof(uint32_t));
+        L.scales = take((size_t)2 * (L.n_mats + 1) * sizeof(float));
+    }
+    const size_t rows = pfilm ? 256 : H, kmax = pfilm ? 256 : 32 * (size_t)(L.n_in > (int)NT ? L.n_in : (int)NT);   // the largest reduced matrix
+    L.dwarg = take((size_t)cnt * rows * kmax * sizeof(float));
+    L.cs = take((size_t)cnt * rows * sizeof(float));
     L.dwh = take((size_t)cnt * 4 * H * sizeof(float));
     L.csh = take((size_t)cnt * 4 * sizeof(float));
     L.total = off;
@@ -1124,9 +1180,9 @@ int chunk32(const cnerf_cfg* cfg, const MatrixSet& ms, const BackwardLayout& L, 
 
 // half precision, FiLM / plain-sine / residual networks (bwd16.hip): the storing re-run (fp16x3 kernel) unless the activations are given,
 // the chain's dry run for the per-matrix scales, the chain, the patch scatter of the input-tile gradients (fc.gin set), one weight_grad16
-// per matrix.  fa: the chunk's pass without gradient volumes (re-run, dry run), fc: with them.
-int chunk16(const cnerf_cfg* cfg, const MatrixSet& ms, const BackwardLayout& L, char* ws, const void* packed_bwd, FieldArgs fa, FieldArgs fc,
-            const Chunk& k, const float* g_out, const float* s_out, void* a_feat, void* a_h, void* a_c, bool store, const float* freq,
+// per matrix.  fc: the chunk's pass with gradient volumes.
+int chunk16(const cnerf_cfg* cfg, const MatrixSet& ms, const BackwardLayout& L, char* ws, const void* packed_bwd, FieldArgs fc, const Chunk& k,
+            const float* g_out, const float* s_out, void* a_feat, void* a_h, void* a_c, bool store, const float* freq,
             const cnerf_field_param_grads* G, float* grad_freq, float* grad_phase, uint32_t* saturated, hipStream_t stream) {
     const int H = cfg->H, NT = H / 32;
     const long long T = (long long)k.cnt * k.tpi;
@@ -1142,7 +1198,10 @@ int chunk16(const cnerf_cfg* cfg, const MatrixSet& ms, const BackwardLayout& L, 
     const long long groups = (long long)k.cnt * ((k.tpi + 3) / 4);
     long long step = groups / 2048;                       // dry-run sampling: every 16th tile group once there are plenty
     step = step < 1 ? 1 : (step > 16 ? 16 : step);
-    // the storing re-run and the dry run leave the gradient volumes alone; the chain (fc) adds to them
+    // the storing re-run and the dry run (fa) leave the gradient volumes alone; the chain (fc) adds to them
+    FieldArgs fa = fc;
+    for (float*& g : fa.lvl_grad) g = nullptr;
+    fa.gin = nullptr;
     if (store)
         if (hipError_t e = launch_field_h3(storing_args(fa, (long long)k.cnt * k.npi, a_feat, a_h, a_c, nullptr, a_g), H, stream))
             return hip_fail(e, "field kernel (fp16 activation store)");
@@ -1238,6 +1297,20 @@ int chunk_pw16(const cnerf_cfg* cfg, const BackwardLayout& L, char* ws, const vo
                     0, H, nullptr, 0, nullptr, nullptr, G->w_final, G->b_final, nullptr, nullptr, stream);
 }
 
+// exact fp32, per-point FiLM family: cnerf_field_backward's re-run and chain (fa as for chunk32), then the mapping-network stage
+// (pfilm_finish.hip), which adds every parameter gradient and the scatter of d feat to the caller's buffers and leaves the d feat rows
+// at ws + L.fin + L.F.d_feat.  points: the chunk's positions (n, 3), or NULL for a ray pass -- its re-run writes them into the workspace.
+int chunk_pw32(const cnerf_cfg* cfg, const BackwardLayout& L, char* ws, FieldArgs fa, const Chunk& k, const float* packed_t, const float* g_out,
+               const float* s_out, const float* points, const cnerf_field_param_grads* G, hipStream_t stream) {
+    float* a_feat = (float*)(ws + L.a_feat);
+    float* a_h = (float*)(ws + L.a_h);
+    float* a_g = (float*)(ws + L.a_g);
+    float* a_go = (float*)(ws + L.a_go);
+    if (!points) points = fa.points_out = (float*)(ws + L.pts);
+    if (int rc = field_backward_run(fa, cfg, (long long)k.cnt * k.npi, packed_t, g_out, s_out, a_feat, a_h, (float*)(ws + L.a_c), a_g, a_go, stream)) return rc;
+    return pfilm_finish_run(cfg, L.F, ws + L.map, k.cnt, k.npi, points, a_feat, a_h, a_g, a_go, G, fa.lvl_grad[0], nullptr, ws + L.fin, stream);
+}
+
 int pfilm_grads_complete(const cnerf_field_params* P, const cnerf_field_param_grads* G, int Lc, const char* who) {
     if (!P->map_w1 || !P->map_w2 || !P->w_final) return fail(CNERF_EINVAL, "%s: mapping network / head parameters are NULL", who);
     if (!G->map_w1 || !G->map_b1 || !G->map_w2 || !G->map_b2 || !G->w_final || !G->b_final)
@@ -1276,6 +1349,12 @@ int cnerf_render_backward(const cnerf_cfg* cfg, int32_t bprec, int32_t cnt_max, 
         return fail(CNERF_EINVAL, "render_backward: saved rgb_sigma / z of the forward are incomplete");
     if (counts_of(cfg).n_film && (!freq || !phase || !grad_freq || !grad_phase))
         return fail(CNERF_EINVAL, "render_backward: FiLM layers need freq, phase and their gradient buffers");
+    const bool pfilm = cfg->layer_kind[0] == CNERF_LAYER_PFILM, half = bprec == CNERF_PREC_FP16;
+    MatrixSet ms;
+    if (pfilm) {
+        if (int rc = pfilm_grads_complete(P, G, cfg->L, "render_backward")) return rc;
+        if (!half && misaligned16(workspace)) return fail(CNERF_EINVAL, "render_backward: workspace must be 16-byte aligned");
+    } else if (int rc = matrix_set(cfg, P, G, "render_backward", ms)) return rc;
     rng = rng_or_none(rng);
     hipStream_t stream = (hipStream_t)stream_;
     const int B = cfg->B;
@@ -1283,82 +1362,43 @@ int cnerf_render_backward(const cnerf_cfg* cfg, int32_t bprec, int32_t cnt_max, 
     char* ws = (char*)workspace;
     float* gc = (float*)(ws + L.gc);
     float* gf = hier ? (float*)(ws + L.gf) : nullptr;
-    char* a_go = ws + L.a_go;
 
     // 1. d(pixels, depth) -> d(rgb_sigma) of every coarse / fine sample
     if (int rc = cnerf_merge_composite_backward(cfg, saved->coarse_rgb_sigma, saved->coarse_z, saved->fine_rgb_sigma, saved->fine_z,
                                                 cfg->noise_std != 0.0f ? rng->eps_final : nullptr, grad_pixels, grad_depth, gc, gf, stream_))
         return rc;
 
-    if (cfg->layer_kind[0] == CNERF_LAYER_PFILM) {
-        // ---- per-point FiLM family, half-precision backward (chunk_pw16)
-        if (int rc = pfilm_grads_complete(P, G, cfg->L, "render_backward")) return rc;
-        if (hipError_t e = hipMemsetAsync(a_go, 0, (size_t)cnt_max * tpi * 2048, stream)) return hip_fail(e, "memset");
-        for (int pass = 0; pass < (hier ? 2 : 1); ++pass) {
-            const float* g_out = pass ? gf : gc;
-            const float* s_out = pass ? saved->fine_rgb_sigma : saved->coarse_rgb_sigma;
-            for (int b0 = 0; b0 < B; b0 += cnt_max) {
-                const int cnt = b0 + cnt_max <= B ? cnt_max : B - b0;
-                // the pass's activations: kept by the forward (all images), or re-computed into the workspace
-                char* a_feat = have_act16 ? (char*)kept->act16[pass].feat : ws + L.a_feat;
-                char* a_h = have_act16 ? (char*)kept->act16[pass].h : ws + L.a_h;
-                char* a_c = have_act16 ? (char*)kept->act16[pass].c : ws + L.a_c;
-                float* a_amax = have_act16 ? (float*)kept->act16[pass].amax : (float*)(ws + L.a_amax);
-                if (have_act16 && (!a_feat || !a_h || !a_c || !a_amax)) return fail(CNERF_EINVAL, "render_backward: act16 of pass %d is incomplete", pass);
-                FieldArgs fa;
-                if (int rc = pass_args(fa, cfg, pass, b0, cnt, vols, grad_vols, packed, nullptr, nullptr, cam2world, rng->u_strat, saved->fine_z)) return rc;
-                if (int rc = chunk_pw16(cfg, L, ws, packed_bwd, fa, Chunk{b0, cnt, npi, tpi}, g_out + (size_t)b0 * npi * 4, s_out + (size_t)b0 * npi * 4,
-                                        a_feat, a_h, a_c, a_amax, !have_act16, G, saturated, stream))
-                    return rc;
-            }
-        }
-        return CNERF_OK;
-    }
+    if (pfilm && !half)      // the mapping-network stage's operands, packed once per call
+        if (hipError_t e = launch_pack_pfilm_map(P->map_w1, P->map_w2, L.F.K2, (float*)(ws + L.map), stream)) return hip_fail(e, "pack_pfilm_map");
+    // half precision: only channels 0..3 of a row of the head gradient are ever written: the rest must read as zero
+    if (half)
+        if (hipError_t e = hipMemsetAsync(ws + L.a_go, 0, (size_t)cnt_max * tpi * 2048, stream)) return hip_fail(e, "memset");
+    // FiLM / plain-sine / residual networks in half precision: the chain stores its input-tile gradients (fp32, 128 B per point) and
+    // scatter_sorted_kernel adds them to the volume pre-reduced per pixel patch (scatter_patch.hip), or the chain adds them itself
+    // (CNERF_SCATTER=chain; a network without a volume has nothing to scatter)
+    float* gin = half && !pfilm && !scatter_by_chain() && !nv ? (float*)(ws + L.a_gin) : nullptr;
 
-    MatrixSet ms;
-    if (int rc = matrix_set(cfg, P, G, "render_backward", ms)) return rc;
-
-    if (bprec == CNERF_PREC_FP16) {
-        // ---- FiLM / plain-sine / residual networks, half-precision backward (chunk16); the chain stores its input-tile gradients (fp32,
-        // 128 B per point) and scatter_sorted_kernel adds them to the volume pre-reduced per pixel patch (scatter_patch.hip), or the chain
-        // adds them itself (CNERF_SCATTER=chain)
-        float* gin = (float*)(ws + L.a_gin);
-        const bool patch = !scatter_by_chain() && !nv;      // (a network without a volume has nothing to scatter)
-        // only channels 0..3 of a row are ever written: the rest must read as zero
-        if (hipError_t e = hipMemsetAsync(a_go, 0, (size_t)cnt_max * tpi * 2048, stream)) return hip_fail(e, "memset");
-        for (int pass = 0; pass < (hier ? 2 : 1); ++pass) {
-            const float* g_out = pass ? gf : gc;
-            const float* s_out = pass ? saved->fine_rgb_sigma : saved->coarse_rgb_sigma;
-            for (int b0 = 0; b0 < B; b0 += cnt_max) {
-                const int cnt = b0 + cnt_max <= B ? cnt_max : B - b0;
-                void* a_feat = have_act16 ? kept->act16[pass].feat : (void*)(ws + L.a_feat);
-                void* a_h = have_act16 ? kept->act16[pass].h : (void*)(ws + L.a_h);
-                void* a_c = have_act16 ? kept->act16[pass].c : (void*)(ws + L.a_c);
-                if (have_act16 && (!a_feat || !a_h || !a_c)) return fail(CNERF_EINVAL, "render_backward: act16 of pass %d is incomplete", pass);
-                FieldArgs fa, fc;
-                if (int rc = pass_args(fa, cfg, pass, b0, cnt, vols, nullptr, packed, freq, phase, cam2world, rng->u_strat, saved->fine_z)) return rc;
-                if (int rc = pass_args(fc, cfg, pass, b0, cnt, vols, grad_vols, packed, freq, phase, cam2world, rng->u_strat, saved->fine_z)) return rc;
-                fc.gin = patch ? gin : nullptr;
-                if (int rc = chunk16(cfg, ms, L, ws, packed_bwd, fa, fc, Chunk{b0, cnt, npi, tpi}, g_out + (size_t)b0 * npi * 4, s_out + (size_t)b0 * npi * 4,
-                                     a_feat, a_h, a_c, !have_act16, freq, G, grad_freq, grad_phase, saturated, stream))
-                    return rc;
-            }
-        }
-        return CNERF_OK;
-    }
-
-    // ---- exact fp32 backward (chunk32)
+    // 2. per ray pass and chunk of images: the chunk body of the layer family and backward precision
     for (int pass = 0; pass < (hier ? 2 : 1); ++pass) {
-        const float* g_out = pass ? gf : gc;
-        const float* s_out = pass ? saved->fine_rgb_sigma : saved->coarse_rgb_sigma;
-        const uint8_t* drop = pass ? rng->drop_fine : rng->drop_coarse;
         for (int b0 = 0; b0 < B; b0 += cnt_max) {
-            const int cnt = b0 + cnt_max <= B ? cnt_max : B - b0;
-            FieldArgs fa;
-            if (int rc = pass_args(fa, cfg, pass, b0, cnt, vols, grad_vols, packed, freq, phase, cam2world, rng->u_strat, saved->fine_z)) return rc;
-            set_dropout(fa, cfg, drop, pass == 0 ? PHILOX_DROP_COARSE : PHILOX_DROP_FINE, npi);
-            if (int rc = chunk32(cfg, ms, L, ws, fa, Chunk{b0, cnt, npi, tpi}, (const float*)packed_bwd, g_out + (size_t)b0 * npi * 4,
-                                 s_out + (size_t)b0 * npi * 4, freq, G, grad_freq, grad_phase, stream))
+            const Chunk k{b0, b0 + cnt_max <= B ? cnt_max : B - b0, npi, tpi};
+            const float* g_out = (pass ? gf : gc) + (size_t)b0 * npi * 4;
+            const float* s_out = (pass ? saved->fine_rgb_sigma : saved->coarse_rgb_sigma) + (size_t)b0 * npi * 4;
+            FieldArgs fa;       // the chunk's pass with the gradient volumes; dropout is the fp32 kernels' alone
+            if (int rc = pass_args(fa, cfg, pass, b0, k.cnt, vols, grad_vols, packed, freq, phase, cam2world, rng->u_strat, saved->fine_z)) return rc;
+            if (!half) set_dropout(fa, cfg, pass ? rng->drop_fine : rng->drop_coarse, pass ? PHILOX_DROP_FINE : PHILOX_DROP_COARSE, npi);
+            fa.gin = gin;
+            // the pass's activations (fp16 backward): kept by the forward (all images), or re-computed into the workspace
+            char* a_feat = have_act16 ? (char*)kept->act16[pass].feat : ws + L.a_feat;
+            char* a_h = have_act16 ? (char*)kept->act16[pass].h : ws + L.a_h;
+            char* a_c = have_act16 ? (char*)kept->act16[pass].c : ws + L.a_c;
+            float* a_amax = have_act16 ? (float*)kept->act16[pass].amax : (float*)(ws + L.a_amax);
+            if (have_act16 && (!a_feat || !a_h || !a_c || (pfilm && !a_amax))) return fail(CNERF_EINVAL, "render_backward: act16 of pass %d is incomplete", pass);
+            if (int rc = pfilm && half ? chunk_pw16(cfg, L, ws, packed_bwd, fa, k, g_out, s_out, a_feat, a_h, a_c, a_amax, !have_act16, G, saturated, stream)
+                       : pfilm         ? chunk_pw32(cfg, L, ws, fa, k, (const float*)packed_bwd, g_out, s_out, nullptr, G, stream)
+                       : half          ? chunk16(cfg, ms, L, ws, packed_bwd, fa, k, g_out, s_out, a_feat, a_h, a_c, !have_act16, freq, G, grad_freq, grad_phase,
+                                                 saturated, stream)
+                                       : chunk32(cfg, ms, L, ws, fa, k, (const float*)packed_bwd, g_out, s_out, freq, G, grad_freq, grad_phase, stream))
                 return rc;
         }
     }
@@ -1415,19 +1455,23 @@ int cnerf_field_query_backward(const cnerf_cfg* cfg, int32_t bprec, int64_t poin
     if (pfilm) {
         if (int rc = pfilm_grads_complete(P, G, cfg->L, "field_query_backward")) return rc;
         if (grad_points && !P->w[0]) return fail(CNERF_EINVAL, "field_query_backward: layer 0 weight is NULL");
+        if (bprec == CNERF_PREC_FP32 && misaligned16(workspace)) return fail(CNERF_EINVAL, "field_query_backward: workspace must be 16-byte aligned");
     }
     MatrixSet ms;
     if (!pfilm)
         if (int rc = matrix_set(cfg, P, G, "field_query_backward", ms)) return rc;
     hipStream_t stream = (hipStream_t)stream_;
+    const bool half = bprec == CNERF_PREC_FP16;
     const int B = cfg->B, H = cfg->H, NT = H / 32;
     const long long n = (long long)n_per_image, ppc = points_per_chunk < n ? (long long)points_per_chunk : n;
     char* ws = (char*)workspace;
     float* rows = (float*)(ws + Q.rows);
     uint8_t* mask = (uint8_t*)(ws + Q.mask);
     // only channels 0..3 of a row of the half-precision head gradient are ever written: the rest must read as zero
-    if (bprec == CNERF_PREC_FP16)
+    if (half)
         if (hipError_t e = hipMemsetAsync(ws + L.a_go, 0, (size_t)((ppc + 31) / 32) * 2048, stream)) return hip_fail(e, "memset");
+    if (pfilm && !half)      // the mapping-network stage's operands, packed once per call
+        if (hipError_t e = launch_pack_pfilm_map(P->map_w1, P->map_w2, L.F.K2, (float*)(ws + L.map), stream)) return hip_fail(e, "pack_pfilm_map");
     for (int b = 0; b < B; ++b) {
         for (long long p0 = 0; p0 < n; p0 += ppc) {
             const long long np = p0 + ppc <= n ? ppc : n - p0;
@@ -1436,9 +1480,10 @@ int cnerf_field_query_backward(const cnerf_cfg* cfg, int32_t bprec, int64_t poin
             const float* pts = points + row0 * 3;
             const float* g_out = grad_rgb_sigma + row0 * 4;
             const float* s_out = saved_rgb_sigma + row0 * 4;
-            // the chunk's field pass: image b, points [p0, p0 + np); fa without, fc with the gradient volumes
-            FieldArgs fa, fc;
-            if (int rc = points_args(fa, cfg, vols, nullptr, packed, freq, phase, pts, b, 1, np, nullptr)) return rc;
+            // the chunk's field pass: image b, points [p0, p0 + np), with the gradient volumes; points are no pixel patches: the half-
+            // precision chain adds its input-tile gradients with its own atomics (fa.gin stays NULL)
+            FieldArgs fa;
+            if (int rc = points_args(fa, cfg, vols, grad_vols, packed, freq, phase, pts, b, 1, np, nullptr)) return rc;
             if (cfg->drop_p > 0.0f) {
                 // the forward's decisions of these points (Philox stream PHILOX_DROP_POINTS at their index in the whole call), as keep bytes
                 // with chunk-local rows: the kernels index them by (image0 + b) * n_per_image + point = the point's row in the chunk
@@ -1448,61 +1493,53 @@ int cnerf_field_query_backward(const cnerf_cfg* cfg, int32_t bprec, int64_t poin
                 fa.drop_points = np;
                 fa.image0 = 0;
             }
-            fc = fa;
-            for (int i = 0; i < n_levels_of(cfg); ++i) fc.lvl_grad[i] = grad_vols->level[i] + (size_t)b * level_floats(cfg, i);
-            fc.gin = nullptr;            // points are no pixel patches: the chain adds its input-tile gradients with its own atomics
-            if (pfilm) {
-                if (int rc = chunk_pw16(cfg, L, ws, packed_bwd, fc, k, g_out, s_out, ws + L.a_feat, ws + L.a_h, ws + L.a_c, (float*)(ws + L.a_amax), true, G,
-                                        saturated, stream))
-                    return rc;
-            } else if (bprec == CNERF_PREC_FP16) {
-                if (int rc = chunk16(cfg, ms, L, ws, packed_bwd, fa, fc, k, g_out, s_out, ws + L.a_feat, ws + L.a_h, ws + L.a_c, true, freq, G, grad_freq,
-                                     grad_phase, saturated, stream))
-                    return rc;
-            } else {
-                if (int rc = chunk32(cfg, ms, L, ws, fc, k, (const float*)packed_bwd, g_out, s_out, freq, G, grad_freq, grad_phase, stream)) return rc;
-            }
+            if (int rc = pfilm && half ? chunk_pw16(cfg, L, ws, packed_bwd, fa, k, g_out, s_out, ws + L.a_feat, ws + L.a_h, ws + L.a_c, (float*)(ws + L.a_amax),
+                                                    true, G, saturated, stream)
+                       : pfilm         ? chunk_pw32(cfg, L, ws, fa, k, (const float*)packed_bwd, g_out, s_out, pts, G, stream)
+                       : half          ? chunk16(cfg, ms, L, ws, packed_bwd, fa, k, g_out, s_out, ws + L.a_feat, ws + L.a_h, ws + L.a_c, true, freq, G,
+                                                 grad_freq, grad_phase, saturated, stream)
+                                       : chunk32(cfg, ms, L, ws, fa, k, (const float*)packed_bwd, g_out, s_out, freq, G, grad_freq, grad_phase, stream))
+                return rc;
             if (!grad_points) continue;
-            // position gradient: layer 0's input gradient from the chunk's layer-0 gradient slab, then its lookup term plus the xyz columns
+            // position gradient: layer 0's input gradient [feature | xyz] = (g_0 (.) freq_0) W_0 from the chunk's layer-0 gradient slab, then
+            // its lookup term plus the xyz columns.  Per-point FiLM: layer 0 reads the position alone (g_pre_0 W_0), the feature columns
+            // are g_mpre Wm1 -- fp16: slot 3 L, 8 channel tiles; fp32: the d feat rows the mapping-network stage left
             const float* scales = (const float*)(ws + L.scales);
+            const float* gfeat = rows;
+            int ldf = 256;
             InputGradArgs ig{};
             ig.out = rows;
             ig.ldo = 256;
             ig.n = np;
-            if (pfilm) {        // feature: g_mpre Wm1 (slot 3 L, 8 channel tiles); xyz: g_pre_0 W_0 (slot 0)
-                const size_t slabH = (size_t)k.tpi * NT * 2048;
-                ig.g16 = ws + L.a_g + (size_t)(3 * cfg->L) * slabH;
+            if (pfilm && half) {
+                ig.g16 = ws + L.a_g + (size_t)(3 * cfg->L) * k.tpi * NT * 2048;
                 ig.g_ct = 8;
                 ig.inv_scale = scales + 2 * (3 * cfg->L) + 1;
                 ig.W = P->map_w1;
                 ig.K = 256;
                 ig.k_in = cfg->C;
                 if (hipError_t e = launch_input_grad(ig, stream)) return hip_fail(e, "input_grad");
+            } else if (pfilm) {
+                gfeat = (const float*)(ws + L.fin + L.F.d_feat);
+                ldf = 32;
+            }
+            if (half) {
                 ig.g16 = ws + L.a_g;
                 ig.g_ct = NT;
                 ig.inv_scale = scales + 1;
-                ig.W = P->w[0];
-                ig.K = H;
-                ig.k_in = 3;
-                ig.out = rows + cfg->C;
-            } else {            // [feature | xyz] = (g_arg_0 (.) freq_0) W_0
-                if (bprec == CNERF_PREC_FP16) {
-                    ig.g16 = ws + L.a_g;
-                    ig.g_ct = NT;
-                    ig.inv_scale = scales + 1;
-                } else {
-                    ig.g32 = (const float*)(ws + L.a_g);
-                    ig.ldg = H;
-                }
-                ig.f = ms.film(freq, 0, b);
-                ig.W = ms.W[0];
-                ig.K = H;
-                ig.k_in = L.k0;
+            } else {
+                ig.g32 = (const float*)(ws + L.a_g);
+                ig.ldg = H;
             }
+            ig.f = pfilm ? nullptr : ms.film(freq, 0, b);
+            ig.W = pfilm ? P->w[0] : ms.W[0];
+            ig.K = H;
+            ig.k_in = L.k0;
+            ig.out = pfilm ? rows + cfg->C : rows;
             if (hipError_t e = launch_input_grad(ig, stream)) return hip_fail(e, "input_grad");
             PointsGradArgs pg = points_grad_args(cfg, vols, b, pts, grad_points + row0 * 3, np);
-            pg.gfeat = rows;
-            pg.ldf = 256;
+            pg.gfeat = gfeat;
+            pg.ldf = ldf;
             pg.gxyz = (pfilm || (cfg->flags & (CNERF_F_INPUT_XYZ | CNERF_F_NO_VOLUME))) ? rows + cfg->C : nullptr;   // (no volume: C = 0, the xyz term alone)
             pg.ldx = 256;
             if (hipError_t e = launch_points_lookup_grad(pg, stream)) return hip_fail(e, "points_lookup_grad");
@@ -1541,36 +1578,6 @@ int cnerf_dropout_keep(const cnerf_cfg* cfg, uint32_t stream_id, int64_t point0,
     return CNERF_OK;
 }
 
-}  // extern "C"
-
-namespace {
-// Buffers of cnerf_pfilm_backward_finish (n = n_images * n_per_image rows), every piece 256-byte aligned:
-//   packed_map = [Wm2 in pfilm_gm32_kernel's A-operand order: 2 L H * 256 floats][Wm1 in its chained product's: 256 * 32 floats]
-//   workspace  = [g_mpre (n, 256)][d feat (n, 32): the rows the scatter reads when the caller passes no grad_feat]
-struct PfilmFinishLayout {
-    size_t packed_map, g_mpre, d_feat, total;
-    int K2;
-};
-int pfilm_finish_layout(const cnerf_cfg* c, int n_images, long long npi, const char* who, PfilmFinishLayout& F) {
-    if (int rc = check_cfg(c, false)) return rc;
-    if (c->layer_kind[0] != CNERF_LAYER_PFILM) return fail(CNERF_EINVAL, "%s: per-point FiLM networks only (layer 0 is of kind %d)", who, c->layer_kind[0]);
-    if (c->precision != CNERF_PREC_FP32)
-        return fail(CNERF_EINVAL, "%s: a stage of the exact fp32 backward: cfg->precision must be CNERF_PREC_FP32 (the fp16 backward runs in cnerf_render_backward)", who);
-    if (c->C != 32 || c->n_levels > 1) return fail(CNERF_EINVAL, "%s: single 32-channel volume only", who);
-    if (n_images < 1 || npi < 1) return fail(CNERF_EINVAL, "%s: empty chunk (n_images=%d, n_per_image=%lld)", who, n_images, npi);
-    const size_t n = (size_t)n_images * (size_t)npi;
-    F.K2 = 2 * c->L * c->H;
-    F.packed_map = align256(((size_t)F.K2 * 256 + 256 * 32) * sizeof(float));
-    F.g_mpre = 0;
-    F.d_feat = align256(n * 256 * sizeof(float));
-    F.total = F.d_feat + align256(n * 32 * sizeof(float));
-    return CNERF_OK;
-}
-bool misaligned16(const void* p) { return ((uintptr_t)p & 15) != 0; }
-}  // namespace
-
-extern "C" {
-
 int cnerf_pfilm_finish_bytes(const cnerf_cfg* cfg, int32_t n_images, int64_t n_per_image, size_t* packed_map, size_t* workspace) {
     g_err[0] = 0;
     PfilmFinishLayout F;
@@ -1602,34 +1609,8 @@ int cnerf_pfilm_backward_finish(const cnerf_cfg* cfg, const cnerf_field_params* 
     if (misaligned16(packed_map) || misaligned16(act_feat) || misaligned16(act_h) || misaligned16(act_g) || misaligned16(act_go) || misaligned16(grad_feat) ||
         misaligned16(workspace))
         return fail(CNERF_EINVAL, "pfilm_backward_finish: packed_map, act_*, grad_feat and workspace must be 16-byte aligned");
-    hipStream_t stream = (hipStream_t)stream_;
-    const int H = cfg->H, Lc = cfg->L;
-    const long long n = (long long)n_images * n_per_image;
-    const size_t slab = (size_t)n * H;
-    const float* m = act_h + (size_t)Lc * slab;
-    const float* Gm = act_g + (size_t)Lc * slab;
-    float* g_mpre = (float*)((char*)workspace + F.g_mpre);
-    float* d_feat = grad_feat ? grad_feat : (float*)((char*)workspace + F.d_feat);
-    // the reductions over the chunk's rows run over all n of them at once and add to the caller's buffers themselves: no per-image partials
-    if (G->w[0] || G->b[0])
-        if (hipError_t e = launch_layer0_grad32(act_g, points, n, H, G->w[0], G->b[0], stream)) return hip_fail(e, "layer0_grad32");
-    for (int l = 1; l < Lc; ++l)
-        if (G->w[l] || G->b[l])
-            if (hipError_t e = launch_weight_grad(1, n, H, H, act_g + (size_t)l * slab, act_h + (size_t)(l - 1) * slab, G->w[l], G->b[l], stream))
-                return hip_fail(e, "weight_grad");
-    if (G->w_final || G->b_final)
-        if (hipError_t e = launch_head_grad32(act_go, act_h + (size_t)(Lc - 1) * slab, n, H, G->w_final, G->b_final, stream)) return hip_fail(e, "head_grad32");
-    if (G->map_w2 || G->map_b2)
-        if (hipError_t e = launch_weight_grad(1, n, F.K2, 256, Gm, m, G->map_w2, G->map_b2, stream)) return hip_fail(e, "weight_grad (Wm2)");
-    if (!G->map_w1 && !G->map_b1 && !grad_fvol_cl && !grad_feat) return CNERF_OK;
-    if (hipError_t e = launch_pfilm_gm32((const float*)packed_map, Gm, m, n, F.K2, g_mpre, d_feat, stream)) return hip_fail(e, "pfilm_gm32");
-    if (G->map_w1 || G->map_b1)
-        if (hipError_t e = launch_weight_grad(1, n, 256, 32, g_mpre, act_feat, G->map_w1, G->map_b1, stream)) return hip_fail(e, "weight_grad (Wm1)");
-    if (grad_fvol_cl) {
-        GatherArgs a{nullptr, points, nullptr, (long long)n_per_image, n_images, cfg->V, cfg->C, cfg->voxel_length / 2.0f};
-        if (hipError_t e = launch_scatter(a, d_feat, grad_fvol_cl, stream)) return hip_fail(e, "scatter");
-    }
-    return CNERF_OK;
+    return pfilm_finish_run(cfg, F, packed_map, n_images, (long long)n_per_image, points, act_feat, act_h, act_g, act_go, G, grad_fvol_cl, grad_feat, workspace,
+                            (hipStream_t)stream_);
 }
 
 }  // extern "C"

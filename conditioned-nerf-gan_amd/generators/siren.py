@@ -178,8 +178,9 @@ class TALLSIREN(FieldNetwork):
     """pi-GAN style field (siren.py:232-331): input = world xyz, eight FiLM layers whose frequencies / phases come per
     POINT from a mapping MLP of the looked-up feature (z is the bare feature volume, z_dim = its channel count).
     Parameters, names and initialisation mirror the reference so its checkpoints load.  Forward: field_pw_kernel (fp32) or
-    field_pw16_kernel (fp16x3 / fp16); backward: storing forward + field_pw_backward_kernel + cnerf_pfilm_backward_finish (fp32,
-    ops._pfilm_backward) or chain_pre_kernel + pw_gm_kernel + weight_grad16 behind cnerf_render_backward (backward_precision "fp16")."""
+    field_pw16_kernel (fp16x3 / fp16); backward: storing forward + field_pw_backward_kernel + the mapping-network stage
+    (pfilm_finish.hip; fp32) or chain_pre_kernel + pw_gm_kernel + weight_grad16 (backward_precision "fp16"), both behind
+    cnerf_render_backward."""
     variant = "TALLSIREN"
     spec = FieldSpec(("pfilm",) * 8, 25, False, False, False, "xyz")
 

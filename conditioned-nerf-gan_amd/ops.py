@@ -357,119 +357,9 @@ def pack_field_transposed(net, cfg):
     return _cached_pack(net, cfg, "transposed", lambda: _abi_bytes("cnerf_backward_bytes", cfg), "cnerf_pack_field_transposed", torch.float32)
 
 
-def pfilm_finish_bytes(cfg, n_images, n_per_image):
-    """(packed_map bytes, workspace bytes) of cnerf_pfilm_backward_finish on a chunk of n_images x n_per_image rows."""
-    pm, ws = C.c_size_t(0), C.c_size_t(0)
-    L.check(L.lib().cnerf_pfilm_finish_bytes(C.byref(cfg), int(n_images), int(n_per_image), C.byref(pm), C.byref(ws)), "cnerf_pfilm_finish_bytes")
-    return pm.value, ws.value
-
-
-def pack_pfilm_map(net, cfg):
-    """Both matrices of the per-point FiLM family's mapping network in the operand order of its exact backward's stage
-    (cnerf_pack_pfilm_map_transposed)."""
-    return _cached_pack(net, cfg, "pfilm_map", lambda: pfilm_finish_bytes(cfg, 1, 1)[0], "cnerf_pack_pfilm_map_transposed", torch.float32)
-
-
 PHASE_TIMER = None              # an object with begin() / end(name, start) (training.gan_step.PhaseTimer): RenderFunction.backward
                                 # reports its span as "render_bwd" so that a caller can split an autograd pass (bench.py gan_step)
-ACT_BUDGET_BYTES = 128 << 30    # chunk buffers of the per-point FiLM backward: at most this much, and MEMORY_FRACTION of what is free
-
-
-def _pfilm_backward(net, o, cfg, levels, cam2world, rng, saved, gc, gf, query=None):
-    """Field gradients of the per-point FiLM family (TALLSIREN, siren.py:232-331).  Per pass and chunk of images
-    cnerf_field_backward re-runs the forward storing its rows, runs the gradient chain of the eight FiLM layers on the MFMA
-    units and leaves g_pre_l = d/d(W_l y_{l-1} + b_l) and G = d/d(output of the mapping network's second Linear) in the
-    chunk buffers (include/cnerf.h); everything that remains -- the parameter gradients of the layers, the head and the mapping
-    network, d feat and its scatter into the volume's gradient -- is ONE more call per chunk, cnerf_pfilm_backward_finish.
-    query = dict(points (B,n,3), g_out / saved_out (B,n,4), drop, grad_points (B,n,3) or None): the same for a field query, per
-    image and range of points (query_chunk) through cnerf_field_backward_points, with the forward's dropout decisions of that
-    range (cnerf_dropout_keep); grad_points receives g_pre_0 W_0 plus the lookup term of d feat (cnerf_feature_points_grad)."""
-    fvol = levels[0]
-    dev = fvol.device
-    H, nl = int(net.hidden_dim), len(net.spec.layers)
-    vs = volumes_struct(levels)
-    packed = pack_field(net, cfg)
-    packed_t = pack_field_transposed(net, cfg)
-    packed_map = pack_pfilm_map(net, cfg)
-    ps = [_f32(p.detach()) for p in net.field_params()]       # Wm1, bm1, Wm2, bm2, (W_l, b_l) x L, W_head, b_head
-    grads = [torch.zeros_like(p) for p in ps]
-    fps, gs = _params_struct(L.FieldParams, net, ps), _params_struct(L.FieldParamGrads, net, grads)
-    g_level = torch.zeros_like(fvol)
-    gvs = volumes_struct([g_level])
-    per_point = (32 + 256 + 7 * nl * H + 4) * 4      # the chunk matrices of cnerf_field_backward; the stage's workspace: pfilm_finish_bytes
-    want_points = query is not None and query["grad_points"] is not None
-    if want_points:
-        per_point += 32 * 4
-    act = None
-
-    def chunk_buffers(cnt, npi):
-        nonlocal act
-        n = cnt * npi
-        if act is None or act[0].shape[0] != n:
-            act = None          # release the previous chunk before allocating a differently sized one
-            act = (torch.empty((n, 32), dtype=torch.float32, device=dev),
-                   torch.empty(nl * n * H + n * 256, dtype=torch.float32, device=dev),
-                   torch.empty((3 * nl, n, H), dtype=torch.float32, device=dev),
-                   torch.empty(3 * nl * n * H, dtype=torch.float32, device=dev),
-                   torch.empty((n, 4), dtype=torch.float32, device=dev),
-                   torch.empty(pfilm_finish_bytes(cfg, cnt, npi)[1], dtype=torch.uint8, device=dev),
-                   torch.empty((n, 32), dtype=torch.float32, device=dev) if want_points else None)   # d feat rows for cnerf_feature_points_grad
-        return act[:5]
-
-    def finish(b0, cnt, npi, pts, g_pts):
-        """The reductions of one chunk (cnt images of npi points from image b0, positions pts (cnt*npi, 3)) and, with g_pts, its position gradient."""
-        a_feat, a_h, a_c, a_g, a_go, ws, d_feat = act
-        L.check(L.lib().cnerf_pfilm_backward_finish(C.byref(cfg), C.byref(fps), L.ptr(packed_map), cnt, npi, L.ptr(pts), L.ptr(a_feat), L.ptr(a_h),
-                                                    L.ptr(a_g), L.ptr(a_go), C.byref(gs), L.ptr(g_level[b0:b0 + cnt]), L.ptr(d_feat), L.ptr(ws),
-                                                    _stream()), "cnerf_pfilm_backward_finish")
-        if g_pts is not None:            # position: the xyz input of layer 0, then the lookup term of d feat
-            g_pts += (a_g[:cnt * npi * H].view(cnt * npi, H) @ ps[4]).view(g_pts.shape)
-            cfgc = make_cfg(net, cnt, int(fvol.shape[1]))
-            L.check(L.lib().cnerf_feature_points_grad(C.byref(cfgc), C.byref(volumes_struct([fvol[b0:b0 + cnt]])), L.ptr(pts), npi, L.ptr(d_feat),
-                                                      L.ptr(g_pts), _stream()), "cnerf_feature_points_grad")
-
-    if query is not None:
-        pts_all, g_all, s_all, g_pts = query["points"], query["g_out"], query["saved_out"], query["grad_points"]
-        B, n = pts_all.shape[0], pts_all.shape[1]
-        drop = query["drop"]
-        mask_bytes = len(net.spec.layers) * H if drop is not None else 0
-        ppc, _ = query_chunk(n, lambda k: k * (per_point + mask_bytes) + pfilm_finish_bytes(cfg, 1, k)[1], dev)
-        for b in range(B):
-            cfgb = make_cfg(net, 1, [fvol[b:b + 1]], precision="fp32", drop=drop)
-            vsb, gvsb = volumes_struct([fvol[b:b + 1]]), volumes_struct([g_level[b:b + 1]])
-            for p0 in range(0, n, ppc):
-                k = min(ppc, n - p0)
-                a_feat, a_h, a_c, a_g, a_go = chunk_buffers(1, k)
-                mask = None
-                if drop is not None:     # the forward's keep decisions of these points (their index in the whole call)
-                    mask = torch.empty((nl, k, H), dtype=torch.uint8, device=dev)
-                    L.check(L.lib().cnerf_dropout_keep(C.byref(cfg), 6, b * n + p0, k, L.ptr(mask), _stream()), "cnerf_dropout_keep")
-                pts = pts_all[b, p0:p0 + k]
-                L.check(L.lib().cnerf_field_backward_points(C.byref(cfgb), C.byref(vsb), L.ptr(packed), L.ptr(packed_t), None, None, L.ptr(pts), k,
-                                                            L.ptr(g_all[b, p0:p0 + k]), L.ptr(s_all[b, p0:p0 + k]), L.ptr(a_feat), L.ptr(a_h),
-                                                            L.ptr(a_c), L.ptr(a_g), L.ptr(a_go), C.byref(gvsb), L.ptr(mask), _stream()),
-                        "cnerf_field_backward_points")
-                finish(b, 1, k, pts, g_pts[b, p0:p0 + k] if g_pts is not None else None)
-        return [g_level], None, None, grads
-
-    B, R, S, hier = o["B"], o["R"], o["S"], o["hier"]
-    npi = R * R * S
-    c_rs, c_z, f_rs, f_z, c_pts, f_pts = saved[:6]
-    nb = max(1, min(B, int(min(ACT_BUDGET_BYTES, MEMORY_FRACTION * free_device_bytes(dev))) // (npi * per_point + pfilm_finish_bytes(cfg, 1, npi)[1])))
-    u_strat = _f32(rng.get("u_strat"))
-    passes = [(0, gc, c_rs, c_pts)] + ([(1, gf, f_rs, f_pts)] if hier else [])
-    for pss, g_out, saved_out, pts_all in passes:
-        pts_all = pts_all.reshape(B, npi, 3)
-        for b0 in range(0, B, nb):
-            cnt = min(nb, B - b0)
-            a_feat, a_h, a_c, a_g, a_go = chunk_buffers(cnt, npi)
-            L.check(L.lib().cnerf_field_backward(C.byref(cfg), pss, b0, cnt, C.byref(vs), L.ptr(packed), L.ptr(packed_t), None, None,
-                                                 L.ptr(cam2world), L.ptr(u_strat), L.ptr(f_z) if hier else None, L.ptr(g_out),
-                                                 L.ptr(saved_out), L.ptr(a_feat), L.ptr(a_h), L.ptr(a_c), L.ptr(a_g), L.ptr(a_go),
-                                                 C.byref(gvs), L.ptr(_u8(rng.get("drop_fine" if pss else "drop_coarse"))), _stream()),
-                    "cnerf_field_backward")
-            finish(b0, cnt, npi, pts_all[b0:b0 + cnt].reshape(cnt * npi, 3), None)
-    return [g_level], None, None, grads
+ACT_BUDGET_BYTES = 128 << 30    # chunk buffers of the per-point FiLM family's fp32 backward: at most this much, and MEMORY_FRACTION of what is free
 
 
 def backward_precision_of(net):
@@ -527,8 +417,11 @@ def free_device_bytes(dev):
 def backward_chunk(cfg, bprec_code, B, have_act16, dev):
     """(images per chunk, workspace bytes) of cnerf_render_backward: the largest chunk whose workspace fits MEMORY_FRACTION of the
     memory that is free NOW -- not a constant sized for an empty 288 GB part: whatever the encoder, the discriminator
-    and DDP already hold is accounted for, and a smaller or shared device gets smaller chunks instead of an out-of-memory error."""
+    and DDP already hold is accounted for, and a smaller or shared device gets smaller chunks instead of an out-of-memory error.
+    The per-point FiLM family's fp32 backward takes ACT_BUDGET_BYTES at most."""
     budget = int(MEMORY_FRACTION * free_device_bytes(dev))
+    if cfg.layer_kind[0] == L.LAYER_PFILM and bprec_code == L.PREC_FP32:
+        budget = min(budget, ACT_BUDGET_BYTES)
     need = C.c_size_t(0)
     for nb in ([B] if have_act16 else range(B, 0, -1)):
         L.check(L.lib().cnerf_backward_workspace_bytes(C.byref(cfg), bprec_code, nb, 1 if have_act16 else 0, C.byref(need)), "cnerf_backward_workspace_bytes")
@@ -580,8 +473,7 @@ def merge_composite_backward(cfg, coarse_rgb_sigma, coarse_z, fine_rgb_sigma, fi
 
 def render_backward(net, o, levels, freq, phase, cam2world, rng, saved, grad_pixels, grad_depth, act16=None):
     """Gradients of one render w.r.t. (channel-last feature volumes, freq, phase, [field parameters]): ONE call into the library
-    (cnerf_render_backward); the exact fp32 backward of the per-point FiLM family is spelled with the library's stage calls, per pass
-    and chunk cnerf_field_backward + cnerf_pfilm_backward_finish (_pfilm_backward)."""
+    (cnerf_render_backward)."""
     global LAST_SATURATED
     B, R, S, hier = o["B"], o["R"], o["S"], o["hier"]
     dev = cam2world.device
@@ -595,10 +487,6 @@ def render_backward(net, o, levels, freq, phase, cam2world, rng, saved, grad_pix
     c_rs, c_z, f_rs, f_z = saved[:4]
     grad_pixels = _f32(grad_pixels)
     grad_depth = _f32(grad_depth) if grad_depth is not None else None
-    if pfilm32:
-        eps_final = rng.get("eps_final") if o["noise_std"] != 0 else None
-        gc, gf = merge_composite_backward(cfg, c_rs, c_z, f_rs if hier else None, f_z if hier else None, eps_final, grad_pixels, grad_depth)
-        return _pfilm_backward(net, o, cfg, levels, cam2world, rng, saved, gc, gf)
     w = _backward_setup(net, cfg, levels, B, dev)
     nb, ws_bytes = backward_chunk(cfg, w.code, B, act16 is not None, dev)
     ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
@@ -643,7 +531,6 @@ class RenderFunction(torch.autograd.Function):
         fr = freq.detach() if freq is not None else None
         ph = phase.detach() if phase is not None else None
         need_grad = o.get("need_grad", any(ctx.needs_input_grad))   # (decided by ops.render: grad mode is always off in here)
-        keys = SAVED_KEYS + (("coarse_points", "fine_points") if net.spec.layers[0] == "pfilm" else ())   # see _pfilm_backward
         act16 = None
         if need_grad and backward_precision_of(net) == "fp16" and precision_of(net) in (("fp16x3",) if net.spec.layers[0] == "pfilm" else ("fp16x3", "fp16")):
             act16 = resident_act16(net, levels, cam2world.shape[0], o["R"], o["S"], o["hier"], cam2world.device)
@@ -651,11 +538,11 @@ class RenderFunction(torch.autograd.Function):
                                             o["S"], o["hier"], o["clamp_mode"], o["noise_std"], o["white_back"],
                                             o["last_back"], rng, want_aux=o["want_aux"], fvol_is_channel_last=True,
                                             field_events=o.get("field_events"),
-                                            aux_keys=keys if need_grad and not o["want_aux"] else None, act16=act16)
+                                            aux_keys=SAVED_KEYS if need_grad and not o["want_aux"] else None, act16=act16)
         ctx.net, ctx.o, ctx.rng, ctx.n_vols = net, o, rng, n_vols
         ctx.act16 = act16
         if need_grad:
-            saved = [aux.get(k) for k in keys]
+            saved = [aux.get(k) for k in SAVED_KEYS]
             if o["hier"] and rng.get("fine_z") is not None:
                 saved[3] = _f32(rng["fine_z"]).reshape(saved[1].shape)   # teacher-forced depths are what the fine pass used
             ctx.saved = (levels, fr, ph, _f32(cam2world), tuple(saved))
@@ -721,19 +608,14 @@ def query_workspace_bytes(cfg, bprec_code, points_per_chunk):
 
 def query_backward(net, levels, freq, phase, points, out, grad_out, drop, want_points):
     """Gradients of one field query w.r.t. (channel-last volume levels, freq, phase, field parameters, points or None): ONE call into
-    the library (cnerf_field_query_backward); the exact fp32 backward of the per-point FiLM family is spelled with the library's stage
-    calls (_pfilm_backward).  The backward precision and the re-run's precision follow render_backward."""
+    the library (cnerf_field_query_backward).  The backward precision and the re-run's precision follow render_backward."""
     global LAST_SATURATED
     B, n = points.shape[0], points.shape[1]
     dev = points.device
     bprec = backward_precision_of(net)
     g_pts = torch.zeros_like(points) if want_points else None
-    if net.spec.layers[0] == "pfilm" and bprec == "fp32":
-        cfg = make_cfg(net, B, levels, precision="fp32", drop=drop)
-        g_levels, _, _, grads = _pfilm_backward(net, None, cfg, levels, None, None, None, None, None,
-                                                query=dict(points=points, g_out=grad_out, saved_out=out, drop=drop, grad_points=g_pts))
-        return g_levels, None, None, grads, g_pts
-    cfg = make_cfg(net, B, levels, precision="fp16x3" if bprec == "fp16" else None, drop=drop)
+    pfilm32 = net.spec.layers[0] == "pfilm" and bprec == "fp32"
+    cfg = make_cfg(net, B, levels, precision="fp16x3" if bprec == "fp16" else ("fp32" if pfilm32 else None), drop=drop)
     w = _backward_setup(net, cfg, levels, B, dev)
     ppc, ws_bytes = query_chunk(n, lambda k: query_workspace_bytes(cfg, w.code, k), dev)
     ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)

@@ -273,7 +273,7 @@ int cnerf_render_forward(const cnerf_cfg* cfg, const cnerf_volumes* vols, const 
  * y_l = sin((15 f_l + 30) (W_l y_{l-1} + b_l) + p_l), y_-1 = xyz): the same call with larger chunk buffers --
  *             act_feat (n,32)                  looked-up feature            act_go (n,4)  d/d head pre-activation
  *             act_h  L (n,H) slabs of y_l, then m (n,256)                    (L*n*H + n*256 floats)
- *             act_c  3L (n,H) slabs: per layer cos(arg), cos*freq, cos*15*pre   (private to the call)
+ *             act_c  3L (n,H) slabs: per layer cos(arg), cos*freq, cos*15*pre   (scratch of the call: nothing reads it afterwards)
  *             act_g  L (n,H) slabs of g_pre_l = d/d (W_l y_{l-1} + b_l), then G (n, 2*L*H) = d/d (Wm2 m + bm2), row by row in
  *                    that Linear's output order [f of layers 0..L-1 | p of layers 0..L-1]           (3*L*n*H floats)
  *         and no volume scatter (grad_vols is not touched).  What remains are products over those matrices, all of them behind ONE
@@ -340,9 +340,9 @@ int cnerf_weight_grad16(int32_t n_images, int64_t tiles_per_image, int32_t n_row
                         const void* X, float* dW, float* colsum, const float* inv_scale, void* stream);
 
 /* Packed operands of the half-precision gradient chain: every W_l^T (and the head's) as fp16 MFMA fragments, each matrix
- * pre-scaled by a power of two, plus their inverse scales.  Bytes via cnerf_backward16_bytes.  FiLM / plain-sine layers
- * (FiLM, plain-sine and residual-block networks; a residual block is two matrices -- fc1, fc2 -- of every per-matrix array below.
- * CNERF_ENOSYS for the per-point FiLM family: use the fp32 backward there). */
+ * pre-scaled by a power of two, plus their inverse scales.  Bytes via cnerf_backward16_bytes.  FiLM, plain-sine and residual-block
+ * networks: a residual block is two matrices -- fc1, fc2 -- of every per-matrix array below; the per-point FiLM family packs the
+ * operands of its own chain (csrc/chain_pw16.hip) behind the same two calls. */
 int cnerf_backward16_bytes(const cnerf_cfg* cfg, size_t* packed16);
 int cnerf_pack_field_chain16(const cnerf_cfg* cfg, const cnerf_field_params* params, void* packed16, void* stream);
 
@@ -356,9 +356,11 @@ int cnerf_pack_field_chain16(const cnerf_cfg* cfg, const cnerf_field_params* par
  *
  *   backward_precision  CNERF_PREC_FP32: exact fp32 chain and weight reductions (re-run in cfg->precision);
  *                       CNERF_PREC_FP16: fp16 operands, fp32 sums (csrc/bwd16.hip, cnerf_weight_grad16; cfg->precision must
- *                       be CNERF_PREC_FP16X3).  Per-point FiLM networks (ABI v7): CNERF_PREC_FP16 runs here (csrc/chain_pw16.hip; grads->map_*
- *                       receive the mapping network's gradients); CNERF_PREC_FP32 answers CNERF_ENOSYS -- the exact path is spelled with
- *                       stage calls: cnerf_merge_composite_backward, then per pass and chunk cnerf_field_backward + cnerf_pfilm_backward_finish.
+ *                       be CNERF_PREC_FP16X3).  Per-point FiLM networks: grads->map_* receive the mapping network's gradients, all of
+ *                       grads' buffers of the family are required; CNERF_PREC_FP16 (ABI v7) is csrc/chain_pw16.hip, CNERF_PREC_FP32 needs
+ *                       cfg->precision = CNERF_PREC_FP32 and runs per pass and chunk what the stage calls spell: cnerf_field_backward,
+ *                       then cnerf_pfilm_backward_finish on the positions the re-run wrote (the forward need not keep any), into a
+ *                       workspace of the five chunk matrices above, (n,3) positions and the stage's workspace and packed_map.
  *   params              the raw parameters (dfreq needs W_l and b_l);  packed: cnerf_pack_field in cfg->precision;
  *   packed_bwd          cnerf_pack_field_transposed (fp32 backward) or cnerf_pack_field_chain16 (fp16 backward).
  *   saved               the forward's coarse / fine rgb_sigma and z (cnerf_aux of that call; fine_* NULL when not hierarchical).
@@ -414,8 +416,9 @@ int cnerf_render_backward(const cnerf_cfg* cfg, int32_t backward_precision, int3
  * term through the trilinear weights of every level (ATen grid_sampler_3d_backward, border padding: zero on an axis whose coordinate
  * sits at or beyond the clamp) plus the xyz columns of TALLSIREN_dgx / TALLSIREN's layer 0.
  *   backward_precision  as cnerf_render_backward, with the same coverage: CNERF_PREC_FP32 re-runs the forward in cfg->precision,
- *                       CNERF_PREC_FP16 needs cfg->precision = CNERF_PREC_FP16X3; per-point FiLM + CNERF_PREC_FP32 answers CNERF_ENOSYS
- *                       (stage calls there: cnerf_field_backward_points, cnerf_pfilm_backward_finish, cnerf_feature_points_grad).
+ *                       CNERF_PREC_FP16 needs cfg->precision = CNERF_PREC_FP16X3; per-point FiLM + CNERF_PREC_FP32 needs cfg->precision =
+ *                       CNERF_PREC_FP32 (per chunk what the stage calls spell: cnerf_field_backward_points, cnerf_pfilm_backward_finish; the
+ *                       position gradient: g_pre_0 W_0 plus the lookup term of the stage's d feat rows).
  *   packed / packed_bwd as cnerf_render_backward.  cfg->R, S, fov are not read (check as for cnerf_field_forward).
  *   grads, grad_freq, grad_phase, grad_vols, grad_points (B,n,3) or NULL = skip: ACCUMULATED INTO (zero them first).
  *   dropout (cfg->drop_p > 0, fp32 only): the decisions of cnerf_field_forward (stream 6 at the point's index in the whole call),
@@ -431,7 +434,7 @@ int cnerf_field_query_backward(const cnerf_cfg* cfg, int32_t backward_precision,
                                const cnerf_grad_volumes* grad_vols, float* grad_points, uint32_t* saturated, void* workspace, void* stream);
 
 /* Stage entries of the per-point FiLM family's exact fp32 query backward (followed per chunk by cnerf_pfilm_backward_finish, as
- * cnerf_field_backward is for the ray passes):
+ * cnerf_field_backward is for the ray passes), for hosts that sequence the stages themselves -- cnerf_field_query_backward runs them all:
  *   cnerf_field_backward_points  cnerf_field_backward (pass 2) for ANY point count: points / grad_rgb_sigma / saved_rgb_sigma are
  *                                (B, n_per_image, ...) of cfg->B images (cfg->R, S unused); act_* sized for B * n_per_image rows;
  *                                drop_mask (n_drop, B * n_per_image, H) or NULL (then Philox stream 6 at index b * n_per_image + p).
@@ -450,7 +453,8 @@ int cnerf_dropout_keep(const cnerf_cfg* cfg, uint32_t stream_id, int64_t point0,
 /* Everything of the per-point FiLM family's exact fp32 backward that follows cnerf_field_backward / cnerf_field_backward_points on
  * one chunk (n = n_images * n_per_image rows): the parameter gradients of the L layers, the head and the mapping network, d feat and
  * its scatter.  Autograd of the mapping network and the nn.Linear layers of TALLSIREN (siren.py:81-101, 232-331) for hosts without a
- * GEMM library; added in ABI v10 without a version change (no struct changed).
+ * GEMM library; added in ABI v10 without a version change (no struct changed).  cnerf_render_backward and cnerf_field_query_backward
+ * run this stage per chunk themselves; the entry stays for hosts that sequence the stages.
  * cfg: PFILM network, precision FP32, one 32-channel volume (else CNERF_EINVAL; cfg->B, R, S are not read).  Chunk inputs exactly as
  * cnerf_field_backward left them:
  *   points (n,3)  act_feat (n,32)  act_h: L slabs y_l (n,H) then m (n,256)  act_g: L slabs g_pre_l (n,H) then G (n,2LH)  act_go (n,4)

@@ -1,8 +1,8 @@
 """cnerf_pfilm_backward_finish: the mapping-network stage of the per-point FiLM family's exact fp32 backward (csrc/pfilm_finish.hip).
 1. the stage alone on synthetic chunk buffers against the same formulas in float64, at the derived dot-product bound;
-2. forward + exact backward of the TALLSIREN fixtures through ctypes ALONE, the backward spelled with stage calls, against the
-   reference's autograd;
-3. the chunk loop of the PyTorch mirror: one stage call per pass and chunk."""
+2. forward + exact backward of the TALLSIREN fixtures through ctypes ALONE, the backward spelled with stage calls and as one
+   cnerf_render_backward call, against the reference's autograd;
+3. the PyTorch mirror: one cnerf_render_backward call whatever the chunking, no stage call from Python."""
 import ctypes as C
 
 import numpy as np
@@ -172,12 +172,14 @@ def test_stage_alone_against_float64(dev, n_images, npi, H, nl):
     assert (ws[wsb.value // 4:] == SENT).all() and (g_vol[n_images] == SENT).all()
 
 
+@pytest.mark.parametrize("spelling", ["stages", "one_call_per_image", "one_call_all_images"])
 @pytest.mark.parametrize("name", ["tallsiren_small", "tallsiren_drop_small"])
-def test_exact_backward_through_ctypes_only(golden, dev, name):
-    """tests/test_gpu_abi_only.py's forward + backward for the one family it could not cover in fp32: the render through
-    cnerf_render_forward, the backward as cnerf_merge_composite_backward, then per pass cnerf_field_backward (one chunk of all images) and
-    cnerf_pfilm_backward_finish on the sample positions cnerf_aux kept -- no cnerf_amd.ops, no torch matmul.  The dropout fixture passes
-    its keep bytes and drop_p.  Against the reference's autograd at test_backward_teacher_forced's tolerance."""
+def test_exact_backward_through_ctypes_only(golden, dev, name, spelling):
+    """tests/test_gpu_abi_only.py's forward + backward for this family in fp32: the render through cnerf_render_forward, the backward
+    either spelled with stage calls -- cnerf_merge_composite_backward, then per pass cnerf_field_backward (one chunk of all images) and
+    cnerf_pfilm_backward_finish on the sample positions cnerf_aux kept -- or as ONE cnerf_render_backward call with images_per_chunk 1
+    or B, whose forward keeps no sample positions (the chunk's re-run writes them) -- no cnerf_amd.ops, no torch matmul.  The dropout
+    fixture passes its keep bytes (cnerf_rng) and drop_p.  Against the reference's autograd at test_backward_teacher_forced's tolerance."""
     import cnerf_amd
     from test_gpu_parity import reference_grad_noise_floor
     L = cnerf_amd._lib
@@ -233,8 +235,9 @@ def test_exact_backward_through_ctypes_only(golden, dev, name):
         setattr(rng, k, t.data_ptr())
     aux = L.Aux()
     sv = {"coarse_rgb_sigma": torch.empty((B, P, S, 4), device=dev), "coarse_z": torch.empty((B, P, S), device=dev),
-          "fine_rgb_sigma": torch.empty((B, P, S, 4), device=dev), "fine_z": torch.empty((B, P, S), device=dev),
-          "coarse_points": torch.empty((B, P, S, 3), device=dev), "fine_points": torch.empty((B, P, S, 3), device=dev)}
+          "fine_rgb_sigma": torch.empty((B, P, S, 4), device=dev), "fine_z": torch.empty((B, P, S), device=dev)}
+    if spelling == "stages":
+        sv.update(coarse_points=torch.empty((B, P, S, 3), device=dev), fine_points=torch.empty((B, P, S, 3), device=dev))
     for k, t in sv.items():
         setattr(aux, k, t.data_ptr())
     cam = T(g["cam2worlds"]).reshape(B, 4, 4).contiguous()
@@ -245,32 +248,43 @@ def test_exact_backward_through_ctypes_only(golden, dev, name):
     grad_pixels = (2.0 * pixels / pixels.numel()).contiguous()              # loss = pixels.square().mean() + depth.mean()
     grad_depth = torch.full_like(depth, 1.0 / depth.numel())
 
-    # ---- the backward, stage by stage ------------------------------------------------------------------------------------------
-    nb, pm, fws = C.c_size_t(), C.c_size_t(), C.c_size_t()
+    nb = C.c_size_t()
     ok(lib.cnerf_backward_bytes(C.byref(cfg), C.byref(nb)), "backward_bytes")
     packed_t = torch.empty(nb.value // 4, device=dev)
     ok(lib.cnerf_pack_field_transposed(C.byref(cfg), C.byref(fp), dptr(packed_t), stream), "pack_field_transposed")
-    ok(lib.cnerf_pfilm_finish_bytes(C.byref(cfg), B, npi, C.byref(pm), C.byref(fws)), "pfilm_finish_bytes")
-    packed_map = torch.empty(pm.value // 4, device=dev)
-    ok(lib.cnerf_pack_pfilm_map_transposed(C.byref(cfg), C.byref(fp), dptr(packed_map), stream), "pack_pfilm_map_transposed")
-    finish_ws = torch.empty(fws.value, dtype=torch.uint8, device=dev)
-    gc, gf = torch.empty((B, P, S, 4), device=dev), torch.empty((B, P, S, 4), device=dev)
-    ok(lib.cnerf_merge_composite_backward(C.byref(cfg), dptr(sv["coarse_rgb_sigma"]), dptr(sv["coarse_z"]), dptr(sv["fine_rgb_sigma"]),
-                                          dptr(keep["fine_z"]), None, dptr(grad_pixels), dptr(grad_depth), dptr(gc), dptr(gf), stream),
-       "merge_composite_backward")
-    act_feat, act_go = torch.empty((n, 32), device=dev), torch.empty((n, 4), device=dev)
-    act_h = torch.empty(nl * n * H + n * 256, device=dev)
-    act_c, act_g = torch.empty(3 * nl * n * H, device=dev), torch.empty(3 * nl * n * H, device=dev)
     g_vol = torch.zeros_like(fcl)
     gvols = L.Volumes()
     gvols.level[0] = g_vol.data_ptr()
-    for pss, g_out, saved_out, points, mask in ((0, gc, sv["coarse_rgb_sigma"], sv["coarse_points"], keep.get("drop_coarse")),
-                                                (1, gf, sv["fine_rgb_sigma"], sv["fine_points"], keep.get("drop_fine"))):
-        ok(lib.cnerf_field_backward(C.byref(cfg), pss, 0, B, C.byref(vols), dptr(packed), dptr(packed_t), None, None, dptr(cam), dptr(keep["u_strat"]),
-                                    dptr(keep["fine_z"]), dptr(g_out), dptr(saved_out), dptr(act_feat), dptr(act_h), dptr(act_c), dptr(act_g),
-                                    dptr(act_go), C.byref(gvols), dptr(mask), stream), "field_backward")
-        ok(lib.cnerf_pfilm_backward_finish(C.byref(cfg), C.byref(fp), dptr(packed_map), B, npi, dptr(points), dptr(act_feat), dptr(act_h), dptr(act_g),
-                                           dptr(act_go), C.byref(gp), dptr(g_vol), None, dptr(finish_ws), stream), "pfilm_backward_finish")
+    if spelling == "stages":          # ---- the backward, stage by stage
+        pm, fws = C.c_size_t(), C.c_size_t()
+        ok(lib.cnerf_pfilm_finish_bytes(C.byref(cfg), B, npi, C.byref(pm), C.byref(fws)), "pfilm_finish_bytes")
+        packed_map = torch.empty(pm.value // 4, device=dev)
+        ok(lib.cnerf_pack_pfilm_map_transposed(C.byref(cfg), C.byref(fp), dptr(packed_map), stream), "pack_pfilm_map_transposed")
+        finish_ws = torch.empty(fws.value, dtype=torch.uint8, device=dev)
+        gc, gf = torch.empty((B, P, S, 4), device=dev), torch.empty((B, P, S, 4), device=dev)
+        ok(lib.cnerf_merge_composite_backward(C.byref(cfg), dptr(sv["coarse_rgb_sigma"]), dptr(sv["coarse_z"]), dptr(sv["fine_rgb_sigma"]),
+                                              dptr(keep["fine_z"]), None, dptr(grad_pixels), dptr(grad_depth), dptr(gc), dptr(gf), stream),
+           "merge_composite_backward")
+        act_feat, act_go = torch.empty((n, 32), device=dev), torch.empty((n, 4), device=dev)
+        act_h = torch.empty(nl * n * H + n * 256, device=dev)
+        act_c, act_g = torch.empty(3 * nl * n * H, device=dev), torch.empty(3 * nl * n * H, device=dev)
+        for pss, g_out, saved_out, points, mask in ((0, gc, sv["coarse_rgb_sigma"], sv["coarse_points"], keep.get("drop_coarse")),
+                                                    (1, gf, sv["fine_rgb_sigma"], sv["fine_points"], keep.get("drop_fine"))):
+            ok(lib.cnerf_field_backward(C.byref(cfg), pss, 0, B, C.byref(vols), dptr(packed), dptr(packed_t), None, None, dptr(cam), dptr(keep["u_strat"]),
+                                        dptr(keep["fine_z"]), dptr(g_out), dptr(saved_out), dptr(act_feat), dptr(act_h), dptr(act_c), dptr(act_g),
+                                        dptr(act_go), C.byref(gvols), dptr(mask), stream), "field_backward")
+            ok(lib.cnerf_pfilm_backward_finish(C.byref(cfg), C.byref(fp), dptr(packed_map), B, npi, dptr(points), dptr(act_feat), dptr(act_h), dptr(act_g),
+                                               dptr(act_go), C.byref(gp), dptr(g_vol), None, dptr(finish_ws), stream), "pfilm_backward_finish")
+    else:                             # ---- the backward in one call
+        cnt = 1 if spelling == "one_call_per_image" else B
+        ok(lib.cnerf_backward_workspace_bytes(C.byref(cfg), L.PREC_FP32, cnt, 0, C.byref(nb)), "backward_workspace_bytes")
+        bws = torch.empty(nb.value, dtype=torch.uint8, device=dev)
+        saved = L.Saved()
+        saved.coarse_rgb_sigma, saved.coarse_z = sv["coarse_rgb_sigma"].data_ptr(), sv["coarse_z"].data_ptr()
+        saved.fine_rgb_sigma, saved.fine_z = sv["fine_rgb_sigma"].data_ptr(), keep["fine_z"].data_ptr()
+        ok(lib.cnerf_render_backward(C.byref(cfg), L.PREC_FP32, cnt, C.byref(vols), C.byref(fp), dptr(packed), dptr(packed_t), None, None, dptr(cam),
+                                     C.byref(rng), C.byref(saved), None, dptr(grad_pixels), dptr(grad_depth), C.byref(gp), None, None, C.byref(gvols),
+                                     None, dptr(bws), stream), "render_backward")
     gv_cf = torch.empty_like(fvol)
     ok(lib.cnerf_fvol_channel_first(B, Cc, Vf, dptr(g_vol), dptr(gv_cf), stream), "channel_first")
     torch.cuda.synchronize()
@@ -286,20 +300,30 @@ def test_exact_backward_through_ctypes_only(golden, dev, name):
     assert e < tol, ("feature_volume", e, tol)
 
 
-def test_mirror_calls_the_stage_once_per_pass_and_chunk(dev, monkeypatch):
-    """With next to no free memory reported the mirror falls back to one image per chunk: 3 images x 2 passes = 6 stage calls, and the
-    gradients still meet the gates of _ragged_backward_case (autograd through the CPU oracle)."""
+def test_mirror_is_one_call_whatever_the_chunking(dev, monkeypatch):
+    """With ops.backward_chunk answering one image per chunk the mirror still makes ONE cnerf_render_backward call (images_per_chunk 1:
+    3 images x 2 passes = 6 chunks inside the library) and no stage call of its own, and the gradients still meet the gates of
+    _ragged_backward_case (autograd through the CPU oracle)."""
     import cnerf_amd
     from cnerf_amd import ops
     from test_gpu_parity import _ragged_backward_case
-    lib = cnerf_amd._lib.lib()
-    real = lib.cnerf_pfilm_backward_finish
-    calls = []
+    L = cnerf_amd._lib
+    lib = L.lib()
+    calls = {k: [] for k in ("cnerf_render_backward", "cnerf_field_backward", "cnerf_pfilm_backward_finish")}
 
-    def counting(*args):
-        calls.append((args[3], args[4]))          # (n_images, n_per_image)
-        return real(*args)
-    monkeypatch.setattr(lib, "cnerf_pfilm_backward_finish", counting)
-    monkeypatch.setattr(ops, "free_device_bytes", lambda dev: 4096)
+    def counting(name, real):
+        def call(*args):
+            calls[name].append(args)
+            return real(*args)
+        return call
+    for name in calls:
+        monkeypatch.setattr(lib, name, counting(name, getattr(lib, name)))
+
+    def by_image(cfg, code, nb_max, have_act16, d):
+        need = C.c_size_t(0)
+        L.check(lib.cnerf_backward_workspace_bytes(C.byref(cfg), code, 1, 0, C.byref(need)), "cnerf_backward_workspace_bytes")
+        return 1, need.value
+    monkeypatch.setattr(ops, "backward_chunk", by_image)
     _ragged_backward_case(dev, dict(B=3, R=4, S=9, V=5, H=256), "TALLSIREN", "fp32")
-    assert calls == [(1, 4 * 4 * 9)] * 6
+    assert len(calls["cnerf_render_backward"]) == 1 and calls["cnerf_render_backward"][0][2] == 1          # images_per_chunk
+    assert calls["cnerf_field_backward"] == [] and calls["cnerf_pfilm_backward_finish"] == []

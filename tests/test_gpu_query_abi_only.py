@@ -17,8 +17,12 @@ def dptr(t):
     return C.c_void_p(t.data_ptr())
 
 
-@pytest.mark.parametrize("variant,fwd,bwd", [("SHORTSIREN_FG", "fp32", "fp32"), ("SHORTSIREN_FG_Pyrmd", "fp16x3", "fp16"), ("TALLSIREN", "fp16x3", "fp16")])
+@pytest.mark.parametrize("variant,fwd,bwd", [("SHORTSIREN_FG", "fp32", "fp32"), ("SHORTSIREN_FG_Pyrmd", "fp16x3", "fp16"), ("TALLSIREN", "fp16x3", "fp16"),
+                                             ("TALLSIREN", "fp32", "fp32")])
 def test_query_forward_and_backward_through_ctypes_only(variant, fwd, bwd):
+    """3001 points per image in chunks of 1024: three chunks per image, the last one ragged.  TALLSIREN's exact fp32 backward (the
+    per-point FiLM body of the one call: the stage kernels behind cnerf_field_query_backward): 4099 points in four 1000-point chunks
+    and a 99-point tail, at the gate of the other fp32 row (rel l2 2e-3, scaled 2e-2 against autograd through the oracle)."""
     import cnerf_amd
     from cnerf_amd.generators import siren as S
     from oracle import render_oracle as O
@@ -30,7 +34,8 @@ def test_query_forward_and_backward_through_ctypes_only(variant, fwd, bwd):
     nul = C.c_void_p(None)
     p_or_null = lambda t: nul if t is None else dptr(t)
     torch.manual_seed(7)
-    B, n, H, V, Z = 2, 3001, 64, 8, 32
+    B, H, V, Z = 2, 64, 8, 32
+    n, ppc = (4099, 1000) if (variant, bwd) == ("TALLSIREN", "fp32") else (3001, 1024)
     spec = O.FIELD_SPECS[variant]
     lv = [(32, V), (64, V // 2), (32, V // 4)] if spec.input == "pyramid" else [(32, V)]
     Cc = sum(c for c, _ in lv)
@@ -107,7 +112,6 @@ def test_query_forward_and_backward_through_ctypes_only(variant, fwd, bwd):
         packed_bwd = torch.empty(nb.value, dtype=torch.uint8, device=dev)
         ok(lib.cnerf_pack_field_transposed(C.byref(cfg), C.byref(fp), dptr(packed_bwd), stream), "pack_field_transposed")
     bcode = L.PREC_CODE[bwd]
-    ppc = 1024                                       # three chunks per image, the last one ragged
     ok(lib.cnerf_field_query_backward_workspace_bytes(C.byref(cfg), bcode, ppc, C.byref(nb)), "query_workspace_bytes")
     ws = torch.empty(nb.value, dtype=torch.uint8, device=dev)
     g_freq = torch.zeros_like(freq) if n_film else None
@@ -132,6 +136,7 @@ def test_query_forward_and_backward_through_ctypes_only(variant, fwd, bwd):
     def close(got, want, k):
         got, want = got.detach().cpu().double().numpy(), want.detach().double().numpy()
         rel_l2 = np.linalg.norm(got - want) / max(np.linalg.norm(want), 1e-30)
+        print(f"{k:40s} rel l2 {rel_l2:.2e} scaled {scaled_err(got, want):.2e}")
         assert rel_l2 < (3e-3 if bwd == "fp16" else 2e-3), (k, rel_l2)
         assert scaled_err(got, want) < (5e-2 if bwd == "fp16" else 2e-2), (k, scaled_err(got, want))
 

@@ -149,7 +149,7 @@ def test_philox_dropout_keep_layout():
 
 def test_backward_workspace_validation_without_gpu():
     """cnerf_backward_workspace_bytes (host code of the one-call backward): sizes grow with the chunk, kept activations shrink them,
-    and what the call cannot do is refused with a message -- per-point FiLM (CNERF_ENOSYS), an fp16 backward behind an fp32 forward cfg."""
+    and what the call cannot do is refused with a message -- an fp16 backward behind an fp32 forward cfg; every layer family is sized."""
     import cnerf_amd
     L = cnerf_amd._lib
     cfg = L.Cfg()
@@ -174,7 +174,8 @@ def test_backward_workspace_validation_without_gpu():
     assert b"fp16x3" in L.lib().cnerf_last_error()
     for l in range(4):
         cfg.layer_kind[l] = L.LAYER_PFILM
-    assert L.lib().cnerf_backward_workspace_bytes(ctypes.byref(cfg), L.PREC_FP32, 1, 0, ctypes.byref(n)) == -38
+    assert L.lib().cnerf_backward_workspace_bytes(ctypes.byref(cfg), L.PREC_FP32, 1, 0, ctypes.byref(n)) == 0, L.lib().cnerf_last_error()
+    assert n.value >= 2 * 4 * npi * 16 + npi * (32 + 4 * 64 + 256 + 2 * 3 * 4 * 64 + 4 + 3 + 256 + 32) * 4      # the per-point FiLM family's chunk
 
 
 @pytest.mark.parametrize("kinds,precision,missing", [(("film",) * 4, "fp32", "w_final"), (("film",) * 4, "fp16", "w_final"),

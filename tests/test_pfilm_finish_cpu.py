@@ -95,11 +95,56 @@ def test_refusals_launch_nothing_and_say_why(L):
     assert pack(ctypes.byref(stage_cfg(L, kinds=("sine",) * 3)), ctypes.byref(L.FieldParams()), ctypes.c_void_p(0x1000), None) == -22
 
 
-def test_one_call_entries_still_refuse_and_name_the_stage(L):
+def test_one_call_entries_size_the_fp32_backward_from_the_documented_pieces(L):
+    """cnerf_render_backward / cnerf_field_query_backward run this family's exact backward themselves: their workspace is the pieces
+    include/cnerf.h documents -- d rgb_sigma of both passes (render), the five chunk matrices of cnerf_field_backward, the chunk's sample
+    positions (render), the stage's workspace and packed_map as cnerf_pfilm_finish_bytes reports them, a query's input-gradient rows
+    (points_per_chunk, 256) -- each padded to 256 bytes at most, and nothing else."""
+    lib, err = L.lib(), lambda: L.lib().cnerf_last_error()
     cfg = stage_cfg(L)
-    cfg.R, cfg.S, cfg.fov_deg = 8, 4, 30.0
+    cfg.R, cfg.S, cfg.fov_deg, cfg.flags = 8, 4, 30.0, L.F_HIERARCHICAL
+    Lc, H, B, npi = 8, 256, 2, 8 * 8 * 4
+    nbytes = ctypes.c_size_t()
+    chunk_floats = lambda n: n * 32 + (Lc * n * H + n * 256) + 3 * Lc * n * H + 3 * Lc * n * H + n * 4
+    for cnt in (1, 2):
+        assert lib.cnerf_backward_workspace_bytes(ctypes.byref(cfg), L.PREC_FP32, cnt, 0, ctypes.byref(nbytes)) == 0, err()
+        rc, pm, fin = finish_bytes(L, cfg, cnt, npi)
+        assert rc == 0
+        n = cnt * npi
+        raw = 2 * B * npi * 4 * 4 + chunk_floats(n) * 4 + n * 3 * 4 + fin + pm
+        assert raw <= nbytes.value <= raw + 256 * 16, (cnt, raw, nbytes.value)
+    for ppc in (1024, 4099):
+        assert lib.cnerf_field_query_backward_workspace_bytes(ctypes.byref(cfg), L.PREC_FP32, ppc, ctypes.byref(nbytes)) == 0, err()
+        rc, pm, fin = finish_bytes(L, cfg, 1, ppc)
+        assert rc == 0
+        raw = chunk_floats(ppc) * 4 + fin + pm + ppc * 256 * 4
+        assert raw <= nbytes.value <= raw + 256 * 16, (ppc, raw, nbytes.value)
+
+
+def test_one_call_entries_refuse_what_the_fp32_backward_cannot_do(L):
+    lib, err = L.lib(), lambda: L.lib().cnerf_last_error()
     n = ctypes.c_size_t()
-    assert L.lib().cnerf_backward_workspace_bytes(ctypes.byref(cfg), L.PREC_FP32, 1, 0, ctypes.byref(n)) == -38
-    assert b"cnerf_pfilm_backward_finish" in L.lib().cnerf_last_error()
-    assert L.lib().cnerf_field_query_backward_workspace_bytes(ctypes.byref(cfg), L.PREC_FP32, 1024, ctypes.byref(n)) == -38
-    assert b"cnerf_pfilm_backward_finish" in L.lib().cnerf_last_error()
+
+    def render_cfg(precision):
+        cfg = stage_cfg(L, precision=precision)
+        cfg.R, cfg.S, cfg.fov_deg = 8, 4, 30.0
+        return cfg
+
+    # the fp32 chain re-runs the fp32 kernel, the fp16 chain the fp16x3 kernel; kept activations are the fp16 backward's
+    for sizes, arg in ((lib.cnerf_backward_workspace_bytes, (1, 0)), (lib.cnerf_field_query_backward_workspace_bytes, (1024,))):
+        assert sizes(ctypes.byref(render_cfg("fp16x3")), L.PREC_FP32, *arg, ctypes.byref(n)) == -22 and b"fp32" in err()
+        assert sizes(ctypes.byref(render_cfg("fp32")), L.PREC_FP16, *arg, ctypes.byref(n)) == -22 and b"fp16x3" in err()
+    assert lib.cnerf_backward_workspace_bytes(ctypes.byref(render_cfg("fp32")), L.PREC_FP32, 2, 1, ctypes.byref(n)) == -22 and b"kept activations" in err()
+    # the call itself, made-up aligned addresses: a gradient struct without the mapping network's buffers is refused before any launch
+    p, a = ctypes.c_void_p, 0x1000
+    vols, gvols, fp, saved = L.Volumes(), L.Volumes(), L.FieldParams(), L.Saved()
+    vols.level[0] = gvols.level[0] = a
+    fp.map_w1 = fp.map_w2 = fp.w_final = a
+    saved.coarse_rgb_sigma = saved.coarse_z = a
+    g = L.FieldParamGrads()
+    g.map_w1 = g.map_b1 = g.map_b2 = g.w_final = g.b_final = a          # map_w2 stays NULL
+    for l in range(8):
+        g.w[l] = g.b[l] = a
+    rc = lib.cnerf_render_backward(ctypes.byref(render_cfg("fp32")), L.PREC_FP32, 1, ctypes.byref(vols), ctypes.byref(fp), p(a), p(a), None, None, p(a),
+                                   None, ctypes.byref(saved), None, p(a), None, ctypes.byref(g), None, None, ctypes.byref(gvols), None, p(a), None)
+    assert rc == -22 and b"mapping network" in err()

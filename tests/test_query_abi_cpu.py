@@ -50,7 +50,10 @@ def test_query_workspace_grows_with_the_chunk_not_with_the_call(L):
 def test_query_backward_refusals(L):
     assert ws_bytes(L, query_cfg(L, precision="fp32"), "fp16", 1024)[0] == -22          # the fp16 backward re-runs the fp16x3 forward
     assert b"fp16x3" in L.lib().cnerf_last_error()
-    assert ws_bytes(L, query_cfg(L, kinds=("pfilm",) * 8, precision="fp32"), "fp32", 1024)[0] == -38   # per-point FiLM fp32: host GEMMs
+    # per-point FiLM, exact fp32: runs here on an fp32 cfg -- the chunk matrices (3 L gradient slabs alone), and grows with the chunk
+    rc, pw = ws_bytes(L, query_cfg(L, kinds=("pfilm",) * 8, precision="fp32"), "fp32", 1024)
+    assert rc == 0 and pw >= 1024 * 3 * 8 * 128 * 4 and ws_bytes(L, query_cfg(L, kinds=("pfilm",) * 8, precision="fp32"), "fp32", 2048)[1] > pw
+    assert ws_bytes(L, query_cfg(L, kinds=("pfilm",) * 8, precision="fp16x3"), "fp32", 1024)[0] == -22 and b"fp32" in L.lib().cnerf_last_error()
     assert ws_bytes(L, query_cfg(L), "fp32", 0)[0] == -22
     cfg = query_cfg(L)
     cfg.drop_p = 0.2
