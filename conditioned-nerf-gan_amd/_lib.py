@@ -47,6 +47,10 @@ class Saved(C.Structure):
     _fields_ = [("coarse_rgb_sigma", C.c_void_p), ("coarse_z", C.c_void_p), ("fine_rgb_sigma", C.c_void_p), ("fine_z", C.c_void_p)]
 
 
+class Rays(C.Structure):
+    _fields_ = [("origins", C.c_void_p), ("dirs", C.c_void_p)]
+
+
 class Rng(C.Structure):
     _fields_ = [("u_strat", C.c_void_p), ("eps_coarse", C.c_void_p), ("u_fine", C.c_void_p), ("eps_final", C.c_void_p),
                 ("fine_z", C.c_void_p), ("drop_coarse", C.c_void_p), ("drop_fine", C.c_void_p)]
@@ -109,6 +113,14 @@ PROTOTYPES = {
     "cnerf_pack_pfilm_map_transposed": (C.c_int, [C.POINTER(Cfg), C.POINTER(FieldParams), C.c_void_p, C.c_void_p]),
     "cnerf_pfilm_backward_finish": (C.c_int, [C.POINTER(Cfg), C.POINTER(FieldParams), C.c_void_p, C.c_int32, C.c_int64] + [C.c_void_p] * 5 +
                                     [C.POINTER(FieldParamGrads), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "cnerf_render_rays_workspace_bytes": (C.c_int, [C.POINTER(Cfg), C.c_int64, C.POINTER(C.c_size_t)]),
+    "cnerf_render_rays_forward": (C.c_int, [C.POINTER(Cfg), C.POINTER(Rays), C.c_int64, C.POINTER(Volumes), C.c_void_p, C.c_void_p, C.c_void_p,
+                                            C.POINTER(Rng), C.c_void_p, C.c_void_p, C.POINTER(Aux), C.c_void_p, C.c_void_p]),
+    "cnerf_render_rays_backward_workspace_bytes": (C.c_int, [C.POINTER(Cfg), C.c_int32, C.c_int64, C.c_int64, C.POINTER(C.c_size_t)]),
+    "cnerf_render_rays_backward": (C.c_int, [C.POINTER(Cfg), C.c_int32, C.c_int64, C.POINTER(Rays), C.c_int64, C.POINTER(Volumes), C.POINTER(FieldParams),
+                                             C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(Rng), C.POINTER(Saved), C.c_void_p, C.c_void_p,
+                                             C.POINTER(FieldParamGrads), C.c_void_p, C.c_void_p, C.POINTER(Volumes), C.c_void_p, C.c_void_p, C.c_void_p,
+                                             C.c_void_p, C.c_void_p]),
 }
 
 _lib = None

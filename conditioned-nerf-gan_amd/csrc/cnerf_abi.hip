@@ -1435,12 +1435,13 @@ int cnerf_field_query_backward_workspace_bytes(const cnerf_cfg* cfg, int32_t bac
     return CNERF_OK;
 }
 
-int cnerf_field_query_backward(const cnerf_cfg* cfg, int32_t bprec, int64_t points_per_chunk, const cnerf_volumes* vols, const cnerf_field_params* P,
-                               const float* packed, const void* packed_bwd, const float* freq, const float* phase, const float* points,
-                               int64_t n_per_image, const float* saved_rgb_sigma, const float* grad_rgb_sigma, const cnerf_field_param_grads* G,
-                               float* grad_freq, float* grad_phase, const cnerf_grad_volumes* grad_vols, float* grad_points, uint32_t* saturated,
-                               void* workspace, void* stream_) {
-    g_err[0] = 0;
+namespace {
+// cnerf_field_query_backward.  check_only: every refusal and no launch -- cnerf_render_rays_backward checks both of its field passes this
+// way before its first kernel (points, saved_rgb_sigma, grad_rgb_sigma, workspace: any non-NULL placeholders then)
+int query_backward(bool check_only, const cnerf_cfg* cfg, int32_t bprec, int64_t points_per_chunk, const cnerf_volumes* vols, const cnerf_field_params* P,
+                   const float* packed, const void* packed_bwd, const float* freq, const float* phase, const float* points, int64_t n_per_image,
+                   const float* saved_rgb_sigma, const float* grad_rgb_sigma, const cnerf_field_param_grads* G, float* grad_freq, float* grad_phase,
+                   const cnerf_grad_volumes* grad_vols, float* grad_points, uint32_t* saturated, void* workspace, void* stream_) {
     if (int rc = check_cfg(cfg, false)) return rc;
     QueryLayout Q;
     if (int rc = query_layout(cfg, bprec, (long long)points_per_chunk, Q)) return rc;
@@ -1460,6 +1461,7 @@ int cnerf_field_query_backward(const cnerf_cfg* cfg, int32_t bprec, int64_t poin
     MatrixSet ms;
     if (!pfilm)
         if (int rc = matrix_set(cfg, P, G, "field_query_backward", ms)) return rc;
+    if (check_only) return CNERF_OK;
     hipStream_t stream = (hipStream_t)stream_;
     const bool half = bprec == CNERF_PREC_FP16;
     const int B = cfg->B, H = cfg->H, NT = H / 32;
@@ -1547,6 +1549,17 @@ int cnerf_field_query_backward(const cnerf_cfg* cfg, int32_t bprec, int64_t poin
     }
     return CNERF_OK;
 }
+}  // namespace
+
+int cnerf_field_query_backward(const cnerf_cfg* cfg, int32_t bprec, int64_t points_per_chunk, const cnerf_volumes* vols, const cnerf_field_params* P,
+                               const float* packed, const void* packed_bwd, const float* freq, const float* phase, const float* points,
+                               int64_t n_per_image, const float* saved_rgb_sigma, const float* grad_rgb_sigma, const cnerf_field_param_grads* G,
+                               float* grad_freq, float* grad_phase, const cnerf_grad_volumes* grad_vols, float* grad_points, uint32_t* saturated,
+                               void* workspace, void* stream) {
+    g_err[0] = 0;
+    return query_backward(false, cfg, bprec, points_per_chunk, vols, P, packed, packed_bwd, freq, phase, points, n_per_image, saved_rgb_sigma,
+                          grad_rgb_sigma, G, grad_freq, grad_phase, grad_vols, grad_points, saturated, workspace, stream);
+}
 
 int cnerf_feature_points_grad(const cnerf_cfg* cfg, const cnerf_volumes* vols, const float* points, int64_t n_per_image, const float* grad_feat,
                               float* grad_points, void* stream) {
@@ -1611,6 +1624,197 @@ int cnerf_pfilm_backward_finish(const cnerf_cfg* cfg, const cnerf_field_params* 
         return fail(CNERF_EINVAL, "pfilm_backward_finish: packed_map, act_*, grad_feat and workspace must be 16-byte aligned");
     return pfilm_finish_run(cfg, F, packed_map, n_images, (long long)n_per_image, points, act_feat, act_h, act_g, act_go, G, grad_fvol_cl, grad_feat, workspace,
                             (hipStream_t)stream_);
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// ray batches: the render on caller-given rays (B, P) instead of the R x R pinhole grid
+// ---------------------------------------------------------------------------------------------------------------------
+namespace {
+int check_rays_cfg(const cnerf_cfg* c, long long P, const char* who) {
+    if (int rc = check_cfg(c, false)) return rc;
+    if (c->S < 2 || c->S > 128) return fail(CNERF_EINVAL, "%s: S=%d out of range [2,128]", who, c->S);
+    if (P < 1) return fail(CNERF_EINVAL, "%s: rays_per_image=%lld must be >= 1", who, P);
+    if (c->drop_p > 0.0f) return fail(CNERF_EINVAL, "%s: dropout (drop_p > 0) is not implemented for ray batches (cnerf_render_forward has it)", who);
+    return CNERF_OK;
+}
+int check_rays(const cnerf_rays* r, const char* who) {
+    if (!r) return fail(CNERF_EINVAL, "%s: rays is NULL", who);
+    if (!r->origins || !r->dirs) return fail(CNERF_EINVAL, "%s: rays.origins / rays.dirs is NULL", who);
+    return CNERF_OK;
+}
+// Workspace of cnerf_render_rays_forward (every piece 256-byte aligned): the coarse and fine rgb_sigma (N, 4) and z (N), the sample
+// positions of the pass in flight (N, 3); N = B P S
+struct RaysForwardLayout {
+    size_t c_rs, f_rs, c_z, f_z, pts, total;
+};
+RaysForwardLayout rays_forward_layout(const cnerf_cfg* c, long long P) {
+    const size_t N = (size_t)c->B * (size_t)P * c->S;
+    RaysForwardLayout F{};
+    size_t off = 0;
+    auto take = [&](size_t bytes) { const size_t o = off; off += align256(bytes); return o; };
+    F.c_rs = take(N * 4 * sizeof(float));
+    F.f_rs = take(N * 4 * sizeof(float));
+    F.c_z = take(N * sizeof(float));
+    F.f_z = take(N * sizeof(float));
+    F.pts = take(N * 3 * sizeof(float));
+    F.total = off;
+    return F;
+}
+// Workspace of cnerf_render_rays_backward: d loss / d rgb_sigma of the coarse and fine samples (N, 4), the positions of the pass in flight
+// and their gradients (N, 3 each), then the workspace of a field query of P S points per image
+struct RaysBackwardLayout {
+    size_t gc, gf, pts, gpts, query, total;
+};
+int rays_backward_layout(const cnerf_cfg* c, int bprec, long long P, long long ppc, RaysBackwardLayout& R) {
+    QueryLayout Q;
+    if (int rc = query_layout(c, bprec, ppc, Q)) return rc;
+    const size_t N = (size_t)c->B * (size_t)P * c->S;
+    size_t off = 0;
+    auto take = [&](size_t bytes) { const size_t o = off; off += align256(bytes); return o; };
+    R.gc = take(N * 4 * sizeof(float));
+    R.gf = take((c->flags & CNERF_F_HIERARCHICAL) ? N * 4 * sizeof(float) : 0);
+    R.pts = take(N * 3 * sizeof(float));
+    R.gpts = take(N * 3 * sizeof(float));
+    R.query = take(Q.total);
+    R.total = off;
+    return CNERF_OK;
+}
+}  // namespace
+
+int cnerf_render_rays_workspace_bytes(const cnerf_cfg* cfg, int64_t rays_per_image, size_t* fwd_ws) {
+    g_err[0] = 0;
+    if (int rc = check_rays_cfg(cfg, (long long)rays_per_image, "render_rays_workspace_bytes")) return rc;
+    if (fwd_ws) *fwd_ws = rays_forward_layout(cfg, (long long)rays_per_image).total;
+    return CNERF_OK;
+}
+
+int cnerf_render_rays_forward(const cnerf_cfg* cfg, const cnerf_rays* rays, int64_t rays_per_image, const cnerf_volumes* vols, const float* packed,
+                              const float* freq, const float* phase, const cnerf_rng* rng, float* pixels, float* dist, const cnerf_aux* aux,
+                              void* workspace, void* stream_) {
+    g_err[0] = 0;
+    const long long P = (long long)rays_per_image;
+    if (int rc = check_rays_cfg(cfg, P, "render_rays_forward")) return rc;
+    if (int rc = check_rays(rays, "render_rays_forward")) return rc;
+    if ((!vols && !no_volume(cfg)) || !packed || !pixels || !dist || !workspace) return fail(CNERF_EINVAL, "render_rays_forward: NULL argument");
+    if (counts_of(cfg).n_film && (!freq || !phase)) return fail(CNERF_EINVAL, "render_rays_forward: FiLM layers need freq and phase");
+    const bool hier = cfg->flags & CNERF_F_HIERARCHICAL;
+    rng = rng_or_none(rng);
+    if (hier && !rng->u_fine && !cfg->philox) return fail(CNERF_EINVAL, "render_rays_forward: hierarchical sampling needs rng.u_fine (or cfg.philox)");
+    hipStream_t stream = (hipStream_t)stream_;
+
+    const int S = cfg->S;
+    const long long n_rays = (long long)cfg->B * P, npi = P * S;
+    const RaysForwardLayout F = rays_forward_layout(cfg, P);
+    char* ws = (char*)workspace;
+    float* c_rs = (float*)(ws + F.c_rs);
+    float* f_rs = (float*)(ws + F.f_rs);
+    float* c_z = (float*)(ws + F.c_z);
+    float* f_z = (float*)(ws + F.f_z);
+    float* c_pts = (float*)(ws + F.pts);
+    float* f_pts = c_pts;
+    if (aux) {   // write straight into the caller's buffers where given
+        if (aux->coarse_rgb_sigma) c_rs = aux->coarse_rgb_sigma;
+        if (aux->fine_rgb_sigma) f_rs = aux->fine_rgb_sigma;
+        if (aux->coarse_z) c_z = aux->coarse_z;
+        if (aux->fine_z) f_z = aux->fine_z;
+        if (aux->coarse_points) c_pts = aux->coarse_points;
+        if (aux->fine_points) f_pts = aux->fine_points;
+    }
+    // both field passes: the network at explicit points, no dropout (refused above)
+    FieldArgs fa;
+    if (int rc = points_args(fa, cfg, vols, nullptr, packed, freq, phase, c_pts, 0, cfg->B, npi, nullptr)) return rc;
+
+    // 1. coarse pass: stratified depths and positions, the field
+    RaySampleArgs sa{rays->origins, rays->dirs, nullptr, rng->u_strat, c_z, c_pts, n_rays, S, cfg->ray_start, cfg->ray_end, philox_of(cfg)};
+    if (hipError_t e = launch_ray_sample(sa, stream)) return hip_fail(e, "ray_sample (coarse)");
+    fa.rgb_sigma = c_rs;
+    if (hipError_t e = launch_forward(fa, cfg, stream)) return hip_fail(e, "field kernel (coarse)");
+    if (hier) {
+        // 2. coarse weights -> inverse-CDF depths
+        ResampleArgs ra{c_z, nullptr, c_rs, rng->eps_coarse, rng->u_fine, f_z, aux ? aux->inds : nullptr, aux ? aux->cdf : nullptr,
+                        aux ? aux->coarse_weights : nullptr, n_rays, S, cfg->noise_std, cfg->flags, philox_of(cfg)};
+        if (hipError_t e = launch_resample(ra, stream)) return hip_fail(e, "resample");
+        // 3. fine pass
+        if (rng->fine_z) f_z = const_cast<float*>(rng->fine_z);   // teacher-forced depths (read only from here on)
+        sa.z = f_z;
+        sa.u_strat = nullptr;
+        sa.z_out = nullptr;
+        sa.points = f_pts;
+        if (hipError_t e = launch_ray_sample(sa, stream)) return hip_fail(e, "ray_sample (fine)");
+        fa.points = f_pts;
+        fa.rgb_sigma = f_rs;
+        if (hipError_t e = launch_forward(fa, cfg, stream)) return hip_fail(e, "field kernel (fine)");
+    }
+    // 4. merge + composite, outputs per ray
+    MergeArgs ma{c_rs, c_z, hier ? f_rs : nullptr, hier ? f_z : nullptr, rng->eps_final, pixels, dist, aux ? aux->sort_idx : nullptr,
+                 aux ? aux->final_weights : nullptr, n_rays, S, RayGeom{}, cfg->noise_std, cfg->flags, philox_of(cfg), 1};
+    if (hipError_t e = launch_merge_composite(ma, stream)) return hip_fail(e, "merge_composite");
+    return CNERF_OK;
+}
+
+int cnerf_render_rays_backward_workspace_bytes(const cnerf_cfg* cfg, int32_t backward_precision, int64_t rays_per_image, int64_t points_per_chunk,
+                                               size_t* bytes) {
+    g_err[0] = 0;
+    if (int rc = check_rays_cfg(cfg, (long long)rays_per_image, "render_rays_backward_workspace_bytes")) return rc;
+    RaysBackwardLayout R;
+    if (int rc = rays_backward_layout(cfg, backward_precision, (long long)rays_per_image, (long long)points_per_chunk, R)) return rc;
+    if (bytes) *bytes = R.total;
+    return CNERF_OK;
+}
+
+int cnerf_render_rays_backward(const cnerf_cfg* cfg, int32_t bprec, int64_t points_per_chunk, const cnerf_rays* rays, int64_t rays_per_image,
+                               const cnerf_volumes* vols, const cnerf_field_params* params, const float* packed, const void* packed_bwd,
+                               const float* freq, const float* phase, const cnerf_rng* rng, const cnerf_saved* saved, const float* grad_pixels,
+                               const float* grad_dist, const cnerf_field_param_grads* grads, float* grad_freq, float* grad_phase,
+                               const cnerf_grad_volumes* grad_vols, float* grad_origins, float* grad_dirs, uint32_t* saturated, void* workspace,
+                               void* stream_) {
+    g_err[0] = 0;
+    const long long P = (long long)rays_per_image;
+    if (int rc = check_rays_cfg(cfg, P, "render_rays_backward")) return rc;
+    if (int rc = check_rays(rays, "render_rays_backward")) return rc;
+    RaysBackwardLayout R;
+    if (int rc = rays_backward_layout(cfg, bprec, P, (long long)points_per_chunk, R)) return rc;
+    if (!saved || !grad_pixels || !workspace) return fail(CNERF_EINVAL, "render_rays_backward: NULL argument");
+    const bool hier = cfg->flags & CNERF_F_HIERARCHICAL;
+    if (!saved->coarse_rgb_sigma || !saved->coarse_z || (hier && (!saved->fine_rgb_sigma || !saved->fine_z)))
+        return fail(CNERF_EINVAL, "render_rays_backward: saved rgb_sigma / z of the forward are incomplete");
+    const int S = cfg->S;
+    const long long n_rays = (long long)cfg->B * P, npi = P * S;
+    char* ws = (char*)workspace;
+    float* gc = (float*)(ws + R.gc);
+    float* gf = hier ? (float*)(ws + R.gf) : nullptr;
+    float* pts = (float*)(ws + R.pts);
+    float* gpts = grad_origins || grad_dirs ? (float*)(ws + R.gpts) : nullptr;
+    // every refusal of the field passes before the first launch
+    if (int rc = query_backward(true, cfg, bprec, points_per_chunk, vols, params, packed, packed_bwd, freq, phase, pts, npi, saved->coarse_rgb_sigma, gc, grads,
+                                grad_freq, grad_phase, grad_vols, gpts, saturated, ws + R.query, stream_))
+        return rc;
+    rng = rng_or_none(rng);
+    hipStream_t stream = (hipStream_t)stream_;
+
+    // 1. d(pixels, dist) -> d(rgb_sigma) of every coarse / fine sample
+    MergeBwdArgs mb{saved->coarse_rgb_sigma, saved->coarse_z, hier ? saved->fine_rgb_sigma : nullptr, hier ? saved->fine_z : nullptr,
+                    cfg->noise_std != 0.0f ? rng->eps_final : nullptr, grad_pixels, grad_dist, gc, gf, n_rays, S, RayGeom{}, cfg->noise_std, cfg->flags,
+                    philox_of(cfg), 1};
+    if (hipError_t e = launch_merge_composite_backward(mb, stream)) return hip_fail(e, "merge_composite_backward");
+    // 2. per pass: the sample positions again from the forward's depths, the field query's backward on them (chunked by points_per_chunk),
+    //    the position gradients reduced onto the rays -- coarse samples first, then the fine ones
+    for (int pass = 0; pass < (hier ? 2 : 1); ++pass) {
+        const float* z = pass ? saved->fine_z : saved->coarse_z;
+        RaySampleArgs sa{rays->origins, rays->dirs, z, nullptr, nullptr, pts, n_rays, S, cfg->ray_start, cfg->ray_end, philox_of(cfg)};
+        if (hipError_t e = launch_ray_sample(sa, stream)) return hip_fail(e, "ray_sample");
+        if (gpts)
+            if (hipError_t e = hipMemsetAsync(gpts, 0, (size_t)n_rays * S * 3 * sizeof(float), stream)) return hip_fail(e, "memset");
+        if (int rc = query_backward(false, cfg, bprec, points_per_chunk, vols, params, packed, packed_bwd, freq, phase, pts, npi,
+                                    pass ? saved->fine_rgb_sigma : saved->coarse_rgb_sigma, pass ? gf : gc, grads, grad_freq, grad_phase, grad_vols, gpts,
+                                    saturated, ws + R.query, stream_))
+            return rc;
+        if (gpts) {
+            RayGradArgs rg{gpts, z, grad_origins, grad_dirs, n_rays, S};
+            if (hipError_t e = launch_ray_grad_reduce(rg, stream)) return hip_fail(e, "ray_grad_reduce");
+        }
+    }
+    return CNERF_OK;
 }
 
 }  // extern "C"

@@ -184,8 +184,8 @@ struct MergeArgs {
     const float* fine_rgb_sigma;    // (rays,S,4) or null (non-hierarchical)
     const float* fine_z;            // (rays,S)   or null
     const float* eps;               // (rays,n) or null, n = 2S or S
-    float* pixels;                  // (B,3,R,R)
-    float* depth;                   // (B,R,R)
+    float* pixels;                  // (B,3,R,R); per_ray: (rays,3)
+    float* depth;                   // (B,R,R);   per_ray: (rays) distance along the ray
     int32_t* sort_idx;              // optional (rays,2S)
     float* final_weights;           // optional (rays,n)
     long long rays;
@@ -194,6 +194,7 @@ struct MergeArgs {
     float noise_std;
     uint32_t flags;
     PhiloxKey philox;               // draws eps (final) in the kernel where the tensor is null
+    int per_ray;                    // 1: a ray batch -- outputs per ray, geom is not read (0: the R x R grid's image layout and depth)
 };
 hipError_t launch_merge_composite(const MergeArgs& a, hipStream_t stream);
 
@@ -203,8 +204,8 @@ struct MergeBwdArgs {
     const float* fine_rgb_sigma;    // (rays,S,4) or null
     const float* fine_z;            // (rays,S)   or null
     const float* eps;               // (rays,n) or null
-    const float* grad_pixels;       // (B,3,R,R)
-    const float* grad_depth;        // (B,R,R) or null
+    const float* grad_pixels;       // (B,3,R,R); per_ray: (rays,3)
+    const float* grad_depth;        // (B,R,R) or null; per_ray: (rays) d loss / d distance
     float* grad_coarse;             // (rays,S,4)
     float* grad_fine;               // (rays,S,4) or null
     long long rays;
@@ -213,8 +214,33 @@ struct MergeBwdArgs {
     float noise_std;
     uint32_t flags;
     PhiloxKey philox;
+    int per_ray;                    // as MergeArgs
 };
 hipError_t launch_merge_composite_backward(const MergeBwdArgs& a, hipStream_t stream);
+
+// ray_batch.hip: sample positions of caller-given rays, and the rays' gradients from those of the sample positions
+struct RaySampleArgs {
+    const float* origins;    // (rays,3) world
+    const float* dirs;       // (rays,3) world, not normalised here: depths are in units of |dir|
+    const float* z;          // (rays,S) depths to sample at, or null: the stratified coarse depths from ...
+    const float* u_strat;    // ... (rays,S) jitter draws, or null: Philox stream 0 at the element's index, or 0.5
+    float* z_out;            // (rays,S) the coarse depths (z == null only)
+    float* points;           // (rays,S,3) o + d z
+    long long rays;
+    int S;
+    float ray_start, ray_end;
+    PhiloxKey philox;
+};
+hipError_t launch_ray_sample(const RaySampleArgs& a, hipStream_t stream);
+struct RayGradArgs {         // grad_origins (rays,3) += sum_s g, grad_dirs (rays,3) += sum_s z g (each may be null)
+    const float* grad_points;  // (rays,S,3)
+    const float* z;            // (rays,S)
+    float* grad_origins;
+    float* grad_dirs;
+    long long rays;
+    int S;
+};
+hipError_t launch_ray_grad_reduce(const RayGradArgs& a, hipStream_t stream);
 
 hipError_t launch_philox_fill(const PhiloxKey& k, uint32_t stream_id, long long n, int normal, float* out, hipStream_t stream);
 hipError_t launch_transpose_cl(int B, int C, int V, const float* src, float* dst, bool to_channel_last, hipStream_t stream);

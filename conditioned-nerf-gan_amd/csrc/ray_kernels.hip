@@ -222,6 +222,8 @@ __global__ __launch_bounds__(256) void resample_kernel(ResampleArgs a) {
 // ---------------------------------------------------------------------------------------------------------------
 // merge [fine, coarse] by depth (rank sort in LDS) + final composite + output formatting
 // ---------------------------------------------------------------------------------------------------------------
+// PER_RAY: the epilogue of a ray batch (cnerf_render_rays_forward) -- pixels (rays,3), the distance along the ray as it is
+template <bool PER_RAY>
 __global__ __launch_bounds__(256) void merge_composite_kernel(MergeArgs a) {
     __shared__ float s_z[RAYS_PER_BLOCK][MAX_N];
     __shared__ f32x4 s_rs[RAYS_PER_BLOCK][MAX_N];
@@ -283,7 +285,15 @@ __global__ __launch_bounds__(256) void merge_composite_kernel(MergeArgs a) {
         for (int c = 0; c < CHUNKS; ++c)
             if (c * WAVE + lane < n) a.final_weights[ray * n + c * WAVE + lane] = w[c];
     }
-    if (lane == 0) {
+    if (PER_RAY) {
+        if (lane == 0) {
+            float* px = a.pixels + ray * 3;
+            px[0] = s.r * 2.0f - 1.0f;
+            px[1] = s.g * 2.0f - 1.0f;
+            px[2] = s.b * 2.0f - 1.0f;
+            a.depth[ray] = s.dist;
+        }
+    } else if (lane == 0) {
         const int R = a.geom.R;
         const long long P = (long long)R * R;
         const long long b = ray / P, p = ray - b * P;
@@ -306,6 +316,7 @@ __global__ __launch_bounds__(256) void merge_composite_kernel(MergeArgs a) {
 //   dL/dalpha_i = Gw_i T_i - (sum_{k>i} Gw_k w_k) / s_i ,   dL/dsigma_i = dL/dalpha_i * delta_i exp(-delta_i dens_i) act'(.)
 // Autograd twin of fancy_integration (volumetric_rendering.py:18-70) and generators.py:162-186.
 // ---------------------------------------------------------------------------------------------------------------
+template <bool PER_RAY>
 __global__ __launch_bounds__(256) void merge_composite_backward_kernel(MergeBwdArgs a) {
     __shared__ float s_z[RAYS_PER_BLOCK][MAX_N];
     __shared__ f32x4 s_rs[RAYS_PER_BLOCK][MAX_N];
@@ -364,15 +375,22 @@ __global__ __launch_bounds__(256) void merge_composite_backward_kernel(MergeBwdA
     wave_lds_sync();
 
     // upstream gradients of this ray
-    const int R = a.geom.R;
-    const long long P = (long long)R * R;
-    const long long b = ray / P, p = ray - b * P;
-    const int row = (int)(p / R), col = (int)(p - (long long)row * R);
-    float dx, dy, dz;
-    camera_dir(a.geom, row, col, dx, dy, dz);
-    const float* gp = a.grad_pixels + b * 3 * P + p;
-    const float gr = 2.0f * gp[0], gg = 2.0f * gp[P], gb = 2.0f * gp[2 * P];   // pixels = 2 rgb - 1
-    const float gd = a.grad_depth ? dz * a.grad_depth[ray] : 0.0f;              // depth = dir_z * dist
+    float gr, gg, gb, gd;
+    if (PER_RAY) {
+        const float* gp = a.grad_pixels + ray * 3;
+        gr = 2.0f * gp[0], gg = 2.0f * gp[1], gb = 2.0f * gp[2];
+        gd = a.grad_depth ? a.grad_depth[ray] : 0.0f;
+    } else {
+        const int R = a.geom.R;
+        const long long P = (long long)R * R;
+        const long long b = ray / P, p = ray - b * P;
+        const int row = (int)(p / R), col = (int)(p - (long long)row * R);
+        float dx, dy, dz;
+        camera_dir(a.geom, row, col, dx, dy, dz);
+        const float* gp = a.grad_pixels + b * 3 * P + p;
+        gr = 2.0f * gp[0], gg = 2.0f * gp[P], gb = 2.0f * gp[2 * P];          // pixels = 2 rgb - 1
+        gd = a.grad_depth ? dz * a.grad_depth[ray] : 0.0f;                     // depth = dir_z * dist
+    }
     const NoiseSrc eps{a.eps ? a.eps + ray * n : nullptr, a.philox, PHILOX_EPS_FINAL, (unsigned long long)ray * n};
 
     // forward recompute (same arithmetic as composite_ray) keeping alpha, trans, exp(-delta dens), act'
@@ -614,12 +632,13 @@ hipError_t launch_resample(const ResampleArgs& a, hipStream_t stream) {
 }
 hipError_t launch_merge_composite(const MergeArgs& a, hipStream_t stream) {
     const unsigned blocks = (unsigned)((a.rays + RAYS_PER_BLOCK - 1) / RAYS_PER_BLOCK);
-    hipLaunchKernelGGL(merge_composite_kernel, dim3(blocks), dim3(256), 0, stream, a);
+    hipLaunchKernelGGL(a.per_ray ? merge_composite_kernel<true> : merge_composite_kernel<false>, dim3(blocks), dim3(256), 0, stream, a);
     return hipGetLastError();
 }
 hipError_t launch_merge_composite_backward(const MergeBwdArgs& a, hipStream_t stream) {
     const unsigned blocks = (unsigned)((a.rays + RAYS_PER_BLOCK - 1) / RAYS_PER_BLOCK);
-    hipLaunchKernelGGL(merge_composite_backward_kernel, dim3(blocks), dim3(256), 0, stream, a);
+    hipLaunchKernelGGL(a.per_ray ? merge_composite_backward_kernel<true> : merge_composite_backward_kernel<false>, dim3(blocks), dim3(256), 0, stream,
+                       a);
     return hipGetLastError();
 }
 hipError_t launch_transpose_cl(int B, int C, int V, const float* src, float* dst, bool to_channel_last,

@@ -103,6 +103,35 @@ class ImplicitGenerator3d(nn.Module):
             aux_out.update(aux)
         return pixels, depth
 
+    def render_rays(self, z, origins, dirs, ray_start, ray_end, num_steps, hierarchical_sample, **kwargs):
+        """`forward` on rays the caller formed instead of the square pinhole grid: a crop or a non-square image, a random subset of
+        pixels, intrinsics with a principal-point offset, one tile of a large image (volumetric_rendering.pinhole_rays makes the
+        grid's rays for any rows / columns).  origins, dirs: (B,P,3) world; directions are not normalised here and depths are in
+        units of |dir|.  z and the kwargs as in `forward`: clamp_mode and nerf_noise are required; white_back, last_back, `_rng` and
+        `_aux` optional.  rng_mode "torch" draws as `forward` does for P rays (draw_rng(B, P, S, ...): same order and shapes),
+        "philox" draws in the kernels.  Differentiable w.r.t. everything `forward` is, and w.r.t. origins and dirs (the sample
+        depths carry no gradient, as in the reference).  Dropout is not implemented here: a training-mode network with
+        drop_out > 0 raises NotImplementedError.
+        Returns pixels (B,P,3) = 2*rgb-1 and dist (B,P) = sum of weight * depth along the ray."""
+        net = self.siren
+        net.check_supported()
+        if net.drop_out and net.training:
+            raise NotImplementedError("render_rays has no dropout: call eval() first, or use forward, the path that has dropout")
+        clamp_mode, noise_std = kwargs["clamp_mode"], kwargs["nerf_noise"]
+        white_back, last_back = kwargs.get("white_back", False), kwargs.get("last_back", False)
+        fvol, glob = net.split_z(z)
+        B, P, S = origins.shape[0], origins.shape[1], int(num_steps)
+        freq, phase = net.film(glob)
+        rng = kwargs.get("_rng")
+        if rng is None:
+            rng = {"philox": self._philox_key()} if self.rng_mode == "philox" else draw_rng(B, P, S, bool(hierarchical_sample), noise_std, origins.device)
+        aux_out = kwargs.get("_aux")
+        pixels, dist, aux = ops.render_rays(net, fvol, freq, phase, origins, dirs, ray_start, ray_end, S, bool(hierarchical_sample), clamp_mode,
+                                            noise_std, white_back, last_back, rng, want_aux=aux_out is not None)
+        if aux_out is not None:
+            aux_out.update(aux)
+        return pixels, dist
+
     def generate_avg_frequencies(self):
         """Mean FiLM frequencies / phase shifts over 10000 random latents (generators.py:189-197)."""
         zs = torch.randn((10000, self.z_dim), device=self.siren.device)

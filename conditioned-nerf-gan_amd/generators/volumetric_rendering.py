@@ -81,3 +81,26 @@ def importance_sample(z_vals, weights, u):
 def distance2depth(distance, ray):
     """Distance along the ray -> camera-space z (volumetric_rendering.py:345-356)."""
     return ray[..., -1:] * distance
+
+
+def pinhole_rays(cam2worlds, img_size, fov, rows=None, cols=None):
+    """World origins and directions (B,P,3) of pixels of the square img_size x img_size pinhole grid that
+    ImplicitGenerator3d.forward renders (volumetric_rendering.py:73-199 of the reference), for ImplicitGenerator3d.render_rays.
+    rows / cols: 1-D index tensors or sequences selecting the crop rows x cols -- P = len(rows) * len(cols), row-major, non-square
+    allowed; None = all of them, so the default is the whole grid with pixel p = row * img_size + col.  For a scattered subset of
+    pixels index the whole grid's rays.
+    Plain torch on the device of cam2worlds.  The directions agree with the grid kernels' to rounding (about 1e-7), not bit for bit:
+    the kernels evaluate the 3x3 rotation as the fused chain of the reference's CPU BLAS, this is a product and a sum."""
+    R = int(img_size)
+    dev = cam2worlds.device
+    lin = torch.linspace(-1, 1, R, device=dev)
+    rows = torch.arange(R, device=dev) if rows is None else torch.as_tensor(rows, device=dev, dtype=torch.long)
+    cols = torch.arange(R, device=dev) if cols is None else torch.as_tensor(cols, device=dev, dtype=torch.long)
+    y = lin[rows].repeat_interleave(cols.numel())
+    x = lin[cols].repeat(rows.numel())
+    focal = float(np.float32(1.0) / np.float32(np.tan((2 * np.pi * fov / 360) / 2)))   # fp32 like the reference: ones / tan
+    d = normalize_vecs(torch.stack([x, y, torch.full_like(x, focal)], -1))             # (P,3) camera space, unit length
+    c2w = cam2worlds.to(torch.float32)
+    dirs = (c2w[:, None, :3, :3] * d[None, :, None, :]).sum(-1)                        # (B,P,3): the rotation alone
+    origins = c2w[:, None, :3, 3].expand_as(dirs)
+    return origins.contiguous(), dirs.contiguous()

@@ -657,3 +657,138 @@ class FieldQueryFunction(torch.autograd.Function):
                                                                     want_points=ctx.needs_input_grad[5])
         g_vols = g_levels if ctx.vols_channel_last else _caller_format(g_levels, ctx.vol_is_cl)
         return (None, None, None, g_freq, g_phase, g_pts, None, *g_vols, *g_params)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# ray batches: the render on caller-given rays (cnerf_render_rays_forward / _backward) as one autograd node
+# ---------------------------------------------------------------------------------------------------------------------
+RAY_RNG_KEYS = ("u_strat", "eps_coarse", "u_fine", "eps_final", "fine_z")
+
+
+def _rays_struct(origins, dirs):
+    r = L.Rays()
+    r.origins, r.dirs = L.ptr(origins).value, L.ptr(dirs).value
+    return r
+
+
+def _rays_cfg(net, o, levels, precision=None, rng=None):
+    return make_cfg(net, o["B"], levels, 1, o["S"], 30.0, o["ray_start"], o["ray_end"], o["noise_std"], o["hier"], o["white_back"], o["last_back"],
+                    o["clamp_mode"], precision=precision, philox=(rng or {}).get("philox"))
+
+
+def render_rays_forward(net, levels, freq, phase, origins, dirs, o, rng=None, want_aux=False, aux_keys=None):
+    """cnerf_render_rays_forward on channel-last levels: origins / dirs (B,P,3) -> pixels (B,P,3), dist (B,P), aux dict."""
+    origins, dirs = _f32(origins), _f32(dirs)
+    if origins.dim() != 3 or origins.shape[-1] != 3 or dirs.shape != origins.shape:
+        raise L.CnerfError(f"render_rays: origins and dirs must both be (B,P,3), got {tuple(origins.shape)} and {tuple(dirs.shape)}")
+    B, P, S, hier = o["B"], int(origins.shape[1]), o["S"], o["hier"]
+    n = 2 * S if hier else S
+    dev = origins.device
+    cfg = _rays_cfg(net, o, levels, rng=rng)
+    packed = pack_field(net, cfg)
+    nb = C.c_size_t(0)
+    L.check(L.lib().cnerf_render_rays_workspace_bytes(C.byref(cfg), P, C.byref(nb)), "cnerf_render_rays_workspace_bytes")
+    ws = torch.empty(nb.value, dtype=torch.uint8, device=dev)
+    pixels = torch.empty((B, P, 3), dtype=torch.float32, device=dev)
+    dist = torch.empty((B, P), dtype=torch.float32, device=dev)
+    r, keep = _rng_struct(rng or {}, RAY_RNG_KEYS)
+    aux_t, aux_s = {}, None
+    if want_aux or aux_keys:
+        aux_s = L.Aux()
+        for k in (L.AUX_FIELDS if want_aux else aux_keys):
+            if not hier and k in HIER_ONLY:
+                continue
+            shape, dt = AUX_SHAPES[k](B, P, S, n)
+            aux_t[k] = torch.empty(shape, dtype=dt, device=dev)
+            setattr(aux_s, k, aux_t[k].data_ptr())
+    vs, rs = volumes_struct(levels), _rays_struct(origins, dirs)
+    L.check(L.lib().cnerf_render_rays_forward(C.byref(cfg), C.byref(rs), P, C.byref(vs), L.ptr(packed), L.ptr(_f32(freq)), L.ptr(_f32(phase)), C.byref(r),
+                                              L.ptr(pixels), L.ptr(dist), C.byref(aux_s) if aux_s is not None else None, L.ptr(ws), _stream()),
+            "cnerf_render_rays_forward")
+    return pixels, dist, aux_t
+
+
+def render_rays_backward(net, o, levels, freq, phase, origins, dirs, rng, saved, grad_pixels, grad_dist, want_rays):
+    """Gradients of one ray render w.r.t. (channel-last volume levels, freq, phase, field parameters, origins, dirs): ONE call into the
+    library (cnerf_render_rays_backward); its field passes are chunked like a field query's (query_chunk)."""
+    global LAST_SATURATED
+    B, P, S, hier = o["B"], int(origins.shape[1]), o["S"], o["hier"]
+    dev = origins.device
+    bprec = backward_precision_of(net)
+    pfilm32 = net.spec.layers[0] == "pfilm" and bprec == "fp32"
+    cfg = _rays_cfg(net, o, levels, precision="fp16x3" if bprec == "fp16" else ("fp32" if pfilm32 else None), rng=rng)
+    w = _backward_setup(net, cfg, levels, B, dev)
+    g_org = torch.zeros_like(origins) if want_rays[0] else None
+    g_dir = torch.zeros_like(dirs) if want_rays[1] else None
+
+    def bytes_of(ppc):
+        nb = C.c_size_t(0)
+        L.check(L.lib().cnerf_render_rays_backward_workspace_bytes(C.byref(cfg), w.code, P, int(ppc), C.byref(nb)), "cnerf_render_rays_backward_workspace_bytes")
+        return nb.value
+
+    ppc, ws_bytes = query_chunk(P * S, bytes_of, dev)
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+    r, keep = _rng_struct(rng, ("u_strat", "eps_final"))
+    c_rs, c_z, f_rs, f_z = saved[:4]
+    sv = L.Saved()
+    sv.coarse_rgb_sigma, sv.coarse_z = L.ptr(c_rs).value, L.ptr(c_z).value
+    if hier:
+        sv.fine_rgb_sigma, sv.fine_z = L.ptr(f_rs).value, L.ptr(f_z).value
+    rs = _rays_struct(origins, dirs)
+    L.check(L.lib().cnerf_render_rays_backward(C.byref(cfg), w.code, ppc, C.byref(rs), P, C.byref(w.vs), C.byref(w.fp), L.ptr(w.packed), L.ptr(w.packed_bwd),
+                                               L.ptr(freq), L.ptr(phase), C.byref(r), C.byref(sv), L.ptr(_f32(grad_pixels)), L.ptr(_f32(grad_dist)),
+                                               C.byref(w.gp), L.ptr(w.g_freq), L.ptr(w.g_phase), C.byref(w.gvs), L.ptr(g_org), L.ptr(g_dir), L.ptr(w.sat),
+                                               L.ptr(ws), _stream()), "cnerf_render_rays_backward")
+    if w.sat is not None:
+        LAST_SATURATED = w.sat
+    return w.grad_levels, w.g_freq, w.g_phase, w.grads, g_org, g_dir
+
+
+class RenderRaysFunction(torch.autograd.Function):
+    """ImplicitGenerator3d.render_rays as one autograd node: differentiable w.r.t. the feature volume(s), freq / phase (and through them
+    the mapping network and the global feature), the field parameters and the rays' origins and directions; the sample depths carry no
+    gradient (the reference draws and resamples them under no_grad: generators.py:57,111)."""
+
+    @staticmethod
+    def forward(ctx, net, o, rng, origins, dirs, freq, phase, n_vols, *rest):
+        vols, params = rest[:n_vols], rest[n_vols:]
+        levels = [channel_last(v.detach()) for v in vols]
+        ctx.vol_is_cl = _is_channel_last(levels, vols)
+        fr = _f32(freq.detach()) if freq is not None else None
+        ph = _f32(phase.detach()) if phase is not None else None
+        org, drs = _f32(origins.detach()), _f32(dirs.detach())
+        need_grad = o["need_grad"]
+        pixels, dist, aux = render_rays_forward(net, levels, fr, ph, org, drs, o, rng, want_aux=o["want_aux"],
+                                                aux_keys=SAVED_KEYS if need_grad and not o["want_aux"] else None)
+        ctx.net, ctx.o, ctx.rng, ctx.n_vols = net, o, rng, n_vols
+        if need_grad:
+            saved = [aux.get(k) for k in SAVED_KEYS]
+            if o["hier"] and rng.get("fine_z") is not None:
+                saved[3] = _f32(rng["fine_z"]).reshape(saved[1].shape)   # teacher-forced depths are what the fine pass used
+            ctx.saved = (levels, fr, ph, org, drs, tuple(saved))
+        RenderRaysFunction.last_aux = aux
+        return pixels, dist
+
+    @staticmethod
+    def backward(ctx, grad_pixels, grad_dist):
+        levels, fr, ph, org, drs, saved = ctx.saved
+        g_levels, g_freq, g_phase, g_params, g_org, g_dir = render_rays_backward(
+            ctx.net, ctx.o, levels, fr, ph, org, drs, ctx.rng, saved, grad_pixels.contiguous(),
+            grad_dist.contiguous() if grad_dist is not None else None, want_rays=ctx.needs_input_grad[3:5])
+        g_vols = _caller_format(g_levels, ctx.vol_is_cl)
+        return (None, None, None, g_org, g_dir, g_freq, g_phase, None, *g_vols, *g_params)
+
+
+def render_rays(net, fvol, freq, phase, origins, dirs, ray_start, ray_end, num_steps, hierarchical, clamp_mode, noise_std,
+                white_back=False, last_back=False, rng=None, want_aux=False):
+    """Differentiable render of caller-given rays, used by ImplicitGenerator3d.render_rays.  origins / dirs (B,P,3) world (dirs are not
+    normalised here: depths are in units of |dir|); fvol: (B,C,V,V,V) or a list of pyramid levels.
+    Returns (pixels (B,P,3) = 2*rgb-1, dist (B,P) = distance along the ray, aux dict)."""
+    o = dict(B=int(origins.shape[0]), S=int(num_steps), ray_start=float(ray_start), ray_end=float(ray_end), hier=bool(hierarchical),
+             clamp_mode=clamp_mode, noise_std=float(noise_std), white_back=bool(white_back), last_back=bool(last_back), want_aux=bool(want_aux))
+    _ray_flags(clamp_mode, white_back, last_back)      # refuses an unknown clamp mode before any work
+    vols = as_levels(fvol)
+    params = net.field_params()
+    o["need_grad"] = torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (origins, dirs, freq, phase, *vols, *params))
+    pixels, dist = RenderRaysFunction.apply(net, o, rng or {}, origins, dirs, freq, phase, len(vols), *vols, *params)
+    return pixels, dist, (RenderRaysFunction.last_aux if want_aux else {})

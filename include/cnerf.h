@@ -252,8 +252,9 @@ int cnerf_render_forward(const cnerf_cfg* cfg, const cnerf_volumes* vols, const 
                          float* depth, const cnerf_aux* aux, void* workspace, void* stream);
 
 /* ---- backward (autograd twin of cnerf_render_forward; gradients flow to the field parameters, freq/phase and the
- * feature volume, never to cam2world or the sample positions: generators.py:57,111 run them under no_grad.  The render
- * backward gives no position gradient; a field query's does: cnerf_field_query_backward below) ----------
+ * feature volume, never to cam2world or the sample positions: generators.py:57,111 run them under no_grad.  This grid render's
+ * backward gives no position gradient; a field query's does (cnerf_field_query_backward below), and so does a render of caller-given
+ * rays: cnerf_render_rays_backward returns d loss / d origins and d loss / d directions) ----------
  *
  * Step 1  cnerf_merge_composite_backward: d(pixels, depth) -> d(rgb_sigma) of the coarse and the fine samples.
  * Step 2  cnerf_field_backward per pass (coarse, fine) and per chunk of images: re-runs the field forward storing the
@@ -475,6 +476,55 @@ int cnerf_pfilm_backward_finish(const cnerf_cfg* cfg, const cnerf_field_params* 
                                 const float* act_h, const float* act_g, const float* act_go,
                                 const cnerf_field_param_grads* grads, float* grad_fvol_cl, float* grad_feat,
                                 void* workspace, void* stream);
+
+/* ---- ray batches: the render on caller-given rays (added in ABI v10 without a version change: no struct changed) ------------------
+ * cnerf_render_forward serves one camera model, the square R x R pinhole grid derived from (cam2world, fov).  These entries take
+ * the rays themselves -- P = rays_per_image world origins and directions per image, any P >= 1 -- so a caller can render a crop or a
+ * non-square image, a random subset of pixels, intrinsics with a principal-point offset, a large image in tiles, and can
+ * differentiate with respect to the rays (camera).  Replaces ImplicitGenerator3d.forward (generators.py:33-187) from line 95 on, for
+ * rays formed by the caller instead of get_initial_rays_trig / transform_sampled_points (volumetric_rendering.py:73-199).
+ *
+ *   cfg        R and fov_deg are not read; S in [2,128]; the rest as cnerf_field_forward checks it.  The flags HIERARCHICAL, WHITE_BACK,
+ *              LAST_BACK, SOFTPLUS, noise_std, philox* and ray_start / ray_end keep their meaning.  drop_p > 0: CNERF_EINVAL (the grid
+ *              render has dropout).  Every layer family and precision of cnerf_field_forward / cnerf_field_query_backward.
+ *   rng        cnerf_rng with P in place of R*R; Philox streams 0-3 are indexed by (b P + p) S + s.  fine_z teacher-forces the fine pass.
+ *              drop_coarse / drop_fine are not read.
+ *   aux        cnerf_aux intermediates with P in place of R*R (sort_idx, final_weights per ray); act16 and field_events are ignored.
+ *
+ * Arithmetic: coarse depth z = zl[s] + (u - 0.5) (zl[1] - zl[0]) with zl = torch.linspace(ray_start, ray_end, S) -- bit-identical to the
+ * grid render's coarse_z for the same u (u_strat, else Philox, else 0.5); sample position per component p = o + d z, the product
+ * rounded, then the sum (no fma), in both passes: generators.py:138-142.  Depths are in units of |dir|: directions are not normalised
+ * here.  The field runs at those explicit points (the kernels of cnerf_field_forward, unfolded FiLM); resampling, the merge by depth and
+ * the compositing are the grid render's kernels.  Outputs per ray: pixels (B,P,3) = 2 rgb - 1 and dist (B,P) = sum w z, the distance
+ * along the ray in units of |dir| -- depth along a camera axis is the caller's business.
+ *
+ * Backward: cnerf_merge_composite_backward's kernel on per-ray gradients, then per pass (coarse, fine) the sample positions again from
+ * the saved depths and what cnerf_field_query_backward runs on them, chunked by points_per_chunk (the feature-volume gradient by the
+ * chain's own atomics; no patch scatter).  Sample depths carry no gradient (generators.py:57,111), so with g_s the position gradient of
+ * sample s:  grad_origins[b,p] += sum_s g_s,  grad_dirs[b,p] += sum_s z_s g_s  over the coarse, then the fine samples, reduced by one
+ * wave per ray in a fixed order without atomics: two runs agree bit for bit.  All gradient buffers are ACCUMULATED INTO (zero them
+ * first); grad_dist, grad_origins, grad_dirs may be NULL.  backward_precision, params, packed, packed_bwd, grads, saturated: as
+ * cnerf_field_query_backward; saved: the forward's cnerf_aux tensors (fine_z: the depths the fine pass used, i.e. rng->fine_z when forced).
+ * Every refusal happens before any launch; nothing is allocated or synchronised. */
+typedef struct cnerf_rays {          /* HOST struct of device pointers */
+    const float* origins;            /* (B,P,3) world */
+    const float* dirs;               /* (B,P,3) world; depths are in units of |dir| (not normalised here) */
+} cnerf_rays;
+
+int cnerf_render_rays_workspace_bytes(const cnerf_cfg* cfg, int64_t rays_per_image, size_t* fwd_ws);
+int cnerf_render_rays_forward(const cnerf_cfg* cfg, const cnerf_rays* rays, int64_t rays_per_image, const cnerf_volumes* vols,
+                              const float* packed, const float* freq, const float* phase, const cnerf_rng* rng,
+                              float* pixels /* (B,P,3) = 2*rgb-1 */, float* dist /* (B,P) = sum w z */, const cnerf_aux* aux,
+                              void* workspace, void* stream);
+int cnerf_render_rays_backward_workspace_bytes(const cnerf_cfg* cfg, int32_t backward_precision, int64_t rays_per_image,
+                                               int64_t points_per_chunk, size_t* bytes);
+int cnerf_render_rays_backward(const cnerf_cfg* cfg, int32_t backward_precision, int64_t points_per_chunk, const cnerf_rays* rays,
+                               int64_t rays_per_image, const cnerf_volumes* vols, const cnerf_field_params* params, const float* packed,
+                               const void* packed_bwd, const float* freq, const float* phase, const cnerf_rng* rng,
+                               const cnerf_saved* saved, const float* grad_pixels /* (B,P,3) */, const float* grad_dist /* (B,P) or NULL */,
+                               const cnerf_field_param_grads* grads, float* grad_freq, float* grad_phase,
+                               const cnerf_grad_volumes* grad_vols, float* grad_origins /* (B,P,3) or NULL */,
+                               float* grad_dirs /* (B,P,3) or NULL */, uint32_t* saturated, void* workspace, void* stream);
 
 #ifdef __cplusplus
 }
