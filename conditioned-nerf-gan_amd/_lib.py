@@ -51,6 +51,11 @@ class Rays(C.Structure):
     _fields_ = [("origins", C.c_void_p), ("dirs", C.c_void_p)]
 
 
+class Occupancy(C.Structure):
+    """cnerf_occupancy: one G^3-bit grid per image over the cube (lo, side); bits (B, G^3 / 32) on the device."""
+    _fields_ = [("bits", C.c_void_p), ("G", C.c_int32), ("lo", C.c_float * 3), ("side", C.c_float)]
+
+
 class Rng(C.Structure):
     _fields_ = [("u_strat", C.c_void_p), ("eps_coarse", C.c_void_p), ("u_fine", C.c_void_p), ("eps_final", C.c_void_p),
                 ("fine_z", C.c_void_p), ("drop_coarse", C.c_void_p), ("drop_fine", C.c_void_p)]
@@ -121,6 +126,14 @@ PROTOTYPES = {
                                              C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(Rng), C.POINTER(Saved), C.c_void_p, C.c_void_p,
                                              C.POINTER(FieldParamGrads), C.c_void_p, C.c_void_p, C.POINTER(Volumes), C.c_void_p, C.c_void_p, C.c_void_p,
                                              C.c_void_p, C.c_void_p]),
+    "cnerf_occupancy_build": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "cnerf_occupancy_compact_bytes": (C.c_int, [C.c_int32, C.c_int64, C.POINTER(C.c_size_t)]),
+    "cnerf_occupancy_compact": (C.c_int, [C.POINTER(Occupancy), C.c_int32, C.c_int64] + [C.c_void_p] * 6),
+    "cnerf_occupancy_expand": (C.c_int, [C.c_int32, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "cnerf_render_rays_masked_workspace_bytes": (C.c_int, [C.POINTER(Cfg), C.c_int64, C.POINTER(C.c_size_t)]),
+    "cnerf_render_rays_masked_forward": (C.c_int, [C.POINTER(Cfg), C.POINTER(Rays), C.c_int64, C.POINTER(Occupancy), C.POINTER(Volumes), C.c_void_p,
+                                                   C.c_void_p, C.c_void_p, C.POINTER(Rng), C.c_void_p, C.c_void_p, C.POINTER(Aux),
+                                                   C.POINTER(C.c_int32), C.c_void_p, C.c_void_p]),
 }
 
 _lib = None

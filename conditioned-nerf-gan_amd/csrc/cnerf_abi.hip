@@ -1,5 +1,6 @@
 // C-ABI entry points of libcnerf_hip.so (declared in include/cnerf.h).  Host-side only: argument validation, buffer
-// carving, launch sequencing on the caller's stream.  No allocation, no synchronisation, no global state.
+// carving, launch sequencing on the caller's stream.  No allocation, no synchronisation, no global state -- with one exception, stated in
+// the header: cnerf_render_rays_masked_forward reads the live counts of its compactions back and synchronises the stream for them.
 #include <math.h>
 #include <stdarg.h>
 #include <stdio.h>
@@ -1815,6 +1816,204 @@ int cnerf_render_rays_backward(const cnerf_cfg* cfg, int32_t bprec, int64_t poin
         }
     }
     return CNERF_OK;
+}
+
+}  // extern "C"
+
+// ---------------------------------------------------------------------------------------------------------------------
+// occupancy grids: forward-only ray renders that skip empty space (csrc/occupancy.hip)
+// ---------------------------------------------------------------------------------------------------------------------
+namespace {
+int check_occ_shape(int G, const char* who) {
+    if (G < 4 || G > 256 || G % 4 != 0) return fail(CNERF_EINVAL, "%s: G=%d must be a multiple of 4 in [4,256]", who, G);
+    return CNERF_OK;
+}
+int check_occ_points(int B, long long n, const char* who) {
+    if (B < 1 || B > 65535) return fail(CNERF_EINVAL, "%s: B=%d out of range [1,65535]", who, B);
+    if (n < 1 || n > 2147483647LL) return fail(CNERF_EINVAL, "%s: n_per_image=%lld out of range [1,2^31)", who, n);
+    return CNERF_OK;
+}
+int occ_grid(const cnerf_occupancy* occ, const char* who, OccGrid& g) {
+    if (!occ) return fail(CNERF_EINVAL, "%s: occupancy is NULL", who);
+    if (int rc = check_occ_shape(occ->G, who)) return rc;
+    if (!(occ->side > 0.0f) || !(occ->side < INFINITY)) return fail(CNERF_EINVAL, "%s: occupancy side=%g must be > 0 and finite", who, (double)occ->side);
+    if (!occ->bits) return fail(CNERF_EINVAL, "%s: occupancy bits is NULL", who);
+    g.bits = occ->bits;
+    g.G = occ->G;
+    for (int k = 0; k < 3; ++k) g.lo[k] = occ->lo[k];
+    g.inv = (float)occ->G / occ->side;
+    return CNERF_OK;
+}
+size_t occ_compact_bytes(int B, long long n) { return align256((size_t)B * (size_t)occ_chunks(n) * sizeof(int32_t)); }
+
+// Workspace of cnerf_render_rays_masked_forward: that of cnerf_render_rays_forward, then of the pass in flight the live positions (N, 3),
+// their values (N, 4), the ranks (N) int32, the B counts and the compaction's scratch; N = B P S
+struct MaskedLayout {
+    RaysForwardLayout F;
+    size_t live_pts, live_rs, rank, counts, compact, total;
+};
+MaskedLayout masked_layout(const cnerf_cfg* c, long long P) {
+    MaskedLayout M{};
+    M.F = rays_forward_layout(c, P);
+    const size_t N = (size_t)c->B * (size_t)P * c->S;
+    size_t off = M.F.total;
+    auto take = [&](size_t bytes) { const size_t o = off; off += align256(bytes); return o; };
+    M.live_pts = take(N * 3 * sizeof(float));
+    M.live_rs = take(N * 4 * sizeof(float));
+    M.rank = take(N * sizeof(int32_t));
+    M.counts = take((size_t)c->B * sizeof(int32_t));
+    M.compact = take(occ_compact_bytes(c->B, P * c->S));
+    M.total = off;
+    return M;
+}
+}  // namespace
+
+extern "C" {
+
+int cnerf_occupancy_build(int32_t B, int32_t G, int32_t dilate, float threshold, const float* sigma, uint32_t* bits, void* stream) {
+    g_err[0] = 0;
+    if (int rc = check_occ_shape(G, "occupancy_build")) return rc;
+    if (B < 1 || B > 65535) return fail(CNERF_EINVAL, "occupancy_build: B=%d out of range [1,65535]", B);
+    if (dilate < 0 || dilate > 4) return fail(CNERF_EINVAL, "occupancy_build: dilate=%d out of range [0,4]", dilate);
+    if (!sigma || !bits) return fail(CNERF_EINVAL, "occupancy_build: NULL argument");
+    if ((uintptr_t)bits % 8) return fail(CNERF_EINVAL, "occupancy_build: bits must be 8-byte aligned");
+    if (hipError_t e = launch_occ_build(OccBuildArgs{sigma, bits, B, G, dilate, threshold}, (hipStream_t)stream)) return hip_fail(e, "occ_build");
+    return CNERF_OK;
+}
+
+int cnerf_occupancy_compact_bytes(int32_t B, int64_t n_per_image, size_t* workspace) {
+    g_err[0] = 0;
+    if (int rc = check_occ_points(B, (long long)n_per_image, "occupancy_compact_bytes")) return rc;
+    if (workspace) *workspace = occ_compact_bytes(B, (long long)n_per_image);
+    return CNERF_OK;
+}
+
+int cnerf_occupancy_compact(const cnerf_occupancy* occ, int32_t B, int64_t n_per_image, const float* points, int32_t* rank, float* live_points,
+                            int32_t* counts, void* workspace, void* stream) {
+    g_err[0] = 0;
+    OccGrid g;
+    if (int rc = occ_grid(occ, "occupancy_compact", g)) return rc;
+    if (int rc = check_occ_points(B, (long long)n_per_image, "occupancy_compact")) return rc;
+    if (!points || !rank || !live_points || !counts || !workspace) return fail(CNERF_EINVAL, "occupancy_compact: NULL argument");
+    const OccCompactArgs a{g, points, rank, live_points, counts, (int32_t*)workspace, (long long)n_per_image, B};
+    if (hipError_t e = launch_occ_compact(a, (hipStream_t)stream)) return hip_fail(e, "occ_compact");
+    return CNERF_OK;
+}
+
+int cnerf_occupancy_expand(int32_t B, int64_t n_per_image, const int32_t* rank, const float* live_rgb_sigma, float* rgb_sigma, void* stream) {
+    g_err[0] = 0;
+    if (int rc = check_occ_points(B, (long long)n_per_image, "occupancy_expand")) return rc;
+    if (!rank || !live_rgb_sigma || !rgb_sigma) return fail(CNERF_EINVAL, "occupancy_expand: NULL argument");
+    if ((uintptr_t)live_rgb_sigma % 16 || (uintptr_t)rgb_sigma % 16) return fail(CNERF_EINVAL, "occupancy_expand: rgb_sigma buffers must be 16-byte aligned");
+    if (live_rgb_sigma == rgb_sigma) return fail(CNERF_EINVAL, "occupancy_expand: live_rgb_sigma and rgb_sigma must be distinct buffers");
+    if (hipError_t e = launch_occ_expand(OccExpandArgs{rank, live_rgb_sigma, rgb_sigma, (long long)n_per_image, B}, (hipStream_t)stream))
+        return hip_fail(e, "occ_expand");
+    return CNERF_OK;
+}
+
+int cnerf_render_rays_masked_workspace_bytes(const cnerf_cfg* cfg, int64_t rays_per_image, size_t* bytes) {
+    g_err[0] = 0;
+    if (int rc = check_rays_cfg(cfg, (long long)rays_per_image, "render_rays_masked_workspace_bytes")) return rc;
+    if (int rc = check_occ_points(cfg->B, (long long)rays_per_image * cfg->S, "render_rays_masked_workspace_bytes")) return rc;
+    if (bytes) *bytes = masked_layout(cfg, (long long)rays_per_image).total;
+    return CNERF_OK;
+}
+
+int cnerf_render_rays_masked_forward(const cnerf_cfg* cfg, const cnerf_rays* rays, int64_t rays_per_image, const cnerf_occupancy* occ,
+                                     const cnerf_volumes* vols, const float* packed, const float* freq, const float* phase, const cnerf_rng* rng,
+                                     float* pixels, float* dist, const cnerf_aux* aux, int32_t* live_counts, void* workspace, void* stream_) {
+    g_err[0] = 0;
+    const char* who = "render_rays_masked_forward";
+    const long long P = (long long)rays_per_image;
+    if (int rc = check_rays_cfg(cfg, P, who)) return rc;
+    if (int rc = check_rays(rays, who)) return rc;
+    OccGrid grid;
+    if (int rc = occ_grid(occ, who, grid)) return rc;
+    const int S = cfg->S, B = cfg->B;
+    const long long n_rays = (long long)B * P, npi = P * S;
+    if (int rc = check_occ_points(B, npi, who)) return rc;
+    if ((!vols && !no_volume(cfg)) || !packed || !pixels || !dist || !workspace) return fail(CNERF_EINVAL, "%s: NULL argument", who);
+    if (counts_of(cfg).n_film && (!freq || !phase)) return fail(CNERF_EINVAL, "%s: FiLM layers need freq and phase", who);
+    const bool hier = cfg->flags & CNERF_F_HIERARCHICAL;
+    rng = rng_or_none(rng);
+    if (hier && !rng->u_fine && !cfg->philox) return fail(CNERF_EINVAL, "%s: hierarchical sampling needs rng.u_fine (or cfg.philox)", who);
+    hipStream_t stream = (hipStream_t)stream_;
+    // the live counts come back to the host between the compaction and the field launches: not something a graph can record
+    hipStreamCaptureStatus capturing = hipStreamCaptureStatusNone;
+    if (hipError_t e = hipStreamIsCapturing(stream, &capturing)) return hip_fail(e, "hipStreamIsCapturing");
+    if (capturing != hipStreamCaptureStatusNone)
+        return fail(CNERF_EINVAL, "%s: the stream is being captured; this call copies the live counts to the host and synchronises", who);
+
+    const MaskedLayout M = masked_layout(cfg, P);
+    char* ws = (char*)workspace;
+    float* c_rs = (float*)(ws + M.F.c_rs);
+    float* f_rs = (float*)(ws + M.F.f_rs);
+    float* c_z = (float*)(ws + M.F.c_z);
+    float* f_z = (float*)(ws + M.F.f_z);
+    float* c_pts = (float*)(ws + M.F.pts);
+    float* f_pts = c_pts;
+    if (aux) {   // write straight into the caller's buffers where given
+        if (aux->coarse_rgb_sigma) c_rs = aux->coarse_rgb_sigma;
+        if (aux->fine_rgb_sigma) f_rs = aux->fine_rgb_sigma;
+        if (aux->coarse_z) c_z = aux->coarse_z;
+        if (aux->fine_z) f_z = aux->fine_z;
+        if (aux->coarse_points) c_pts = aux->coarse_points;
+        if (aux->fine_points) f_pts = aux->fine_points;
+    }
+    float* live_pts = (float*)(ws + M.live_pts);
+    float* live_rs = (float*)(ws + M.live_rs);
+    int32_t* rank = (int32_t*)(ws + M.rank);
+    int32_t* counts = (int32_t*)(ws + M.counts);
+    // every refusal of the field passes before the first launch (the arguments of image 0 stand for all)
+    FieldArgs fa;
+    if (int rc = points_args(fa, cfg, vols, nullptr, packed, freq, phase, live_pts, 0, 1, npi, nullptr)) return rc;
+    int32_t* own_counts = live_counts ? nullptr : (int32_t*)malloc((size_t)B * sizeof(int32_t));
+    if (!live_counts && !own_counts) return fail(CNERF_EINVAL, "%s: out of host memory", who);
+
+    // one field pass on the live points of `pts`: compact, counts to the host, the field per image, expand into rs
+    auto field_pass = [&](const float* pts, float* rs, int32_t* host_counts, const char* what) -> int {
+        const OccCompactArgs ca{grid, pts, rank, live_pts, counts, (int32_t*)(ws + M.compact), npi, B};
+        if (hipError_t e = launch_occ_compact(ca, stream)) return hip_fail(e, "occ_compact");
+        if (hipError_t e = hipMemcpyAsync(host_counts, counts, (size_t)B * sizeof(int32_t), hipMemcpyDeviceToHost, stream)) return hip_fail(e, "live counts");
+        if (hipError_t e = hipStreamSynchronize(stream)) return hip_fail(e, "live counts");
+        for (int b = 0; b < B; ++b) {
+            if (host_counts[b] <= 0) continue;
+            if (int rc = points_args(fa, cfg, vols, nullptr, packed, freq, phase, live_pts + (size_t)b * npi * 3, b, 1, host_counts[b], nullptr)) return rc;
+            fa.rgb_sigma = live_rs + (size_t)b * npi * 4;
+            if (hipError_t e = launch_forward(fa, cfg, stream)) return hip_fail(e, what);
+        }
+        if (hipError_t e = launch_occ_expand(OccExpandArgs{rank, live_rs, rs, npi, B}, stream)) return hip_fail(e, "occ_expand");
+        return CNERF_OK;
+    };
+    auto run = [&]() -> int {
+        int32_t* hc = live_counts ? live_counts : own_counts;
+        // 1. coarse pass: stratified depths and positions, the field on the live ones
+        RaySampleArgs sa{rays->origins, rays->dirs, nullptr, rng->u_strat, c_z, c_pts, n_rays, S, cfg->ray_start, cfg->ray_end, philox_of(cfg)};
+        if (hipError_t e = launch_ray_sample(sa, stream)) return hip_fail(e, "ray_sample (coarse)");
+        if (int rc = field_pass(c_pts, c_rs, hc, "field kernel (coarse)")) return rc;
+        if (hier) {
+            // 2. coarse weights -> inverse-CDF depths
+            ResampleArgs ra{c_z, nullptr, c_rs, rng->eps_coarse, rng->u_fine, f_z, aux ? aux->inds : nullptr, aux ? aux->cdf : nullptr,
+                            aux ? aux->coarse_weights : nullptr, n_rays, S, cfg->noise_std, cfg->flags, philox_of(cfg)};
+            if (hipError_t e = launch_resample(ra, stream)) return hip_fail(e, "resample");
+            // 3. fine pass
+            if (rng->fine_z) f_z = const_cast<float*>(rng->fine_z);   // teacher-forced depths (read only from here on)
+            sa.z = f_z;
+            sa.u_strat = nullptr;
+            sa.z_out = nullptr;
+            sa.points = f_pts;
+            if (hipError_t e = launch_ray_sample(sa, stream)) return hip_fail(e, "ray_sample (fine)");
+            if (int rc = field_pass(f_pts, f_rs, live_counts ? live_counts + B : own_counts, "field kernel (fine)")) return rc;
+        }
+        // 4. merge + composite, outputs per ray
+        MergeArgs ma{c_rs, c_z, hier ? f_rs : nullptr, hier ? f_z : nullptr, rng->eps_final, pixels, dist, aux ? aux->sort_idx : nullptr,
+                     aux ? aux->final_weights : nullptr, n_rays, S, RayGeom{}, cfg->noise_std, cfg->flags, philox_of(cfg), 1};
+        if (hipError_t e = launch_merge_composite(ma, stream)) return hip_fail(e, "merge_composite");
+        return CNERF_OK;
+    };
+    const int rc = run();
+    free(own_counts);
+    return rc;
 }
 
 }  // extern "C"

@@ -242,6 +242,42 @@ struct RayGradArgs {         // grad_origins (rays,3) += sum_s g, grad_dirs (ray
 };
 hipError_t launch_ray_grad_reduce(const RayGradArgs& a, hipStream_t stream);
 
+// occupancy.hip: occupancy bits from corner densities, the stable compaction of the live points of every image, the expansion of their values
+struct OccGrid {             // cnerf_occupancy on the device side
+    const uint32_t* bits;    // (B, G^3 / 32): bit (ix G + iy) G + iz of an image in word idx >> 5, bit idx & 31
+    int G;
+    float lo[3];
+    float inv;               // (float)G / side, rounded once on the host
+};
+struct OccBuildArgs {
+    const float* sigma;      // (B, (G+1)^3) densities at the cell corners, index (ix (G+1) + iy) (G+1) + iz
+    uint32_t* bits;          // (B, G^3 / 32)
+    int B, G, dilate;
+    float threshold;
+};
+constexpr int OCC_CHUNK = 2048;      // points of an image one block counts and ranks (8 rounds of 256)
+inline long long occ_chunks(long long n) { return (n + OCC_CHUNK - 1) / OCC_CHUNK; }
+struct OccCompactArgs {
+    OccGrid grid;
+    const float* points;     // (B,n,3)
+    int32_t* rank;           // (B,n): index among the image's live points in ascending order, -1 = skipped
+    float* live_points;      // (B,n,3): the live positions of image b packed at the front of its n rows
+    int32_t* counts;         // (B) live points per image
+    int32_t* block_counts;   // (B, occ_chunks(n)) scratch: live points per chunk, then their exclusive offsets
+    long long n;
+    int B;
+};
+struct OccExpandArgs {
+    const int32_t* rank;            // (B,n)
+    const float* live_rgb_sigma;    // (B,n,4): image b's values at the front of its n rows
+    float* rgb_sigma;               // (B,n,4)
+    long long n;
+    int B;
+};
+hipError_t launch_occ_build(const OccBuildArgs& a, hipStream_t stream);
+hipError_t launch_occ_compact(const OccCompactArgs& a, hipStream_t stream);
+hipError_t launch_occ_expand(const OccExpandArgs& a, hipStream_t stream);
+
 hipError_t launch_philox_fill(const PhiloxKey& k, uint32_t stream_id, long long n, int normal, float* out, hipStream_t stream);
 hipError_t launch_transpose_cl(int B, int C, int V, const float* src, float* dst, bool to_channel_last, hipStream_t stream);
 

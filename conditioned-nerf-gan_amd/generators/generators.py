@@ -11,6 +11,8 @@ import torch.nn as nn
 from . import siren
 from .. import ops
 
+OccupancyGrid = ops.OccupancyGrid      # what build_occupancy returns
+
 
 def draw_rng(B, P, S, hierarchical, noise_std, dev):
     """The random tensors of one forward, drawn with the reference's shapes and in its order (rand (B,P,S,1),
@@ -112,11 +114,23 @@ class ImplicitGenerator3d(nn.Module):
         "philox" draws in the kernels.  Differentiable w.r.t. everything `forward` is, and w.r.t. origins and dirs (the sample
         depths carry no gradient, as in the reference).  Dropout is not implemented here: a training-mode network with
         drop_out > 0 raises NotImplementedError.
+        occupancy=grid (an OccupancyGrid of build_occupancy, one grid per image): samples in cells whose bit is clear are not given to
+        the field network -- forward only: raises when grad mode is on and any of z, the parameters, origins or dirs requires grad, and
+        when the grid's batch is not B; `_aux` then also receives live_coarse / live_fine, (B,) int32: the points each pass evaluated.
+        Without the key the call is what it was.
         Returns pixels (B,P,3) = 2*rgb-1 and dist (B,P) = sum of weight * depth along the ray."""
         net = self.siren
         net.check_supported()
         if net.drop_out and net.training:
             raise NotImplementedError("render_rays has no dropout: call eval() first, or use forward, the path that has dropout")
+        occupancy = kwargs.get("occupancy")
+        if occupancy is not None:
+            fv, gl = net.split_z(z)
+            zs = [t for t in (*ops.as_levels(fv), gl) if torch.is_tensor(t)]
+            if torch.is_grad_enabled() and any(t.requires_grad for t in (*zs, *self.parameters(), origins, dirs)):
+                raise RuntimeError("render_rays(occupancy=...) is forward only: call it under torch.no_grad()")
+            if occupancy.bits.shape[0] != origins.shape[0]:
+                raise ValueError(f"occupancy holds {occupancy.bits.shape[0]} grids, the call renders {origins.shape[0]} images")
         clamp_mode, noise_std = kwargs["clamp_mode"], kwargs["nerf_noise"]
         white_back, last_back = kwargs.get("white_back", False), kwargs.get("last_back", False)
         fvol, glob = net.split_z(z)
@@ -127,10 +141,36 @@ class ImplicitGenerator3d(nn.Module):
             rng = {"philox": self._philox_key()} if self.rng_mode == "philox" else draw_rng(B, P, S, bool(hierarchical_sample), noise_std, origins.device)
         aux_out = kwargs.get("_aux")
         pixels, dist, aux = ops.render_rays(net, fvol, freq, phase, origins, dirs, ray_start, ray_end, S, bool(hierarchical_sample), clamp_mode,
-                                            noise_std, white_back, last_back, rng, want_aux=aux_out is not None)
+                                            noise_std, white_back, last_back, rng, want_aux=aux_out is not None,
+                                            **({} if occupancy is None else {"occupancy": occupancy}))
         if aux_out is not None:
             aux_out.update(aux)
         return pixels, dist
+
+    def build_occupancy(self, z, lo, side, resolution=64, threshold=0.0, dilate=1, max_points=1 << 22):
+        """Occupancy grids of the scenes z for render_rays(..., occupancy=grid): build once, render many cameras.  The density is queried
+        at the (G+1)^3 corners lo + i (side / G), G = resolution (a multiple of 4 in [4,256]), of the cube with corner lo (3 floats) and
+        edge side -- self.siren(points, z) under no_grad, max_points per image at a time -- and cnerf_occupancy_build sets the bit of every
+        cell whose corners, or those of a cell within `dilate` of it, exceed `threshold` (include/cnerf.h has the exact rule).  Density
+        between the corners is not seen: choose the resolution for the field's detail, and dilate.
+        Returns OccupancyGrid(bits (B, G^3 / 32) int32, lo, side, G)."""
+        net = self.siren
+        G = int(resolution)
+        if G % 4 or not 4 <= G <= 256:
+            raise ValueError(f"resolution={G} must be a multiple of 4 in [4,256]")
+        lo = tuple(float(v) for v in lo)
+        with torch.no_grad():
+            fvol, glob = net.split_z(z)
+            ref = glob if glob is not None else ops.as_levels(fvol)[0]
+            B, dev = ref.shape[0], ref.device
+            i = torch.arange(G + 1, device=dev, dtype=torch.float32)
+            step = torch.tensor(float(side), device=dev, dtype=torch.float32) / G
+            ax = [torch.tensor(v, device=dev, dtype=torch.float32) + i * step for v in lo]
+            pts = torch.stack(torch.meshgrid(*ax, indexing="ij"), -1).reshape(1, -1, 3)
+            chunk = max(1, int(max_points))
+            sigma = torch.cat([net(pts[:, p0:p0 + chunk].expand(B, -1, -1).contiguous(), z)[..., 3] for p0 in range(0, pts.shape[1], chunk)], 1)
+            bits = ops.occupancy_build(sigma, G, threshold, dilate)
+        return ops.OccupancyGrid(bits, lo, float(side), G)
 
     def generate_avg_frequencies(self):
         """Mean FiLM frequencies / phase shifts over 10000 random latents (generators.py:189-197)."""

@@ -3,7 +3,7 @@ stream and autograd plumbing here; every computation below happens in libcnerf_h
 import ctypes as C
 import weakref
 from types import SimpleNamespace
-from typing import Optional
+from typing import NamedTuple, Optional
 
 import torch
 import torch.nn.functional as F
@@ -676,8 +676,74 @@ def _rays_cfg(net, o, levels, precision=None, rng=None):
                     o["clamp_mode"], precision=precision, philox=(rng or {}).get("philox"))
 
 
-def render_rays_forward(net, levels, freq, phase, origins, dirs, o, rng=None, want_aux=False, aux_keys=None):
-    """cnerf_render_rays_forward on channel-last levels: origins / dirs (B,P,3) -> pixels (B,P,3), dist (B,P), aux dict."""
+class OccupancyGrid(NamedTuple):
+    """One occupancy grid per image: bits (B, G^3 / 32) int32 on the device -- bit (ix G + iy) G + iz of an image in word idx >> 5, bit
+    idx & 31 -- over the axis-aligned cube with corner lo (3 floats) and edge side.  include/cnerf.h states what a set bit means."""
+    bits: torch.Tensor
+    lo: tuple
+    side: float
+    G: int
+
+
+def _occ_struct(grid, B):
+    bits = grid.bits
+    G = int(grid.G)
+    if bits.dtype != torch.int32 or bits.dim() != 2 or bits.shape[0] != B or bits.shape[1] * 32 != G ** 3:
+        raise L.CnerfError(f"occupancy bits must be int32 (B={B}, G^3/32={G ** 3 // 32}), got {bits.dtype} {tuple(bits.shape)}")
+    oc = L.Occupancy()
+    oc.bits, oc.G, oc.side = L.ptr(bits).value, G, float(grid.side)
+    oc.lo[0], oc.lo[1], oc.lo[2] = (float(v) for v in grid.lo)
+    return oc
+
+
+def occupancy_build(sigma, G, threshold=0.0, dilate=1):
+    """cnerf_occupancy_build: sigma (B, (G+1)^3), the density at the cell corners (index (ix (G+1) + iy) (G+1) + iz) -> bits (B, G^3 / 32)
+    int32.  A cell's bit is set iff the maximum over the corners of the cells within `dilate` of it is not <= threshold (a NaN sets it)."""
+    sigma = _f32(sigma)
+    G = int(G)
+    if sigma.dim() != 2 or sigma.shape[1] != (G + 1) ** 3:
+        raise L.CnerfError(f"occupancy_build: sigma must be (B, (G+1)^3 = {(G + 1) ** 3}), got {tuple(sigma.shape)}")
+    B = sigma.shape[0]
+    bits = torch.empty((B, max(G, 0) ** 3 // 32), dtype=torch.int32, device=sigma.device)
+    L.check(L.lib().cnerf_occupancy_build(B, G, int(dilate), float(threshold), L.ptr(sigma), C.c_void_p(bits.data_ptr()), _stream()),
+            "cnerf_occupancy_build")
+    return bits
+
+
+def occupancy_compact(grid, points, rank=None, live_points=None):
+    """cnerf_occupancy_compact: points (B,n,3) -> rank (B,n) int32 (index among the image's live points, -1 = skipped), live_points
+    (B,n,3) with image b's live positions at the front of its rows, counts (B) int32 on the device.  rank / live_points: buffers to
+    write into (the rows of live_points behind counts[b] are left as they are)."""
+    points = _f32(points)
+    B, n = points.shape[0], points.shape[1]
+    dev = points.device
+    oc = _occ_struct(grid, B)
+    nb = C.c_size_t(0)
+    L.check(L.lib().cnerf_occupancy_compact_bytes(B, n, C.byref(nb)), "cnerf_occupancy_compact_bytes")
+    ws = torch.empty(nb.value, dtype=torch.uint8, device=dev)
+    rank = torch.empty((B, n), dtype=torch.int32, device=dev) if rank is None else rank
+    live_points = torch.empty((B, n, 3), dtype=torch.float32, device=dev) if live_points is None else live_points
+    counts = torch.empty((B,), dtype=torch.int32, device=dev)
+    L.check(L.lib().cnerf_occupancy_compact(C.byref(oc), B, n, L.ptr(points), L.ptr(rank), L.ptr(live_points), L.ptr(counts), L.ptr(ws), _stream()),
+            "cnerf_occupancy_compact")
+    return rank, live_points, counts
+
+
+def occupancy_expand(rank, live_rgb_sigma, out=None):
+    """cnerf_occupancy_expand: rank (B,n) int32, live_rgb_sigma (B,n,4) -> rgb_sigma (B,n,4): the live values at their samples,
+    (0, 0, 0, -inf) where the sample was skipped."""
+    live_rgb_sigma = _f32(live_rgb_sigma)
+    B, n = rank.shape
+    out = torch.empty((B, n, 4), dtype=torch.float32, device=rank.device) if out is None else out
+    L.check(L.lib().cnerf_occupancy_expand(B, n, L.ptr(rank), L.ptr(live_rgb_sigma), L.ptr(out), _stream()), "cnerf_occupancy_expand")
+    return out
+
+
+def render_rays_forward(net, levels, freq, phase, origins, dirs, o, rng=None, want_aux=False, aux_keys=None, occupancy=None):
+    """cnerf_render_rays_forward on channel-last levels: origins / dirs (B,P,3) -> pixels (B,P,3), dist (B,P), aux dict.
+    occupancy (an OccupancyGrid with one grid per image): cnerf_render_rays_masked_forward instead -- samples in cells whose bit is
+    clear are not evaluated; forward only; the call synchronises the stream.  aux then also holds live_coarse / live_fine, (B,) int32
+    on the host: the points each pass gave to the field."""
     origins, dirs = _f32(origins), _f32(dirs)
     if origins.dim() != 3 or origins.shape[-1] != 3 or dirs.shape != origins.shape:
         raise L.CnerfError(f"render_rays: origins and dirs must both be (B,P,3), got {tuple(origins.shape)} and {tuple(dirs.shape)}")
@@ -687,7 +753,8 @@ def render_rays_forward(net, levels, freq, phase, origins, dirs, o, rng=None, wa
     cfg = _rays_cfg(net, o, levels, rng=rng)
     packed = pack_field(net, cfg)
     nb = C.c_size_t(0)
-    L.check(L.lib().cnerf_render_rays_workspace_bytes(C.byref(cfg), P, C.byref(nb)), "cnerf_render_rays_workspace_bytes")
+    ws_entry = "cnerf_render_rays_workspace_bytes" if occupancy is None else "cnerf_render_rays_masked_workspace_bytes"
+    L.check(getattr(L.lib(), ws_entry)(C.byref(cfg), P, C.byref(nb)), ws_entry)
     ws = torch.empty(nb.value, dtype=torch.uint8, device=dev)
     pixels = torch.empty((B, P, 3), dtype=torch.float32, device=dev)
     dist = torch.empty((B, P), dtype=torch.float32, device=dev)
@@ -702,6 +769,18 @@ def render_rays_forward(net, levels, freq, phase, origins, dirs, o, rng=None, wa
             aux_t[k] = torch.empty(shape, dtype=dt, device=dev)
             setattr(aux_s, k, aux_t[k].data_ptr())
     vs, rs = volumes_struct(levels), _rays_struct(origins, dirs)
+    if occupancy is not None:
+        oc = _occ_struct(occupancy, B)
+        live = (C.c_int32 * (2 * B))()
+        L.check(L.lib().cnerf_render_rays_masked_forward(C.byref(cfg), C.byref(rs), P, C.byref(oc), C.byref(vs), L.ptr(packed), L.ptr(_f32(freq)),
+                                                         L.ptr(_f32(phase)), C.byref(r), L.ptr(pixels), L.ptr(dist),
+                                                         C.byref(aux_s) if aux_s is not None else None, live, L.ptr(ws), _stream()),
+                "cnerf_render_rays_masked_forward")
+        if want_aux or aux_keys:
+            aux_t["live_coarse"] = torch.tensor(live[:B], dtype=torch.int32)
+            if hier:
+                aux_t["live_fine"] = torch.tensor(live[B:], dtype=torch.int32)
+        return pixels, dist, aux_t
     L.check(L.lib().cnerf_render_rays_forward(C.byref(cfg), C.byref(rs), P, C.byref(vs), L.ptr(packed), L.ptr(_f32(freq)), L.ptr(_f32(phase)), C.byref(r),
                                               L.ptr(pixels), L.ptr(dist), C.byref(aux_s) if aux_s is not None else None, L.ptr(ws), _stream()),
             "cnerf_render_rays_forward")
@@ -780,9 +859,10 @@ class RenderRaysFunction(torch.autograd.Function):
 
 
 def render_rays(net, fvol, freq, phase, origins, dirs, ray_start, ray_end, num_steps, hierarchical, clamp_mode, noise_std,
-                white_back=False, last_back=False, rng=None, want_aux=False):
+                white_back=False, last_back=False, rng=None, want_aux=False, occupancy=None):
     """Differentiable render of caller-given rays, used by ImplicitGenerator3d.render_rays.  origins / dirs (B,P,3) world (dirs are not
     normalised here: depths are in units of |dir|); fvol: (B,C,V,V,V) or a list of pyramid levels.
+    occupancy (OccupancyGrid): the masked render -- forward only, no autograd node; refuses inputs that require grad in grad mode.
     Returns (pixels (B,P,3) = 2*rgb-1, dist (B,P) = distance along the ray, aux dict)."""
     o = dict(B=int(origins.shape[0]), S=int(num_steps), ray_start=float(ray_start), ray_end=float(ray_end), hier=bool(hierarchical),
              clamp_mode=clamp_mode, noise_std=float(noise_std), white_back=bool(white_back), last_back=bool(last_back), want_aux=bool(want_aux))
@@ -790,5 +870,12 @@ def render_rays(net, fvol, freq, phase, origins, dirs, ray_start, ray_end, num_s
     vols = as_levels(fvol)
     params = net.field_params()
     o["need_grad"] = torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (origins, dirs, freq, phase, *vols, *params))
+    if occupancy is not None:
+        if o["need_grad"]:
+            raise L.CnerfError("render_rays with an occupancy grid is forward only: call it under torch.no_grad()")
+        det = lambda t: None if t is None else _f32(t.detach())
+        with torch.no_grad():
+            return render_rays_forward(net, [channel_last(v.detach()) for v in vols], det(freq), det(phase), det(origins), det(dirs), o, rng or {},
+                                       want_aux=want_aux, occupancy=occupancy)
     pixels, dist = RenderRaysFunction.apply(net, o, rng or {}, origins, dirs, freq, phase, len(vols), *vols, *params)
     return pixels, dist, (RenderRaysFunction.last_aux if want_aux else {})

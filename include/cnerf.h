@@ -526,6 +526,59 @@ int cnerf_render_rays_backward(const cnerf_cfg* cfg, int32_t backward_precision,
                                const cnerf_grad_volumes* grad_vols, float* grad_origins /* (B,P,3) or NULL */,
                                float* grad_dirs /* (B,P,3) or NULL */, uint32_t* saturated, void* workspace, void* stream);
 
+/* ---- occupancy grids: forward-only ray renders that skip empty space (added in ABI v10 without a version change: no struct changed) ----
+ * An inference job renders one conditioned scene from many cameras (the reference's render_video, render_pcl and
+ * _inference_fixed_camera loops), and most samples of a ray fall where the field has no density.  An occupancy grid marks the cells of a
+ * cube that can hold density; a sample in a cell that cannot is not given to the field network.  The reference has no such stage.
+ *
+ * A grid belongs to ONE image of the call: G^3 bits (G a multiple of 4 in [4,256]) over the axis-aligned cube with corner lo[3] and edge
+ * `side`; bit index (ix G + iy) G + iz in word idx >> 5, bit idx & 31, where (x, y, z) are columns 0, 1, 2 of a point.  Cell coordinate
+ * per axis, in fp32 with every operation rounded on its own:  inv = (float)G / side (once, on the host), t = (p - lo) * inv; the point is
+ * INSIDE iff 0 <= t < G on all three axes (a NaN is not inside), and then its cell is floor(t).  A point is LIVE iff it is not inside or
+ * its cell's bit is set: outside the cube nothing is skipped, so choose a cube that covers the rays.  A point that is not live is not
+ * evaluated; its rgb_sigma is (0, 0, 0, -inf), which both clamp modes turn into density 0 (with noise_std != 0 as well: -inf + noise is
+ * -inf).  Live points go through the kernels of cnerf_field_forward and get bit for bit the values of an unmasked call at the same precision.
+ *
+ *   cnerf_occupancy_build    sigma (B, (G+1)^3): the density at the cell corners, index (ix (G+1) + iy) (G+1) + iz.  m of a cell = maximum
+ *                            over its 8 corners; m' = maximum of m over the cells within `dilate` (0..4) of it on every axis, clipped at the
+ *                            grid; the bit is set iff !(m' <= threshold).  The maxima keep a NaN, so a NaN corner sets its bits.
+ *                            bits (B, G^3 / 32), 8-byte aligned, every word written.
+ *   cnerf_occupancy_compact  points (B,n,3), n < 2^31 -> rank (B,n) int32: the point's index among its image's live points in ascending
+ *                            order, -1 if it is skipped; live_points (B,n,3): image b's live positions packed at the front of its n rows
+ *                            (the rows behind counts[b] are not written); counts (B) DEVICE int32.  Stable and deterministic: ballots and
+ *                            scans, no atomics.  workspace: cnerf_occupancy_compact_bytes.
+ *   cnerf_occupancy_expand   rgb_sigma[b,i] = rank[b,i] >= 0 ? live_rgb_sigma[b, rank[b,i]] : (0, 0, 0, -inf); both (B,n,4), 16-byte aligned,
+ *                            distinct buffers.
+ * All three are asynchronous on `stream` and allocate nothing.
+ *
+ *   cnerf_render_rays_masked_forward   cnerf_render_rays_forward with each field pass replaced by: compact, copy the B counts to the host
+ *                            and SYNCHRONISE THE STREAM (so: twice per hierarchical call, once otherwise -- unlike every other entry this one
+ *                            blocks the calling thread, and it refuses a stream that is being captured), one field launch per image on
+ *                            counts[b] points (none when the count is 0), expand.  Resampling, merge and compositing run as they are.
+ *                            occ->bits holds one grid per image of the call.  aux pointers mean what they mean in cnerf_render_rays_forward
+ *                            (coarse / fine rgb_sigma: the expanded tensors).  live_counts: HOST int32 (2,B) or NULL -- row 0 the coarse,
+ *                            row 1 the fine pass (row 1 is not written when not hierarchical).  No backward, no dropout.
+ *                            CNERF_EINVAL before any launch: what cnerf_render_rays_forward refuses (drop_p > 0 among it), occ NULL, G not
+ *                            a multiple of 4 in [4,256], side <= 0, bits NULL, a capturing stream.
+ *                            workspace: cnerf_render_rays_masked_workspace_bytes. */
+typedef struct cnerf_occupancy {     /* HOST struct */
+    const uint32_t* bits;            /* (B, G*G*G/32) device */
+    int32_t G;
+    float lo[3];
+    float side;
+} cnerf_occupancy;
+
+int cnerf_occupancy_build(int32_t B, int32_t G, int32_t dilate, float threshold, const float* sigma, uint32_t* bits, void* stream);
+int cnerf_occupancy_compact_bytes(int32_t B, int64_t n_per_image, size_t* workspace);
+int cnerf_occupancy_compact(const cnerf_occupancy* occ, int32_t B, int64_t n_per_image, const float* points, int32_t* rank,
+                            float* live_points, int32_t* counts /* (B) device */, void* workspace, void* stream);
+int cnerf_occupancy_expand(int32_t B, int64_t n_per_image, const int32_t* rank, const float* live_rgb_sigma, float* rgb_sigma, void* stream);
+int cnerf_render_rays_masked_workspace_bytes(const cnerf_cfg* cfg, int64_t rays_per_image, size_t* bytes);
+int cnerf_render_rays_masked_forward(const cnerf_cfg* cfg, const cnerf_rays* rays, int64_t rays_per_image, const cnerf_occupancy* occ,
+                                     const cnerf_volumes* vols, const float* packed, const float* freq, const float* phase,
+                                     const cnerf_rng* rng, float* pixels /* (B,P,3) */, float* dist /* (B,P) */, const cnerf_aux* aux,
+                                     int32_t* live_counts /* HOST int32 (2,B) or NULL */, void* workspace, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
