@@ -56,6 +56,11 @@ class Occupancy(C.Structure):
     _fields_ = [("bits", C.c_void_p), ("G", C.c_int32), ("lo", C.c_float * 3), ("side", C.c_float)]
 
 
+class RayBounds(C.Structure):
+    """cnerf_ray_bounds: per-ray interval of the coarse depths, (B,P) float32 each on the device; both NULL: the scalars of the cfg."""
+    _fields_ = [("near", C.c_void_p), ("far", C.c_void_p)]
+
+
 class Rng(C.Structure):
     _fields_ = [("u_strat", C.c_void_p), ("eps_coarse", C.c_void_p), ("u_fine", C.c_void_p), ("eps_final", C.c_void_p),
                 ("fine_z", C.c_void_p), ("drop_coarse", C.c_void_p), ("drop_fine", C.c_void_p)]
@@ -134,6 +139,13 @@ PROTOTYPES = {
     "cnerf_render_rays_masked_forward": (C.c_int, [C.POINTER(Cfg), C.POINTER(Rays), C.c_int64, C.POINTER(Occupancy), C.POINTER(Volumes), C.c_void_p,
                                                    C.c_void_p, C.c_void_p, C.POINTER(Rng), C.c_void_p, C.c_void_p, C.POINTER(Aux),
                                                    C.POINTER(C.c_int32), C.c_void_p, C.c_void_p]),
+    "cnerf_occupancy_ray_bounds": (C.c_int, [C.POINTER(Occupancy), C.POINTER(Rays), C.c_int32, C.c_int64, C.c_float, C.c_float, C.c_float, C.c_void_p,
+                                             C.c_void_p, C.c_void_p, C.c_void_p]),
+    "cnerf_render_rays_bounded_forward": (C.c_int, [C.POINTER(Cfg), C.POINTER(Rays), C.c_int64, C.POINTER(RayBounds), C.POINTER(Volumes), C.c_void_p,
+                                                    C.c_void_p, C.c_void_p, C.POINTER(Rng), C.c_void_p, C.c_void_p, C.POINTER(Aux), C.c_void_p, C.c_void_p]),
+    "cnerf_render_rays_bounded_masked_forward": (C.c_int, [C.POINTER(Cfg), C.POINTER(Rays), C.c_int64, C.POINTER(RayBounds), C.POINTER(Occupancy),
+                                                           C.POINTER(Volumes), C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(Rng), C.c_void_p, C.c_void_p,
+                                                           C.POINTER(Aux), C.POINTER(C.c_int32), C.c_void_p, C.c_void_p]),
 }
 
 _lib = None

@@ -1643,6 +1643,13 @@ int check_rays(const cnerf_rays* r, const char* who) {
     if (!r->origins || !r->dirs) return fail(CNERF_EINVAL, "%s: rays.origins / rays.dirs is NULL", who);
     return CNERF_OK;
 }
+// per-ray sampling interval of the coarse pass: both arrays, or neither (a NULL struct or NULL members: the scalars of cfg)
+int ray_bounds_of(const cnerf_ray_bounds* b, const char* who, const float*& near, const float*& far) {
+    near = b ? b->near : nullptr;
+    far = b ? b->far : nullptr;
+    if (!near != !far) return fail(CNERF_EINVAL, "%s: bounds.near and bounds.far must both be given, or both be NULL", who);
+    return CNERF_OK;
+}
 // Workspace of cnerf_render_rays_forward (every piece 256-byte aligned): the coarse and fine rgb_sigma (N, 4) and z (N), the sample
 // positions of the pass in flight (N, 3); N = B P S
 struct RaysForwardLayout {
@@ -1689,18 +1696,21 @@ int cnerf_render_rays_workspace_bytes(const cnerf_cfg* cfg, int64_t rays_per_ima
     return CNERF_OK;
 }
 
-int cnerf_render_rays_forward(const cnerf_cfg* cfg, const cnerf_rays* rays, int64_t rays_per_image, const cnerf_volumes* vols, const float* packed,
-                              const float* freq, const float* phase, const cnerf_rng* rng, float* pixels, float* dist, const cnerf_aux* aux,
-                              void* workspace, void* stream_) {
+// cnerf_render_rays_forward and cnerf_render_rays_bounded_forward (bounds == NULL: the scalars of cfg)
+static int render_rays_forward_impl(const char* who, const cnerf_cfg* cfg, const cnerf_rays* rays, int64_t rays_per_image, const cnerf_ray_bounds* bounds,
+                                    const cnerf_volumes* vols, const float* packed, const float* freq, const float* phase, const cnerf_rng* rng,
+                                    float* pixels, float* dist, const cnerf_aux* aux, void* workspace, void* stream_) {
     g_err[0] = 0;
     const long long P = (long long)rays_per_image;
-    if (int rc = check_rays_cfg(cfg, P, "render_rays_forward")) return rc;
-    if (int rc = check_rays(rays, "render_rays_forward")) return rc;
-    if ((!vols && !no_volume(cfg)) || !packed || !pixels || !dist || !workspace) return fail(CNERF_EINVAL, "render_rays_forward: NULL argument");
-    if (counts_of(cfg).n_film && (!freq || !phase)) return fail(CNERF_EINVAL, "render_rays_forward: FiLM layers need freq and phase");
+    if (int rc = check_rays_cfg(cfg, P, who)) return rc;
+    if (int rc = check_rays(rays, who)) return rc;
+    const float *near, *far;
+    if (int rc = ray_bounds_of(bounds, who, near, far)) return rc;
+    if ((!vols && !no_volume(cfg)) || !packed || !pixels || !dist || !workspace) return fail(CNERF_EINVAL, "%s: NULL argument", who);
+    if (counts_of(cfg).n_film && (!freq || !phase)) return fail(CNERF_EINVAL, "%s: FiLM layers need freq and phase", who);
     const bool hier = cfg->flags & CNERF_F_HIERARCHICAL;
     rng = rng_or_none(rng);
-    if (hier && !rng->u_fine && !cfg->philox) return fail(CNERF_EINVAL, "render_rays_forward: hierarchical sampling needs rng.u_fine (or cfg.philox)");
+    if (hier && !rng->u_fine && !cfg->philox) return fail(CNERF_EINVAL, "%s: hierarchical sampling needs rng.u_fine (or cfg.philox)", who);
     hipStream_t stream = (hipStream_t)stream_;
 
     const int S = cfg->S;
@@ -1726,7 +1736,7 @@ int cnerf_render_rays_forward(const cnerf_cfg* cfg, const cnerf_rays* rays, int6
     if (int rc = points_args(fa, cfg, vols, nullptr, packed, freq, phase, c_pts, 0, cfg->B, npi, nullptr)) return rc;
 
     // 1. coarse pass: stratified depths and positions, the field
-    RaySampleArgs sa{rays->origins, rays->dirs, nullptr, rng->u_strat, c_z, c_pts, n_rays, S, cfg->ray_start, cfg->ray_end, philox_of(cfg)};
+    RaySampleArgs sa{rays->origins, rays->dirs, nullptr, rng->u_strat, c_z, c_pts, n_rays, S, cfg->ray_start, cfg->ray_end, philox_of(cfg), near, far};
     if (hipError_t e = launch_ray_sample(sa, stream)) return hip_fail(e, "ray_sample (coarse)");
     fa.rgb_sigma = c_rs;
     if (hipError_t e = launch_forward(fa, cfg, stream)) return hip_fail(e, "field kernel (coarse)");
@@ -1751,6 +1761,20 @@ int cnerf_render_rays_forward(const cnerf_cfg* cfg, const cnerf_rays* rays, int6
                  aux ? aux->final_weights : nullptr, n_rays, S, RayGeom{}, cfg->noise_std, cfg->flags, philox_of(cfg), 1};
     if (hipError_t e = launch_merge_composite(ma, stream)) return hip_fail(e, "merge_composite");
     return CNERF_OK;
+}
+
+int cnerf_render_rays_forward(const cnerf_cfg* cfg, const cnerf_rays* rays, int64_t rays_per_image, const cnerf_volumes* vols, const float* packed,
+                              const float* freq, const float* phase, const cnerf_rng* rng, float* pixels, float* dist, const cnerf_aux* aux,
+                              void* workspace, void* stream) {
+    return render_rays_forward_impl("render_rays_forward", cfg, rays, rays_per_image, nullptr, vols, packed, freq, phase, rng, pixels, dist, aux, workspace,
+                                    stream);
+}
+
+int cnerf_render_rays_bounded_forward(const cnerf_cfg* cfg, const cnerf_rays* rays, int64_t rays_per_image, const cnerf_ray_bounds* bounds,
+                                      const cnerf_volumes* vols, const float* packed, const float* freq, const float* phase, const cnerf_rng* rng,
+                                      float* pixels, float* dist, const cnerf_aux* aux, void* workspace, void* stream) {
+    return render_rays_forward_impl("render_rays_bounded_forward", cfg, rays, rays_per_image, bounds, vols, packed, freq, phase, rng, pixels, dist, aux,
+                                    workspace, stream);
 }
 
 int cnerf_render_rays_backward_workspace_bytes(const cnerf_cfg* cfg, int32_t backward_precision, int64_t rays_per_image, int64_t points_per_chunk,
@@ -1919,14 +1943,17 @@ int cnerf_render_rays_masked_workspace_bytes(const cnerf_cfg* cfg, int64_t rays_
     return CNERF_OK;
 }
 
-int cnerf_render_rays_masked_forward(const cnerf_cfg* cfg, const cnerf_rays* rays, int64_t rays_per_image, const cnerf_occupancy* occ,
-                                     const cnerf_volumes* vols, const float* packed, const float* freq, const float* phase, const cnerf_rng* rng,
-                                     float* pixels, float* dist, const cnerf_aux* aux, int32_t* live_counts, void* workspace, void* stream_) {
+// cnerf_render_rays_masked_forward and cnerf_render_rays_bounded_masked_forward (bounds == NULL: the scalars of cfg)
+static int render_rays_masked_forward_impl(const char* who, const cnerf_cfg* cfg, const cnerf_rays* rays, int64_t rays_per_image,
+                                           const cnerf_ray_bounds* bounds, const cnerf_occupancy* occ, const cnerf_volumes* vols, const float* packed,
+                                           const float* freq, const float* phase, const cnerf_rng* rng, float* pixels, float* dist, const cnerf_aux* aux,
+                                           int32_t* live_counts, void* workspace, void* stream_) {
     g_err[0] = 0;
-    const char* who = "render_rays_masked_forward";
     const long long P = (long long)rays_per_image;
     if (int rc = check_rays_cfg(cfg, P, who)) return rc;
     if (int rc = check_rays(rays, who)) return rc;
+    const float *near, *far;
+    if (int rc = ray_bounds_of(bounds, who, near, far)) return rc;
     OccGrid grid;
     if (int rc = occ_grid(occ, who, grid)) return rc;
     const int S = cfg->S, B = cfg->B;
@@ -1988,7 +2015,7 @@ int cnerf_render_rays_masked_forward(const cnerf_cfg* cfg, const cnerf_rays* ray
     auto run = [&]() -> int {
         int32_t* hc = live_counts ? live_counts : own_counts;
         // 1. coarse pass: stratified depths and positions, the field on the live ones
-        RaySampleArgs sa{rays->origins, rays->dirs, nullptr, rng->u_strat, c_z, c_pts, n_rays, S, cfg->ray_start, cfg->ray_end, philox_of(cfg)};
+        RaySampleArgs sa{rays->origins, rays->dirs, nullptr, rng->u_strat, c_z, c_pts, n_rays, S, cfg->ray_start, cfg->ray_end, philox_of(cfg), near, far};
         if (hipError_t e = launch_ray_sample(sa, stream)) return hip_fail(e, "ray_sample (coarse)");
         if (int rc = field_pass(c_pts, c_rs, hc, "field kernel (coarse)")) return rc;
         if (hier) {
@@ -2014,6 +2041,40 @@ int cnerf_render_rays_masked_forward(const cnerf_cfg* cfg, const cnerf_rays* ray
     const int rc = run();
     free(own_counts);
     return rc;
+}
+
+int cnerf_render_rays_masked_forward(const cnerf_cfg* cfg, const cnerf_rays* rays, int64_t rays_per_image, const cnerf_occupancy* occ,
+                                     const cnerf_volumes* vols, const float* packed, const float* freq, const float* phase, const cnerf_rng* rng,
+                                     float* pixels, float* dist, const cnerf_aux* aux, int32_t* live_counts, void* workspace, void* stream) {
+    return render_rays_masked_forward_impl("render_rays_masked_forward", cfg, rays, rays_per_image, nullptr, occ, vols, packed, freq, phase, rng, pixels, dist,
+                                           aux, live_counts, workspace, stream);
+}
+
+int cnerf_render_rays_bounded_masked_forward(const cnerf_cfg* cfg, const cnerf_rays* rays, int64_t rays_per_image, const cnerf_ray_bounds* bounds,
+                                             const cnerf_occupancy* occ, const cnerf_volumes* vols, const float* packed, const float* freq,
+                                             const float* phase, const cnerf_rng* rng, float* pixels, float* dist, const cnerf_aux* aux,
+                                             int32_t* live_counts, void* workspace, void* stream) {
+    return render_rays_masked_forward_impl("render_rays_bounded_masked_forward", cfg, rays, rays_per_image, bounds, occ, vols, packed, freq, phase, rng, pixels,
+                                           dist, aux, live_counts, workspace, stream);
+}
+
+int cnerf_occupancy_ray_bounds(const cnerf_occupancy* occ, const cnerf_rays* rays, int32_t B, int64_t rays_per_image, float t_min, float t_max, float pad,
+                               float* near, float* far, uint8_t* hit, void* stream) {
+    g_err[0] = 0;
+    const char* who = "occupancy_ray_bounds";
+    OccGrid g;
+    if (int rc = occ_grid(occ, who, g)) return rc;
+    if (int rc = check_rays(rays, who)) return rc;
+    if (B < 1 || B > 65535) return fail(CNERF_EINVAL, "%s: B=%d out of range [1,65535]", who, B);
+    if (rays_per_image < 1 || rays_per_image > (1LL << 38) / B)       // one lane per ray, 256 per block: at most 2^30 blocks
+        return fail(CNERF_EINVAL, "%s: rays_per_image=%lld must be >= 1 (and B * rays_per_image <= 2^38)", who, (long long)rays_per_image);
+    if (!(fabsf(t_min) < INFINITY) || !(fabsf(t_max) < INFINITY)) return fail(CNERF_EINVAL, "%s: t_min=%g and t_max=%g must be finite", who, (double)t_min, (double)t_max);
+    if (!(t_min < t_max)) return fail(CNERF_EINVAL, "%s: t_max=%g must be greater than t_min=%g", who, (double)t_max, (double)t_min);
+    if (!(pad >= 0.0f) || !(pad < INFINITY)) return fail(CNERF_EINVAL, "%s: pad=%g must be >= 0 and finite", who, (double)pad);
+    if (!near || !far) return fail(CNERF_EINVAL, "%s: near / far is NULL", who);
+    const OccBoundsArgs a{g, occ->side / (float)occ->G, rays->origins, rays->dirs, near, far, hit, (long long)rays_per_image, B, t_min, t_max, pad};
+    if (hipError_t e = launch_occ_ray_bounds(a, (hipStream_t)stream)) return hip_fail(e, "occ_ray_bounds");
+    return CNERF_OK;
 }
 
 }  // extern "C"

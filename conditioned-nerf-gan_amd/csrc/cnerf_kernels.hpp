@@ -230,6 +230,8 @@ struct RaySampleArgs {
     int S;
     float ray_start, ray_end;
     PhiloxKey philox;
+    const float* near;       // (rays) per-ray interval of the coarse depths in place of ray_start ...
+    const float* far;        // ... and ray_end (z == null only), or both null: the two scalars
 };
 hipError_t launch_ray_sample(const RaySampleArgs& a, hipStream_t stream);
 struct RayGradArgs {         // grad_origins (rays,3) += sum_s g, grad_dirs (rays,3) += sum_s z g (each may be null)
@@ -274,7 +276,20 @@ struct OccExpandArgs {
     long long n;
     int B;
 };
+struct OccBoundsArgs {       // per-ray [near, far] from the grid: include/cnerf.h states the contract
+    OccGrid grid;
+    float cell;              // side / (float)G, rounded once on the host: plane j of axis k is lo[k] + (float)j * cell
+    const float* origins;    // (B,P,3)
+    const float* dirs;       // (B,P,3)
+    float* near;             // (B,P)
+    float* far;              // (B,P)
+    uint8_t* hit;            // (B,P) or null
+    long long P;
+    int B;
+    float t_min, t_max, pad;
+};
 hipError_t launch_occ_build(const OccBuildArgs& a, hipStream_t stream);
+hipError_t launch_occ_ray_bounds(const OccBoundsArgs& a, hipStream_t stream);
 hipError_t launch_occ_compact(const OccCompactArgs& a, hipStream_t stream);
 hipError_t launch_occ_expand(const OccExpandArgs& a, hipStream_t stream);
 

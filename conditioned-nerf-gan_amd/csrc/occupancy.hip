@@ -180,6 +180,110 @@ __global__ __launch_bounds__(OCC_BLOCK) void occ_expand_kernel(OccExpandArgs a) 
     }
 }
 
+// ---- per-ray sampling bounds (cnerf_occupancy_ray_bounds) -----------------------------------------------------------------------------
+// [near, far] of a ray = the hull of the depths at which it is inside a set cell, widened by pad and clamped to [t_min, t_max]
+// (include/cnerf.h states the contract).  Unlike occ_live, a segment of the ray OUTSIDE the cube is empty here: the ray is clipped to
+// the cube by a slab test and only cells are looked at.  One lane per ray walks the cells the ray crosses -- a 3-D DDA over the bit
+// words, over the whole clipped span, because the last set cell is wanted as well as the first -- and writes its own three results:
+// no atomics, nothing shared, two runs agree bit for bit.
+//
+// Arithmetic, every operation rounded on its own: plane j of axis k is lo[k] + (float)j * cell (j = 0 .. G; cell = side / G rounded
+// once on the host), and the ray crosses it at ((plane - o_k) / d_k).  Every crossing depth is formed afresh from its plane index --
+// nothing is accumulated from step to step, so the error of a depth does not grow with G: about 4.5 * 2^-23 M in space on the axis
+// crossed, M the largest coordinate magnitude among the origin and the cube's corners.  The depths of one axis are monotone in j
+// (each operation is), so the walk's depth never decreases.  The cell at the entry comes from the position o + d t0 by occ_live's
+// rule, clamped into the grid; where rounding put it one cell behind, the first step has length zero and the walk goes on.
+//
+// Safe without a division by zero and without an unbounded loop: a component d_k == 0 (+0.0 or -0.0) is never divided by and never
+// stepped (the ray misses unless o_k lies in the cube's slab); a NaN or an infinity anywhere in the ray is a miss; every step moves one
+// cell index by one inside [0, G), so there are at most 3 G - 2 of them, and the loop counts to 3 G + 3 besides.
+__device__ __forceinline__ float occ_plane(float lo, float cell, int j) { return lo + (float)j * cell; }
+__device__ __forceinline__ float occ_cross(float lo, float cell, int j, float o, float d) { return (occ_plane(lo, cell, j) - o) / d; }
+// cell index of coordinate p on an axis by occ_live's rule, clamped into [0, G) in float (so that no NaN or infinity is converted)
+__device__ __forceinline__ int occ_entry_cell(float p, float lo, float inv, int G) {
+    return (int)fminf(fmaxf(floorf((p - lo) * inv), 0.0f), (float)(G - 1));
+}
+
+__global__ __launch_bounds__(OCC_BLOCK) void occ_ray_bounds_kernel(OccBoundsArgs a) {
+    const long long r = (long long)blockIdx.x * OCC_BLOCK + threadIdx.x;
+    if (r >= a.P * a.B) return;
+    const uint32_t* bits = occ_image_bits(a.grid, (int)(r / a.P));
+    const int G = a.grid.G;
+    const float cell = a.cell, inv = a.grid.inv;
+    const float lx = a.grid.lo[0], ly = a.grid.lo[1], lz = a.grid.lo[2];
+    const float ox = a.origins[r * 3], oy = a.origins[r * 3 + 1], oz = a.origins[r * 3 + 2];
+    const float dx = a.dirs[r * 3], dy = a.dirs[r * 3 + 1], dz = a.dirs[r * 3 + 2];
+    // a NaN compares false: not finite
+    bool ok = fabsf(ox) < INFINITY && fabsf(oy) < INFINITY && fabsf(oz) < INFINITY && fabsf(dx) < INFINITY && fabsf(dy) < INFINITY && fabsf(dz) < INFINITY;
+    // slab test: [t0, t1] = [t_min, t_max] cut to the depths inside the cube
+    float t0 = a.t_min, t1 = a.t_max;
+    const int sx = dx > 0.0f ? 1 : dx < 0.0f ? -1 : 0, sy = dy > 0.0f ? 1 : dy < 0.0f ? -1 : 0, sz = dz > 0.0f ? 1 : dz < 0.0f ? -1 : 0;
+    auto slab = [&](float lo, float o, float d, int s) {
+        if (s == 0) {
+            ok = ok && o >= lo && o <= occ_plane(lo, cell, G);
+            return;
+        }
+        const float ta = occ_cross(lo, cell, s > 0 ? 0 : G, o, d), tb = occ_cross(lo, cell, s > 0 ? G : 0, o, d);
+        t0 = fmaxf(t0, ta);
+        t1 = fminf(t1, tb);
+    };
+    if (ok) {
+        slab(lx, ox, dx, sx);
+        slab(ly, oy, dy, sy);
+        slab(lz, oz, dz, sz);
+    }
+    bool hit = false;
+    float near = 0.0f, far = 0.0f;
+    if (ok && t0 <= t1) {
+        int cx = occ_entry_cell(ox + dx * t0, lx, inv, G), cy = occ_entry_cell(oy + dy * t0, ly, inv, G), cz = occ_entry_cell(oz + dz * t0, lz, inv, G);
+        // depth at which the ray leaves the current cell through each axis' next plane (never, for an axis it does not move along)
+        float nx = sx ? occ_cross(lx, cell, sx > 0 ? cx + 1 : cx, ox, dx) : INFINITY;
+        float ny = sy ? occ_cross(ly, cell, sy > 0 ? cy + 1 : cy, oy, dy) : INFINITY;
+        float nz = sz ? occ_cross(lz, cell, sz > 0 ? cz + 1 : cz, oz, dz) : INFINITY;
+        float t = t0;
+        for (int n = 0; n < 3 * G + 3; ++n) {
+            const float t_next = fminf(nx, fminf(ny, nz));
+            const float t_out = fminf(fmaxf(t_next, t), t1);           // the cell holds the ray over [t, t_out]
+            const int idx = (cx * G + cy) * G + cz;
+            if ((bits[idx >> 5] >> (idx & 31)) & 1u) {
+                if (!hit) near = t;
+                hit = true;
+                far = t_out;
+            }
+            if (!(t_next < t1)) break;
+            // across the plane that comes first (x before y before z where depths tie), out of the grid: done
+            if (nx <= ny && nx <= nz) {
+                cx += sx;
+                if (cx < 0 || cx >= G) break;
+                nx = occ_cross(lx, cell, sx > 0 ? cx + 1 : cx, ox, dx);
+            } else if (ny <= nz) {
+                cy += sy;
+                if (cy < 0 || cy >= G) break;
+                ny = occ_cross(ly, cell, sy > 0 ? cy + 1 : cy, oy, dy);
+            } else {
+                cz += sz;
+                if (cz < 0 || cz >= G) break;
+                nz = occ_cross(lz, cell, sz > 0 ? cz + 1 : cz, oz, dz);
+            }
+            t = t_out;
+        }
+    }
+    if (hit) {
+        near = fmaxf(a.t_min, near - a.pad);
+        far = fminf(a.t_max, far + a.pad);
+        hit = far > near;
+    }
+    a.near[r] = hit ? near : a.t_min;        // a missed ray keeps the whole interval: it is sampled as it always was
+    a.far[r] = hit ? far : a.t_max;
+    if (a.hit) a.hit[r] = hit ? 1 : 0;
+}
+
+hipError_t launch_occ_ray_bounds(const OccBoundsArgs& a, hipStream_t stream) {
+    const long long rays = a.P * a.B;
+    hipLaunchKernelGGL(occ_ray_bounds_kernel, dim3((unsigned)((rays + OCC_BLOCK - 1) / OCC_BLOCK)), dim3(OCC_BLOCK), 0, stream, a);
+    return hipGetLastError();
+}
+
 hipError_t launch_occ_build(const OccBuildArgs& a, hipStream_t stream) {
     const long long threads = (long long)a.B * a.G * a.G * a.G;
     hipLaunchKernelGGL(occ_build_kernel, dim3((unsigned)((threads + OCC_BLOCK - 1) / OCC_BLOCK)), dim3(OCC_BLOCK), 0, stream, a);

@@ -7,7 +7,7 @@
 // transformed_ray_origins + transformed_ray_directions * z_vals (generators.py:138-142, for the coarse samples as well); autograd of
 // that expression with respect to origins / directions (the depths carry no gradient: generators.py:57,111).
 //
-// All three kernels move 16-28 B per sample point against the field's 0.41 MFLOP: a lane per sample (consecutive lanes write consecutive
+// The kernels here move 16-28 B per sample point against the field's 0.41 MFLOP: a lane per sample (consecutive lanes write consecutive
 // depths and 12-B positions), the ray's six floats are a broadcast load.
 #include "cnerf_dev.hpp"
 #include "cnerf_kernels.hpp"
@@ -34,6 +34,25 @@ __global__ __launch_bounds__(256) void ray_sample_coarse_kernel(RaySampleArgs a)
         const int s = (int)(i - ray * a.S);
         const float u = a.u_strat ? a.u_strat[i] : a.philox.on ? philox_uniform(a.philox, PHILOX_U_STRAT, (unsigned long long)i) : 0.5f;
         const float zl = linspace_at(a.ray_start, a.ray_end, a.S, s);
+        const float off = (u - 0.5f) * dz01;
+        const float z = zl + off;
+        a.z_out[i] = z;
+        store_point(a, i, ray, z);
+    }
+}
+
+// coarse samples over a per-ray interval: the kernel above with zl[s] = linspace_at(near[ray], far[ray], S, s) -- the same linspace_at, the
+// same order of roundings, the same Philox element -- so near / far filled with ray_start / ray_end give its depths bit for bit.  The
+// two interval loads are broadcasts: the S lanes of a ray read the same two floats.
+__global__ __launch_bounds__(256) void ray_sample_coarse_bounded_kernel(RaySampleArgs a) {
+    const long long n = a.rays * a.S;
+    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) {
+        const long long ray = i / a.S;
+        const int s = (int)(i - ray * a.S);
+        const float t0 = a.near[ray], t1 = a.far[ray];
+        const float dz01 = linspace_at(t0, t1, a.S, 1) - linspace_at(t0, t1, a.S, 0);
+        const float u = a.u_strat ? a.u_strat[i] : a.philox.on ? philox_uniform(a.philox, PHILOX_U_STRAT, (unsigned long long)i) : 0.5f;
+        const float zl = linspace_at(t0, t1, a.S, s);
         const float off = (u - 0.5f) * dz01;
         const float z = zl + off;
         a.z_out[i] = z;
@@ -85,6 +104,8 @@ static unsigned sample_blocks(long long n) {
 hipError_t launch_ray_sample(const RaySampleArgs& a, hipStream_t stream) {
     if (a.z)
         hipLaunchKernelGGL(ray_sample_at_kernel, dim3(sample_blocks(a.rays * a.S)), dim3(256), 0, stream, a);
+    else if (a.near)
+        hipLaunchKernelGGL(ray_sample_coarse_bounded_kernel, dim3(sample_blocks(a.rays * a.S)), dim3(256), 0, stream, a);
     else
         hipLaunchKernelGGL(ray_sample_coarse_kernel, dim3(sample_blocks(a.rays * a.S)), dim3(256), 0, stream, a);
     return hipGetLastError();

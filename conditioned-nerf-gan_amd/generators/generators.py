@@ -118,11 +118,20 @@ class ImplicitGenerator3d(nn.Module):
         the field network -- forward only: raises when grad mode is on and any of z, the parameters, origins or dirs requires grad, and
         when the grid's batch is not B; `_aux` then also receives live_coarse / live_fine, (B,) int32: the points each pass evaluated.
         Without the key the call is what it was.
+        ray_near=near, ray_far=far (both (B,P), e.g. from ray_bounds; both or neither): the coarse samples of ray (b,p) are stratified
+        over [near, far] instead of [ray_start, ray_end]; the fine pass resamples inside that span as it always did.  With and without
+        `occupancy`, and differentiable like the unbounded call: the bounds themselves are detached and get no gradient.  ValueError:
+        only one of the two, or a shape other than (B,P).  Without the keys the call is what it was.
         Returns pixels (B,P,3) = 2*rgb-1 and dist (B,P) = sum of weight * depth along the ray."""
         net = self.siren
         net.check_supported()
         if net.drop_out and net.training:
             raise NotImplementedError("render_rays has no dropout: call eval() first, or use forward, the path that has dropout")
+        near, far = kwargs.get("ray_near"), kwargs.get("ray_far")
+        if (near is None) != (far is None):
+            raise ValueError("render_rays: ray_near and ray_far must both be given, or neither")
+        if near is not None and (tuple(near.shape) != tuple(origins.shape[:2]) or tuple(far.shape) != tuple(origins.shape[:2])):
+            raise ValueError(f"render_rays: ray_near and ray_far must be (B,P) = {tuple(origins.shape[:2])}, got {tuple(near.shape)} and {tuple(far.shape)}")
         occupancy = kwargs.get("occupancy")
         if occupancy is not None:
             fv, gl = net.split_z(z)
@@ -142,10 +151,30 @@ class ImplicitGenerator3d(nn.Module):
         aux_out = kwargs.get("_aux")
         pixels, dist, aux = ops.render_rays(net, fvol, freq, phase, origins, dirs, ray_start, ray_end, S, bool(hierarchical_sample), clamp_mode,
                                             noise_std, white_back, last_back, rng, want_aux=aux_out is not None,
-                                            **({} if occupancy is None else {"occupancy": occupancy}))
+                                            **({} if occupancy is None else {"occupancy": occupancy}),
+                                            **({} if near is None else {"near": near, "far": far}))
         if aux_out is not None:
             aux_out.update(aux)
         return pixels, dist
+
+    def ray_bounds(self, grid, origins, dirs, ray_start, ray_end, pad=None):
+        """Per-ray sampling bounds for render_rays(..., ray_near=near, ray_far=far) from an OccupancyGrid of build_occupancy: the span of
+        [ray_start, ray_end] over which ray (b,p) crosses set cells of image b's grid, widened by `pad` on both sides and clamped to
+        [ray_start, ray_end].  A ray that crosses no set cell has hit = 0 and keeps [ray_start, ray_end].  Outside the grid's cube a ray
+        counts as empty (unlike the masked render, which skips nothing there): choose a cube that covers the density.
+        pad is a depth, in units of |dir| like ray_start / ray_end; None: half a cell edge, 0.5 * side / G, which is a length in space --
+        right for unit directions; for unnormalised rays pass pad = 0.5 * side / G / |dir| yourself (one number, e.g. for the shortest
+        direction).  Choose pad no smaller than half a coarse step, (far - near) / (2 (num_steps - 1)): the jitter moves the last
+        coarse sample that far to either side of `far`, the compositing gives a ray's last sample an unbounded interval (as the
+        reference does), and a last sample inside density is opaque (profiles/ray_bounds.md: the default loses at 16 samples).
+        No gradient flows through the bounds.
+        Returns near, far (B,P) float32 and hit (B,P) uint8."""
+        if pad is None:
+            pad = 0.5 * float(grid.side) / int(grid.G)
+        if grid.bits.shape[0] != origins.shape[0]:
+            raise ValueError(f"occupancy holds {grid.bits.shape[0]} grids, the call has rays of {origins.shape[0]} images")
+        with torch.no_grad():
+            return ops.occupancy_ray_bounds(grid, origins, dirs, ray_start, ray_end, pad)
 
     def build_occupancy(self, z, lo, side, resolution=64, threshold=0.0, dilate=1, max_points=1 << 22):
         """Occupancy grids of the scenes z for render_rays(..., occupancy=grid): build once, render many cameras.  The density is queried

@@ -739,14 +739,51 @@ def occupancy_expand(rank, live_rgb_sigma, out=None):
     return out
 
 
-def render_rays_forward(net, levels, freq, phase, origins, dirs, o, rng=None, want_aux=False, aux_keys=None, occupancy=None):
+def _ray_bounds(near, far, B, P):
+    """near / far as render_rays takes them -> detached float32 (B,P) tensors, or (None, None).  ValueError: only one given, a shape other
+    than (B,P)."""
+    if near is None and far is None:
+        return None, None
+    if near is None or far is None:
+        raise ValueError("render_rays: near and far must both be given, or neither")
+    near, far = _f32(near.detach()), _f32(far.detach())
+    if tuple(near.shape) != (B, P) or tuple(far.shape) != (B, P):
+        raise ValueError(f"render_rays: near and far must both be (B,P) = ({B}, {P}), got {tuple(near.shape)} and {tuple(far.shape)}")
+    return near, far
+
+
+def occupancy_ray_bounds(grid, origins, dirs, t_min, t_max, pad=0.0):
+    """cnerf_occupancy_ray_bounds: origins / dirs (B,P,3), one grid per image -> near, far (B,P) float32 and hit (B,P) uint8: the span of
+    [t_min, t_max] over which the ray crosses set cells, widened by pad (t and pad in units of |dir|); a ray that crosses none has
+    hit = 0 and keeps [t_min, t_max].  Outside the grid's cube a ray counts as empty.  include/cnerf.h states the contract."""
+    origins, dirs = _f32(origins.detach()), _f32(dirs.detach())
+    if origins.dim() != 3 or origins.shape[-1] != 3 or dirs.shape != origins.shape:
+        raise L.CnerfError(f"occupancy_ray_bounds: origins and dirs must both be (B,P,3), got {tuple(origins.shape)} and {tuple(dirs.shape)}")
+    B, P = int(origins.shape[0]), int(origins.shape[1])
+    oc, rs = _occ_struct(grid, B), _rays_struct(origins, dirs)
+    near = torch.empty((B, P), dtype=torch.float32, device=origins.device)
+    far = torch.empty_like(near)
+    hit = torch.empty((B, P), dtype=torch.uint8, device=origins.device)
+    L.check(L.lib().cnerf_occupancy_ray_bounds(C.byref(oc), C.byref(rs), B, P, float(t_min), float(t_max), float(pad), L.ptr(near), L.ptr(far),
+                                               C.c_void_p(hit.data_ptr()), _stream()), "cnerf_occupancy_ray_bounds")
+    return near, far, hit
+
+
+def render_rays_forward(net, levels, freq, phase, origins, dirs, o, rng=None, want_aux=False, aux_keys=None, occupancy=None, near=None, far=None):
     """cnerf_render_rays_forward on channel-last levels: origins / dirs (B,P,3) -> pixels (B,P,3), dist (B,P), aux dict.
     occupancy (an OccupancyGrid with one grid per image): cnerf_render_rays_masked_forward instead -- samples in cells whose bit is
     clear are not evaluated; forward only; the call synchronises the stream.  aux then also holds live_coarse / live_fine, (B,) int32
-    on the host: the points each pass gave to the field."""
+    on the host: the points each pass gave to the field.
+    near / far (B,P): the coarse samples of ray (b,p) are placed over [near, far] instead of [ray_start, ray_end] (the bounded entries);
+    without them the call is what it was."""
     origins, dirs = _f32(origins), _f32(dirs)
     if origins.dim() != 3 or origins.shape[-1] != 3 or dirs.shape != origins.shape:
         raise L.CnerfError(f"render_rays: origins and dirs must both be (B,P,3), got {tuple(origins.shape)} and {tuple(dirs.shape)}")
+    near, far = _ray_bounds(near, far, o["B"], int(origins.shape[1]))
+    bounds = None
+    if near is not None:
+        bounds = L.RayBounds()
+        bounds.near, bounds.far = L.ptr(near).value, L.ptr(far).value
     B, P, S, hier = o["B"], int(origins.shape[1]), o["S"], o["hier"]
     n = 2 * S if hier else S
     dev = origins.device
@@ -772,18 +809,24 @@ def render_rays_forward(net, levels, freq, phase, origins, dirs, o, rng=None, wa
     if occupancy is not None:
         oc = _occ_struct(occupancy, B)
         live = (C.c_int32 * (2 * B))()
-        L.check(L.lib().cnerf_render_rays_masked_forward(C.byref(cfg), C.byref(rs), P, C.byref(oc), C.byref(vs), L.ptr(packed), L.ptr(_f32(freq)),
-                                                         L.ptr(_f32(phase)), C.byref(r), L.ptr(pixels), L.ptr(dist),
-                                                         C.byref(aux_s) if aux_s is not None else None, live, L.ptr(ws), _stream()),
-                "cnerf_render_rays_masked_forward")
+        tail = (C.byref(oc), C.byref(vs), L.ptr(packed), L.ptr(_f32(freq)), L.ptr(_f32(phase)), C.byref(r), L.ptr(pixels), L.ptr(dist),
+                C.byref(aux_s) if aux_s is not None else None, live, L.ptr(ws), _stream())
+        if bounds is None:
+            L.check(L.lib().cnerf_render_rays_masked_forward(C.byref(cfg), C.byref(rs), P, *tail), "cnerf_render_rays_masked_forward")
+        else:
+            L.check(L.lib().cnerf_render_rays_bounded_masked_forward(C.byref(cfg), C.byref(rs), P, C.byref(bounds), *tail),
+                    "cnerf_render_rays_bounded_masked_forward")
         if want_aux or aux_keys:
             aux_t["live_coarse"] = torch.tensor(live[:B], dtype=torch.int32)
             if hier:
                 aux_t["live_fine"] = torch.tensor(live[B:], dtype=torch.int32)
         return pixels, dist, aux_t
-    L.check(L.lib().cnerf_render_rays_forward(C.byref(cfg), C.byref(rs), P, C.byref(vs), L.ptr(packed), L.ptr(_f32(freq)), L.ptr(_f32(phase)), C.byref(r),
-                                              L.ptr(pixels), L.ptr(dist), C.byref(aux_s) if aux_s is not None else None, L.ptr(ws), _stream()),
-            "cnerf_render_rays_forward")
+    tail = (C.byref(vs), L.ptr(packed), L.ptr(_f32(freq)), L.ptr(_f32(phase)), C.byref(r), L.ptr(pixels), L.ptr(dist),
+            C.byref(aux_s) if aux_s is not None else None, L.ptr(ws), _stream())
+    if bounds is None:
+        L.check(L.lib().cnerf_render_rays_forward(C.byref(cfg), C.byref(rs), P, *tail), "cnerf_render_rays_forward")
+    else:
+        L.check(L.lib().cnerf_render_rays_bounded_forward(C.byref(cfg), C.byref(rs), P, C.byref(bounds), *tail), "cnerf_render_rays_bounded_forward")
     return pixels, dist, aux_t
 
 
@@ -826,7 +869,9 @@ def render_rays_backward(net, o, levels, freq, phase, origins, dirs, rng, saved,
 class RenderRaysFunction(torch.autograd.Function):
     """ImplicitGenerator3d.render_rays as one autograd node: differentiable w.r.t. the feature volume(s), freq / phase (and through them
     the mapping network and the global feature), the field parameters and the rays' origins and directions; the sample depths carry no
-    gradient (the reference draws and resamples them under no_grad: generators.py:57,111)."""
+    gradient (the reference draws and resamples them under no_grad: generators.py:57,111).  Per-ray bounds travel in o["near"] / o["far"],
+    detached: they place depths, so they get no gradient either (None in backward, with the rest of `o`); the backward reads the saved
+    depths and never the interval."""
 
     @staticmethod
     def forward(ctx, net, o, rng, origins, dirs, freq, phase, n_vols, *rest):
@@ -838,7 +883,7 @@ class RenderRaysFunction(torch.autograd.Function):
         org, drs = _f32(origins.detach()), _f32(dirs.detach())
         need_grad = o["need_grad"]
         pixels, dist, aux = render_rays_forward(net, levels, fr, ph, org, drs, o, rng, want_aux=o["want_aux"],
-                                                aux_keys=SAVED_KEYS if need_grad and not o["want_aux"] else None)
+                                                aux_keys=SAVED_KEYS if need_grad and not o["want_aux"] else None, near=o.get("near"), far=o.get("far"))
         ctx.net, ctx.o, ctx.rng, ctx.n_vols = net, o, rng, n_vols
         if need_grad:
             saved = [aux.get(k) for k in SAVED_KEYS]
@@ -859,14 +904,18 @@ class RenderRaysFunction(torch.autograd.Function):
 
 
 def render_rays(net, fvol, freq, phase, origins, dirs, ray_start, ray_end, num_steps, hierarchical, clamp_mode, noise_std,
-                white_back=False, last_back=False, rng=None, want_aux=False, occupancy=None):
+                white_back=False, last_back=False, rng=None, want_aux=False, occupancy=None, near=None, far=None):
     """Differentiable render of caller-given rays, used by ImplicitGenerator3d.render_rays.  origins / dirs (B,P,3) world (dirs are not
     normalised here: depths are in units of |dir|); fvol: (B,C,V,V,V) or a list of pyramid levels.
     occupancy (OccupancyGrid): the masked render -- forward only, no autograd node; refuses inputs that require grad in grad mode.
+    near / far (B,P), both or neither: the coarse samples of a ray are placed over its own [near, far] instead of [ray_start, ray_end]
+    (occupancy_ray_bounds makes them from a grid), with and without `occupancy`, forward and backward.  They are detached: no gradient
+    flows to them, whether or not they require one.  ValueError: only one given, a shape other than (B,P).
     Returns (pixels (B,P,3) = 2*rgb-1, dist (B,P) = distance along the ray, aux dict)."""
     o = dict(B=int(origins.shape[0]), S=int(num_steps), ray_start=float(ray_start), ray_end=float(ray_end), hier=bool(hierarchical),
              clamp_mode=clamp_mode, noise_std=float(noise_std), white_back=bool(white_back), last_back=bool(last_back), want_aux=bool(want_aux))
     _ray_flags(clamp_mode, white_back, last_back)      # refuses an unknown clamp mode before any work
+    near, far = _ray_bounds(near, far, o["B"], int(origins.shape[1]))
     vols = as_levels(fvol)
     params = net.field_params()
     o["need_grad"] = torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (origins, dirs, freq, phase, *vols, *params))
@@ -876,6 +925,8 @@ def render_rays(net, fvol, freq, phase, origins, dirs, ray_start, ray_end, num_s
         det = lambda t: None if t is None else _f32(t.detach())
         with torch.no_grad():
             return render_rays_forward(net, [channel_last(v.detach()) for v in vols], det(freq), det(phase), det(origins), det(dirs), o, rng or {},
-                                       want_aux=want_aux, occupancy=occupancy)
+                                       want_aux=want_aux, occupancy=occupancy, near=near, far=far)
+    if near is not None:
+        o["near"], o["far"] = near, far
     pixels, dist = RenderRaysFunction.apply(net, o, rng or {}, origins, dirs, freq, phase, len(vols), *vols, *params)
     return pixels, dist, (RenderRaysFunction.last_aux if want_aux else {})

@@ -579,6 +579,57 @@ int cnerf_render_rays_masked_forward(const cnerf_cfg* cfg, const cnerf_rays* ray
                                      const cnerf_rng* rng, float* pixels /* (B,P,3) */, float* dist /* (B,P) */, const cnerf_aux* aux,
                                      int32_t* live_counts /* HOST int32 (2,B) or NULL */, void* workspace, void* stream);
 
+/* ---- per-ray sampling bounds (added in ABI v10 without a version change: no struct changed, additive symbols only) -------------------
+ * cnerf_render_rays_forward places the S coarse samples of every ray over the one interval [cfg.ray_start, cfg.ray_end].  The entries
+ * below place them over an interval of the ray's own, and cnerf_occupancy_ray_bounds takes such intervals from an occupancy grid: the
+ * span of the ray that crosses set cells.  The reference has neither.
+ *
+ *   cnerf_render_rays_bounded_forward, cnerf_render_rays_bounded_masked_forward
+ *       cnerf_render_rays_forward / cnerf_render_rays_masked_forward (which are these two with bounds == NULL) with the coarse depths
+ *       z = zl[s] + (u - 0.5) (zl[1] - zl[0]),  zl = torch.linspace(near[b,p], far[b,p], S):  the same linspace, order of roundings and
+ *       Philox indexing, so near / far filled with ray_start / ray_end give the unbounded call's bits.  The fine pass, the merge and the
+ *       compositing do not change.  bounds NULL, or both members NULL: the scalars of cfg.  CNERF_EINVAL before any launch: what the
+ *       unbounded entry refuses; only one of near / far given.  The values are not checked: far <= near, a NaN or an infinity give the
+ *       depths that arithmetic gives.  Workspaces: those of the unbounded entries.
+ *       There is no bounded backward entry and none is needed: the depths carry no gradient (generators.py:57,111), and
+ *       cnerf_render_rays_backward re-forms the sample positions from saved->coarse_z / fine_z, never from ray_start / ray_end -- pass
+ *       it the tensors a bounded forward saved.
+ *
+ *   cnerf_occupancy_ray_bounds   near, far (B,P) float32 and hit (B,P) uint8 (may be NULL) of rays (B,P), one grid per image.
+ *       Contract, exact on the real line (the fp32 kernel's error is stated below).  Omega_b = the union of the CLOSED cells of image b
+ *       whose bit is set, cell (ix, iy, iz) = the product of [lo_k + i_k side / G, lo_k + (i_k + 1) side / G];  T = the set of t in
+ *       [t_min, t_max] with o + t d in Omega_b.
+ *         T empty:    hit = 0, near = t_min, far = t_max -- a missed ray is sampled as it always was, never over a degenerate interval.
+ *         otherwise:  hit = 1, near = max(t_min, inf T - pad), far = min(t_max, sup T + pad); if that leaves far <= near the ray counts
+ *                     as missed (so with pad = 0 a ray that only touches Omega_b at one depth is a miss).
+ *       t and pad are in units of |dir|, like every depth of the ray path: for a pad of a length in space divide it by |dir|.
+ *       Segments of a ray OUTSIDE the cube count as EMPTY here -- unlike the liveness rule of the masked render above, where nothing
+ *       outside the cube is skipped.  Samples placed over [near, far] therefore see nothing of density outside the cube.
+ *       The kernel clips the ray to the cube (slab test) and walks the cells it crosses over the whole clipped span (3-D DDA over the bit
+ *       words, at most 3 G + 3 steps, one lane per ray, no atomics: deterministic).  fp32, every operation rounded on its own: plane j of
+ *       axis k at lo_k + (float)j * (side / (float)G), crossed at (plane - o_k) / d_k, each depth formed from its plane index, none
+ *       accumulated.  With M the largest coordinate magnitude among the origin and the cube's corners, [near, far] of a hit lies
+ *       between the exact hulls for every set cell shrunk and grown by 32 * 2^-23 * M in space, and hit is exact outside that margin.
+ *       A component d_k == 0 (either sign) is not divided by: the ray misses unless o_k is in the cube's slab.  A NaN or an infinity in
+ *       the ray's origin or direction: a miss.  A ray that starts inside the cube starts at t_min; t_min beyond the exit: a miss.
+ *       CNERF_EINVAL before the launch: the grid checks of cnerf_occupancy_compact, rays / near / far NULL, B or rays_per_image < 1,
+ *       t_min or t_max not finite, t_max <= t_min, pad < 0 or not finite.  Asynchronous on `stream`, allocates nothing. */
+typedef struct cnerf_ray_bounds {    /* HOST struct of device pointers */
+    const float* near;               /* (B,P) */
+    const float* far;                /* (B,P) */
+} cnerf_ray_bounds;
+
+int cnerf_occupancy_ray_bounds(const cnerf_occupancy* occ, const cnerf_rays* rays, int32_t B, int64_t rays_per_image, float t_min, float t_max,
+                               float pad, float* near /* (B,P) */, float* far /* (B,P) */, uint8_t* hit /* (B,P) or NULL */, void* stream);
+int cnerf_render_rays_bounded_forward(const cnerf_cfg* cfg, const cnerf_rays* rays, int64_t rays_per_image, const cnerf_ray_bounds* bounds,
+                                      const cnerf_volumes* vols, const float* packed, const float* freq, const float* phase, const cnerf_rng* rng,
+                                      float* pixels /* (B,P,3) */, float* dist /* (B,P) */, const cnerf_aux* aux, void* workspace, void* stream);
+int cnerf_render_rays_bounded_masked_forward(const cnerf_cfg* cfg, const cnerf_rays* rays, int64_t rays_per_image, const cnerf_ray_bounds* bounds,
+                                             const cnerf_occupancy* occ, const cnerf_volumes* vols, const float* packed, const float* freq,
+                                             const float* phase, const cnerf_rng* rng, float* pixels /* (B,P,3) */, float* dist /* (B,P) */,
+                                             const cnerf_aux* aux, int32_t* live_counts /* HOST int32 (2,B) or NULL */, void* workspace,
+                                             void* stream);
+
 #ifdef __cplusplus
 }
 #endif
