@@ -146,6 +146,10 @@ PROTOTYPES = {
     "cnerf_render_rays_bounded_masked_forward": (C.c_int, [C.POINTER(Cfg), C.POINTER(Rays), C.c_int64, C.POINTER(RayBounds), C.POINTER(Occupancy),
                                                            C.POINTER(Volumes), C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(Rng), C.c_void_p, C.c_void_p,
                                                            C.POINTER(Aux), C.POINTER(C.c_int32), C.c_void_p, C.c_void_p]),
+    "cnerf_isosurface_bytes": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_size_t)]),
+    "cnerf_isosurface_count": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "cnerf_isosurface_emit": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_float, C.POINTER(C.c_float), C.c_float, C.c_void_p, C.c_int32,
+                                        C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
 }
 
 _lib = None

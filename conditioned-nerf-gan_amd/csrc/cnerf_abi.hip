@@ -2078,3 +2078,81 @@ int cnerf_occupancy_ray_bounds(const cnerf_occupancy* occ, const cnerf_rays* ray
 }
 
 }  // extern "C"
+
+// ---------------------------------------------------------------------------------------------------------------------
+// isosurfaces: marching tetrahedra on a scalar lattice (csrc/isosurface.hip)
+// ---------------------------------------------------------------------------------------------------------------------
+namespace {
+int check_iso_shape(int n0, int n1, int n2, const char* who) {
+    const int n[3] = {n0, n1, n2};
+    for (int c = 0; c < 3; ++c)
+        if (n[c] < 2 || n[c] > 1024) return fail(CNERF_EINVAL, "%s: n%d=%d out of range [2,1024]", who, c, n[c]);
+    if ((long long)n0 * n1 * n2 > (1LL << 27)) return fail(CNERF_EINVAL, "%s: n0 n1 n2 = %lld exceeds 2^27", who, (long long)n0 * n1 * n2);
+    return CNERF_OK;
+}
+// Workspace of cnerf_isosurface_count / _emit: code (n) uint8, voff (n) int32, toff (n) int32, block sums (2, blocks) int32
+struct IsoLayout {
+    size_t code, voff, toff, sums, total;
+};
+IsoLayout iso_layout(const IsoDims& d) {
+    IsoLayout W{};
+    size_t off = 0;
+    auto take = [&](size_t bytes) { const size_t o = off; off += align256(bytes); return o; };
+    W.code = take((size_t)d.n);
+    W.voff = take((size_t)d.n * sizeof(int32_t));
+    W.toff = take((size_t)d.n * sizeof(int32_t));
+    W.sums = take((size_t)2 * d.blocks * sizeof(int32_t));
+    W.total = off;
+    return W;
+}
+}  // namespace
+
+extern "C" {
+
+int cnerf_isosurface_bytes(int32_t n0, int32_t n1, int32_t n2, size_t* workspace) {
+    g_err[0] = 0;
+    if (int rc = check_iso_shape(n0, n1, n2, "isosurface_bytes")) return rc;
+    if (workspace) *workspace = iso_layout(iso_dims(n0, n1, n2)).total;
+    return CNERF_OK;
+}
+
+int cnerf_isosurface_count(int32_t n0, int32_t n1, int32_t n2, const float* values, float level, int32_t* counts, void* workspace, void* stream) {
+    g_err[0] = 0;
+    const char* who = "isosurface_count";
+    if (int rc = check_iso_shape(n0, n1, n2, who)) return rc;
+    if (!values || !counts || !workspace) return fail(CNERF_EINVAL, "%s: NULL argument (values / counts / workspace)", who);
+    if (!(fabsf(level) < INFINITY)) return fail(CNERF_EINVAL, "%s: level=%g must be finite", who, (double)level);
+    const IsoDims d = iso_dims(n0, n1, n2);
+    const IsoLayout W = iso_layout(d);
+    char* ws = (char*)workspace;
+    const IsoCountArgs a{d, values, level, (uint8_t*)(ws + W.code), (int32_t*)(ws + W.voff), (int32_t*)(ws + W.toff), (int32_t*)(ws + W.sums), counts};
+    if (hipError_t e = launch_iso_count(a, (hipStream_t)stream)) return hip_fail(e, "iso_count");
+    return CNERF_OK;
+}
+
+int cnerf_isosurface_emit(int32_t n0, int32_t n1, int32_t n2, const float* values, float level, const float lo[3], float pitch, const float* attrs,
+                          int32_t n_attr, int64_t max_vertices, int64_t max_triangles, float* vertices, float* vertex_attrs, int32_t* triangles,
+                          const void* workspace, void* stream) {
+    g_err[0] = 0;
+    const char* who = "isosurface_emit";
+    if (int rc = check_iso_shape(n0, n1, n2, who)) return rc;
+    if (!values || !workspace || !vertices || !triangles || !lo) return fail(CNERF_EINVAL, "%s: NULL argument (values / lo / workspace / vertices / triangles)", who);
+    if (!(fabsf(level) < INFINITY)) return fail(CNERF_EINVAL, "%s: level=%g must be finite", who, (double)level);
+    if (!(pitch > 0.0f) || !(pitch < INFINITY)) return fail(CNERF_EINVAL, "%s: pitch=%g must be > 0 and finite", who, (double)pitch);
+    for (int c = 0; c < 3; ++c)
+        if (!(fabsf(lo[c]) < INFINITY)) return fail(CNERF_EINVAL, "%s: lo[%d]=%g must be finite", who, c, (double)lo[c]);
+    if ((attrs == nullptr) != (vertex_attrs == nullptr)) return fail(CNERF_EINVAL, "%s: attrs and vertex_attrs must both be given, or neither", who);
+    if (attrs && (n_attr < 1 || n_attr > 8)) return fail(CNERF_EINVAL, "%s: n_attr=%d out of range [1,8]", who, n_attr);
+    if (max_vertices < 0 || max_triangles < 0)
+        return fail(CNERF_EINVAL, "%s: max_vertices=%lld and max_triangles=%lld must be >= 0", who, (long long)max_vertices, (long long)max_triangles);
+    const IsoDims d = iso_dims(n0, n1, n2);
+    const IsoLayout W = iso_layout(d);
+    const char* ws = (const char*)workspace;
+    const IsoEmitArgs a{d, values, level, {lo[0], lo[1], lo[2]}, pitch, attrs, attrs ? n_attr : 0, (long long)max_vertices, (long long)max_triangles,
+                        vertices, vertex_attrs, triangles, (const uint8_t*)(ws + W.code), (const int32_t*)(ws + W.voff), (const int32_t*)(ws + W.toff),
+                        (const int32_t*)(ws + W.sums)};
+    if (hipError_t e = launch_iso_emit(a, (hipStream_t)stream)) return hip_fail(e, "iso_emit");
+    return CNERF_OK;
+}
+
+}  // extern "C"

@@ -292,6 +292,49 @@ hipError_t launch_occ_build(const OccBuildArgs& a, hipStream_t stream);
 hipError_t launch_occ_ray_bounds(const OccBoundsArgs& a, hipStream_t stream);
 hipError_t launch_occ_compact(const OccCompactArgs& a, hipStream_t stream);
 hipError_t launch_occ_expand(const OccExpandArgs& a, hipStream_t stream);
+// rows of `chunks` counts each -> their exclusive offsets in place and the rows' totals in counts (rows): one block per row
+hipError_t launch_occ_scan(int32_t* block_counts, int32_t* counts, int rows, int chunks, hipStream_t stream);
+
+// isosurface.hip: marching tetrahedra on a scalar lattice (include/cnerf.h states the algorithm, DESIGN.md 3.19 the workspace)
+constexpr int ISO_BLOCK = 256;       // lattice points of a block, one per lane: the unit of the block sums
+struct IsoDims {
+    int n0, n1, n2;
+    int n;                   // n0 n1 n2 <= 2^27
+    int blocks;              // ceil(n / ISO_BLOCK)
+};
+inline IsoDims iso_dims(int n0, int n1, int n2) {
+    const int n = n0 * n1 * n2;
+    return IsoDims{n0, n1, n2, n, (n + ISO_BLOCK - 1) / ISO_BLOCK};
+}
+struct IsoCountArgs {
+    IsoDims d;
+    const float* values;     // (n0,n1,n2)
+    float level;
+    uint8_t* code;           // (n) INSIDE bits of the point (bit 0) and its seven forward neighbours (bit d0 + 2 d1 + 4 d2)
+    int32_t* voff;           // (n) vertices owned by the points before this one in its block
+    int32_t* toff;           // (n) triangles of the cells before this one in its block
+    int32_t* block_sums;     // (2, blocks) vertices, triangles per block; after the scan their exclusive offsets
+    int32_t* counts;         // (2) vertices, triangles
+};
+struct IsoEmitArgs {
+    IsoDims d;
+    const float* values;
+    float level;
+    float lo[3];
+    float pitch;
+    const float* attrs;      // (n0,n1,n2,n_attr) or null
+    int n_attr;              // 0 without attrs
+    long long max_vertices, max_triangles;
+    float* vertices;         // (max_vertices,3)
+    float* vertex_attrs;     // (max_vertices,n_attr) or null
+    int32_t* triangles;      // (max_triangles,3)
+    const uint8_t* code;
+    const int32_t* voff;
+    const int32_t* toff;
+    const int32_t* block_offsets;    // (2, blocks)
+};
+hipError_t launch_iso_count(const IsoCountArgs& a, hipStream_t stream);
+hipError_t launch_iso_emit(const IsoEmitArgs& a, hipStream_t stream);
 
 hipError_t launch_philox_fill(const PhiloxKey& k, uint32_t stream_id, long long n, int normal, float* out, hipStream_t stream);
 hipError_t launch_transpose_cl(int B, int C, int V, const float* src, float* dst, bool to_channel_last, hipStream_t stream);

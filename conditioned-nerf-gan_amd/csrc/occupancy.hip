@@ -290,12 +290,16 @@ hipError_t launch_occ_build(const OccBuildArgs& a, hipStream_t stream) {
     return hipGetLastError();
 }
 
+hipError_t launch_occ_scan(int32_t* block_counts, int32_t* counts, int rows, int chunks, hipStream_t stream) {
+    hipLaunchKernelGGL(occ_scan_kernel, dim3(rows), dim3(OCC_BLOCK), 0, stream, block_counts, counts, chunks);
+    return hipGetLastError();
+}
+
 hipError_t launch_occ_compact(const OccCompactArgs& a, hipStream_t stream) {
     const int chunks = (int)occ_chunks(a.n);
     hipLaunchKernelGGL(occ_count_kernel, dim3(chunks, a.B), dim3(OCC_BLOCK), 0, stream, a);
     if (hipError_t e = hipGetLastError()) return e;
-    hipLaunchKernelGGL(occ_scan_kernel, dim3(a.B), dim3(OCC_BLOCK), 0, stream, a.block_counts, a.counts, chunks);
-    if (hipError_t e = hipGetLastError()) return e;
+    if (hipError_t e = launch_occ_scan(a.block_counts, a.counts, a.B, chunks, stream)) return e;
     hipLaunchKernelGGL(occ_rank_kernel, dim3(chunks, a.B), dim3(OCC_BLOCK), 0, stream, a);
     return hipGetLastError();
 }

@@ -4,9 +4,19 @@ here, not pinned: the grid arithmetic below is written to give the same sample c
 
     sigma = sample_generator(generator, z, voxel_resolution=256)        # (N, N, N) numpy array, sigma[i0, i1, i2]
 
-The field kernel takes the whole grid in a few launches (2^22 points per call) instead of the reference's 64^3 slices."""
+The field kernel takes the whole grid in a few launches (2^22 points per call) instead of the reference's 64^3 slices.
+
+The surface itself, which the reference leaves to outside tools:
+
+    vertices, faces, colors = extract_mesh(generator, z, voxel_resolution=256)     # device tensors: (Nv,3), (Nt,3) int32, (Nv,3)
+    write_ply("car.ply", vertices, faces, colors)
+
+extract_mesh keeps the grid's four field channels on the device and hands them to ops.isosurface (marching tetrahedra in HIP,
+include/cnerf.h states the algorithm); nothing but the two counts crosses to the host."""
 import numpy as np
 import torch
+
+from . import ops
 
 
 def create_samples(N=256, voxel_origin=(0, 0, 0), cube_length=2.0):
@@ -38,3 +48,52 @@ def sample_generator(generator, z, voxel_resolution=256, voxel_origin=(0, 0, 0),
             chunk = pts[:, s0:s0 + max_points].contiguous()
             sig[:, s0:s0 + chunk.shape[1]] = generator.siren(chunk, z, N, 1)[..., 3]
     return sig.reshape(N, N, N).cpu().numpy()
+
+
+def extract_mesh(generator, z, voxel_resolution=256, voxel_origin=(0, 0, 0), cube_length=1.2, level=0.0, colors=True, max_points=1 << 22):
+    """The level set sigma = level of one conditioned scene as an indexed triangle mesh on the device: vertices (Nv,3) float32, faces
+    (Nt,3) int32, colors (Nv,3) float32 (the field's channels 0..2 interpolated along the crossed edges) or None.
+
+    The grid is sample_generator's (same coordinates, same chunking).  Lattice point (i0,i1,i2) is given the position
+    i_c * pitch + (corner[2], corner[1], corner[0])[c] -- create_samples' column convention; its columns 0 and 1 are not floored, so off
+    the i2 = 0 face the field is sampled up to one pitch beyond that position on those axes, as in every grid the reference extracts.
+    The normals point toward falling sigma: out of the shape."""
+    N = int(voxel_resolution)
+    pts, corner, pitch = create_samples(N, voxel_origin, cube_length)
+    pts = pts.to(generator.device)
+    field = torch.empty((1, N ** 3, 4), dtype=torch.float32, device=generator.device)
+    with torch.no_grad():
+        for s0 in range(0, N ** 3, max_points):
+            chunk = pts[:, s0:s0 + max_points].contiguous()
+            field[:, s0:s0 + chunk.shape[1]] = generator.siren(chunk, z, N, 1)
+    field = field.reshape(N, N, N, 4)
+    sigma = field[..., 3].contiguous()
+    attrs = field[..., :3].contiguous() if colors else None
+    lo = (float(corner[2]), float(corner[1]), float(corner[0]))
+    return ops.isosurface(sigma, level, lo=lo, pitch=pitch, attrs=attrs)
+
+
+def write_ply(path, vertices, faces, colors=None):
+    """Binary little-endian PLY: float x y z per vertex (and uchar red green blue = clamp(rgb, 0, 1) * 255 when colors is given), one
+    uchar count + three int indices per face.  Takes tensors on any device or NumPy arrays."""
+    as_np = lambda a: a.detach().cpu().numpy() if torch.is_tensor(a) else np.asarray(a)
+    v = as_np(vertices).astype("<f4").reshape(-1, 3)
+    f = as_np(faces).astype("<i4").reshape(-1, 3)
+    props = [("x", "<f4"), ("y", "<f4"), ("z", "<f4")]
+    names = ["property float x", "property float y", "property float z"]
+    if colors is not None:
+        props += [("red", "u1"), ("green", "u1"), ("blue", "u1")]
+        names += ["property uchar red", "property uchar green", "property uchar blue"]
+    vert = np.empty(len(v), dtype=props)
+    vert["x"], vert["y"], vert["z"] = v[:, 0], v[:, 1], v[:, 2]
+    if colors is not None:
+        c = (np.clip(as_np(colors).astype(np.float32).reshape(-1, 3), 0.0, 1.0) * 255.0).astype(np.uint8)
+        vert["red"], vert["green"], vert["blue"] = c[:, 0], c[:, 1], c[:, 2]
+    face = np.empty(len(f), dtype=[("n", "u1"), ("v", "<i4", (3,))])
+    face["n"], face["v"] = 3, f
+    header = ["ply", "format binary_little_endian 1.0", f"element vertex {len(v)}", *names, f"element face {len(f)}",
+              "property list uchar int vertex_indices", "end_header"]
+    with open(path, "wb") as out:
+        out.write(("\n".join(header) + "\n").encode("ascii"))
+        out.write(vert.tobytes())
+        out.write(face.tobytes())

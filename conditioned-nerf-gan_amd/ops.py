@@ -769,6 +769,40 @@ def occupancy_ray_bounds(grid, origins, dirs, t_min, t_max, pad=0.0):
     return near, far, hit
 
 
+def isosurface(values, level, lo=(0.0, 0.0, 0.0), pitch=1.0, attrs=None):
+    """cnerf_isosurface_count / _emit: the level set of a scalar lattice values (N0,N1,N2) as an indexed triangle mesh, by marching
+    tetrahedra (include/cnerf.h states the algorithm: orderings, arithmetic and orientation are fixed).  Lattice point (i0,i1,i2) sits at
+    i * pitch + lo; attrs (N0,N1,N2,C), C <= 8, are interpolated along the edges like the positions.
+    -> vertices (Nv,3) float32, faces (Nt,3) int32, vertex_attrs (Nv,C) float32 or None, on the device of `values`.  The two counts are
+    copied to the host between the calls (one synchronisation); an empty surface gives empty tensors and no second launch."""
+    values = _f32(values.detach())
+    if values.dim() != 3:
+        raise L.CnerfError(f"isosurface: values must be (N0,N1,N2), got {tuple(values.shape)}")
+    n0, n1, n2 = (int(s) for s in values.shape)
+    dev = values.device
+    if attrs is not None:
+        attrs = _f32(attrs.detach())
+        if attrs.dim() != 4 or tuple(attrs.shape[:3]) != (n0, n1, n2):
+            raise L.CnerfError(f"isosurface: attrs must be ({n0},{n1},{n2},C), got {tuple(attrs.shape)}")
+    n_attr = 0 if attrs is None else int(attrs.shape[3])
+    lib = L.lib()
+    nb = C.c_size_t(0)
+    L.check(lib.cnerf_isosurface_bytes(n0, n1, n2, C.byref(nb)), "cnerf_isosurface_bytes")
+    ws = torch.empty(nb.value, dtype=torch.uint8, device=dev)
+    counts = torch.empty((2,), dtype=torch.int32, device=dev)
+    L.check(lib.cnerf_isosurface_count(n0, n1, n2, L.ptr(values), float(level), L.ptr(counts), L.ptr(ws), _stream()), "cnerf_isosurface_count")
+    nv, nt = (int(c) for c in counts.tolist())
+    vertices = torch.empty((nv, 3), dtype=torch.float32, device=dev)
+    faces = torch.empty((nt, 3), dtype=torch.int32, device=dev)
+    vertex_attrs = None if attrs is None else torch.empty((nv, n_attr), dtype=torch.float32, device=dev)
+    if nv == 0:
+        return vertices, faces, vertex_attrs
+    lo3 = (C.c_float * 3)(*(float(v) for v in lo))
+    L.check(lib.cnerf_isosurface_emit(n0, n1, n2, L.ptr(values), float(level), lo3, float(pitch), L.ptr(attrs), n_attr, nv, nt, L.ptr(vertices),
+                                      L.ptr(vertex_attrs), L.ptr(faces), L.ptr(ws), _stream()), "cnerf_isosurface_emit")
+    return vertices, faces, vertex_attrs
+
+
 def render_rays_forward(net, levels, freq, phase, origins, dirs, o, rng=None, want_aux=False, aux_keys=None, occupancy=None, near=None, far=None):
     """cnerf_render_rays_forward on channel-last levels: origins / dirs (B,P,3) -> pixels (B,P,3), dist (B,P), aux dict.
     occupancy (an OccupancyGrid with one grid per image): cnerf_render_rays_masked_forward instead -- samples in cells whose bit is

@@ -630,6 +630,51 @@ int cnerf_render_rays_bounded_masked_forward(const cnerf_cfg* cfg, const cnerf_r
                                              const cnerf_aux* aux, int32_t* live_counts /* HOST int32 (2,B) or NULL */, void* workspace,
                                              void* stream);
 
+/* ---- isosurfaces: an indexed triangle mesh of a scalar lattice (added in ABI v10 without a version change: additive symbols only) -----
+ * The other consumer of a conditioned field is its shape (the reference's extract_shapes.py samples sigma on an N^3 grid and leaves the
+ * surface to outside tools).  These entries turn a scalar lattice on the device into vertices and triangles on the device, by marching
+ * tetrahedra on the Kuhn split of every cell.  The algorithm is fixed here so that it can be checked exactly.
+ *
+ * Lattice.  values v[i0,i1,i2], (n0,n1,n2) row-major fp32, each n_c in [2,1024], n0 n1 n2 <= 2^27 (both totals then fit int32).  Point
+ *   (i0,i1,i2) sits at position component c = (float)i_c * pitch + lo[c]: the product rounded, then the sum, no fma.
+ * Cells.  A point is INSIDE iff v > level: a value equal to the level is outside, a NaN is outside.  Cell (i0,i1,i2) exists for
+ *   i_c < n_c - 1 and is cut into the six tetrahedra of the Kuhn triangulation: tetrahedron t belongs to the axis permutation (a,b,c),
+ *   in lexicographic order 012, 021, 102, 120, 201, 210, with vertices w0 = corner, w1 = w0 + e_a, w2 = w1 + e_b, w3 = corner + (1,1,1).
+ *   Every tetrahedron edge points in a non-negative direction and is OWNED by its lower endpoint; it has one of seven kinds
+ *   k = d0 + 2 d1 + 4 d2 - 1 for the offset (d0,d1,d2) in {0,1}^3 \ 0: three axis edges, three face diagonals, the body diagonal.  The
+ *   split is translation invariant, so neighbouring cells agree on every shared face diagonal: the mesh is watertight by construction and
+ *   there are no ambiguous cases, at 2-3 times the triangles of marching cubes.
+ * Vertices.  One per lattice edge (both ends in the lattice) whose ends differ in INSIDE, numbered by (owner's flat index
+ *   (i0 n1 + i1) n2 + i2 ascending, kind ascending).  Position in fp32, every operation rounded on its own, always from the owner P0 to
+ *   the other end P1:  t = (level - v0) / (v1 - v0),  pos_c = P0_c + t * (P1_c - P0_c);  t = 0.5 if either end's value is not finite.
+ *   attrs (n0,n1,n2,C), 1 <= C <= 8, are interpolated with the same t: a0 + t * (a1 - a0).
+ * Triangles.  Ordered by (cell flat index (i0 (n1-1) + i1) (n2-1) + i2 ascending, tetrahedron 0..5, triangle 0..1), each a triple of
+ *   vertex indices.  E(x,y) = the vertex on edge w_x w_y.  One vertex m alone on its side, the others p < q < r: (E(m,p), E(m,q), E(m,r)).
+ *   Two inside a < b, two outside c < d: the quad q0..q3 = E(a,c), E(a,d), E(b,d), E(b,c) as (q0,q1,q2) and (q0,q2,q3).  The last two
+ *   indices of a triangle are exchanged where needed so that its right-hand normal points from INSIDE to outside, toward falling values;
+ *   whether depends on (tetrahedron parity, 4-bit case) only.  Zero-area triangles occur where an outside corner equals the level; they
+ *   are kept, so the index structure stays closed.
+ *
+ *   cnerf_isosurface_bytes   workspace of a lattice: 9 bytes per point (the 8 INSIDE bits of a point and its forward neighbours, its
+ *                            vertex offset, its cell's triangle offset) and two sums per block of 256 points.
+ *   cnerf_isosurface_count   classifies every point and scans: counts = DEVICE int32[2] (vertices, triangles), workspace filled for emit.
+ *   cnerf_isosurface_emit    writes vertices (max_vertices,3), vertex_attrs (max_vertices,C) and triangles (max_triangles,3) int32 from the
+ *                            workspace as count left it (same lattice, values and level).  A row at or beyond a capacity is skipped, never
+ *                            written; rows the surface does not reach are left as they are.
+ * Both are asynchronous on `stream` and allocate nothing; the caller copies counts to the host between them, which is the only
+ * synchronisation.  Ballots, popcounts and one block's scan, no atomics, no block waits for another: two runs agree bit for bit.
+ * CNERF_EINVAL before any launch: an n_c outside [2,1024] or n0 n1 n2 > 2^27; values / counts / workspace / lo / vertices / triangles
+ * NULL; level, pitch or a lo[c] not finite, pitch <= 0; attrs given with n_attr outside [1,8]; attrs without vertex_attrs or the reverse;
+ * a negative capacity. */
+int cnerf_isosurface_bytes(int32_t n0, int32_t n1, int32_t n2, size_t* workspace);
+int cnerf_isosurface_count(int32_t n0, int32_t n1, int32_t n2, const float* values, float level,
+                           int32_t* counts /* DEVICE int32[2]: vertices, triangles */, void* workspace, void* stream);
+int cnerf_isosurface_emit(int32_t n0, int32_t n1, int32_t n2, const float* values, float level, const float lo[3], float pitch,
+                          const float* attrs /* (n0,n1,n2,C) or NULL */, int32_t n_attr,
+                          int64_t max_vertices, int64_t max_triangles,
+                          float* vertices /* (max_vertices,3) */, float* vertex_attrs /* (max_vertices,C) or NULL */,
+                          int32_t* triangles /* (max_triangles,3) */, const void* workspace /* as count left it */, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
