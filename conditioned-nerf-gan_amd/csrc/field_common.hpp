@@ -19,6 +19,94 @@ __device__ __forceinline__ f32x16 load_chan16(const float* __restrict__ p, int t
     return r;
 }
 
+// ---------------------------------------------------------------------------------------------------------------
+// Wave-uniform streams of the fp32 MFMA kernels (field_kernel.hip) through a buffer descriptor.  The A operands of a
+// matrix and its per-channel vectors are "wave-uniform base + lane part + compile-time (or scalar) offset": with the
+// base in a descriptor (4 SGPRs), the lane part in ONE constant VGPR and the rest in the scalar offset, a load needs no
+// vector address arithmetic at all -- the flat 64-bit form re-based a VGPR pointer pair every few loads (its immediate
+// reaches +-4 KiB), and every vector instruction between two fp32 MFMAs is paid in full (mlp_matrix's note).
+//
+// Invariant that makes the readfirstlane legal: every lane of a wave works on the same tile (tile_range hands tiles out
+// per WAVE), hence on the same image, hence holds the same base pointer -- the compiler only cannot prove it, because
+// the tile index comes from threadIdx.  All 64 lanes are active wherever a stream is built (the tile loops are
+// wave-uniform), so the first active lane's value is every lane's.
+// num_records is the real size of the matrix / vector.  What that protects is limited: on gfx9 / CDNA a raw buffer's range check
+// covers the vector offset plus the instruction's immediate only, NOT the scalar offset.  A lane part that runs past the records
+// (or a record count that is too small for it) returns zeros instead of foreign memory; the group index, which travels in the
+// scalar offset, is not checked at all -- a wrong group index reads whatever lies there, exactly as the flat load did.  The
+// group indices are compile-time constants, or (layer 0) scalar arithmetic on n_in and tk, bounded by the host's packing.
+// ---------------------------------------------------------------------------------------------------------------
+typedef unsigned int u32x4_vs __attribute__((vector_size(16)));     // the builtin's own result type
+
+__device__ __forceinline__ __amdgpu_buffer_rsrc_t uniform_rsrc(const void* p, unsigned bytes) {
+    const unsigned long long v = reinterpret_cast<unsigned long long>(p);
+    const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)v), hi = __builtin_amdgcn_readfirstlane((unsigned)(v >> 32));
+    return __builtin_amdgcn_make_buffer_rsrc(reinterpret_cast<void*>(((unsigned long long)hi << 32) | lo), 0, (int)bytes, 0x00020000);
+}
+
+// A descriptor costs 4 scalar registers (and one more per offset literal in flight).  The kernels whose scalar registers are
+// already spilled to vector lanes pay for them with a larger frame, so the choice is made per kernel family (BUF): the plain
+// forwards on folded weights and the per-point FiLM kernels stream through descriptors, the storing / dropout / residual forwards
+// and field_backward_kernel keep the flat addressing (BUF = false: the loads they always had, instruction for instruction).
+// profiles/field32_weight_stream.md has the table.
+//
+// packed A operands of one matrix: group i (64 lanes x float4 = 1 KiB, the operands of 4 consecutive k-steps) of `groups`
+template <bool BUF>
+struct WeightStream;
+template <>
+struct WeightStream<true> {
+    __amdgpu_buffer_rsrc_t rsrc;
+    int voff;                                    // lane * 16: the only vector part of every address
+    __device__ __forceinline__ WeightStream(const f32x4* __restrict__ wp, size_t groups, int lane)
+        : rsrc(uniform_rsrc(wp, (unsigned)groups * 1024u)), voff(lane * 16) {}
+    __device__ __forceinline__ f32x4 group(int i) const {       // i compile-time or wave-uniform: it travels in soffset
+        const u32x4_vs q = __builtin_amdgcn_raw_buffer_load_b128(rsrc, voff, i * 1024, 0);
+        return __builtin_bit_cast(f32x4, q);
+    }
+    // a runtime index (layer 0: (t * n_in + tk) * 4 + g).  It is narrowed to int and the byte offset i * 1024 is a 32-bit scalar:
+    // good for matrices below 2 GiB, i.e. 2^21 groups -- layer 0 has at most NT * n_in * 4 = 8 * 8 * 4 = 256 (FieldArgs::in_level
+    // holds 8 input tiles).
+    __device__ __forceinline__ f32x4 group_at(size_t i) const { return group((int)i); }
+};
+template <>
+struct WeightStream<false> {
+    const f32x4* __restrict__ wp;
+    int lane;
+    __device__ __forceinline__ WeightStream(const f32x4* __restrict__ wp_, size_t, int lane_) : wp(wp_), lane(lane_) {}
+    __device__ __forceinline__ f32x4 group(int i) const { return wp[i * 64 + lane]; }
+    __device__ __forceinline__ f32x4 group_at(size_t i) const { return *(wp + i * 64 + lane); }     // a runtime index: 64-bit arithmetic
+};
+
+// per-channel vector of `n` floats (bias, starting values, freq, phase, ...): load_chan16 through a descriptor.
+// The lane part is the half's 4 floats, the tile and group are compile-time.
+template <bool BUF>
+struct ChanStream;
+template <>
+struct ChanStream<false> {
+    const float* __restrict__ p;
+    int h;
+    __device__ __forceinline__ ChanStream(const float* __restrict__ p_, unsigned, int h_) : p(p_), h(h_) {}
+    __device__ __forceinline__ f32x16 tile(int t) const { return load_chan16(p, t, h); }
+};
+template <>
+struct ChanStream<true> {
+    __amdgpu_buffer_rsrc_t rsrc;
+    int voff;                                    // h * 16
+    __device__ __forceinline__ ChanStream(const float* __restrict__ p, unsigned n, int h) : rsrc(uniform_rsrc(p, n * 4u)), voff(h * 16) {}
+    __device__ __forceinline__ f32x16 tile(int t) const {
+        f32x16 r;
+#pragma unroll
+        for (int g = 0; g < 4; ++g) {
+            const f32x4 q = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rsrc, voff, (32 * t + 8 * g) * 4, 0));
+            r[4 * g + 0] = q[0];
+            r[4 * g + 1] = q[1];
+            r[4 * g + 2] = q[2];
+            r[4 * g + 3] = q[3];
+        }
+        return r;
+    }
+};
+
 
 // ---------------------------------------------------------------------------------------------------------------
 // Layer-0 input tiles.  The input of layer 0 is a runtime list of 32-wide tiles: 32 channels of one pyramid level's

@@ -144,7 +144,7 @@ __device__ __forceinline__ void store_tile_rows(float* __restrict__ row /* &buf[
 // full 2 cycles whether spread between the MFMAs or clumped, with one or two accumulator chains -- so for the fp32
 // path  time = MFMA + VALU + stalls  and the epilogue placement only matters for register pressure and load distance.
 // DROP: the finished tile (and its cosine row) is multiplied by the dropout factors of layer `drop_d` at point `drop_gp`.
-template <int OT, int KT, int EPI, bool STORE, bool DROP = false, bool FOLD = false, int WFOLD = 0>
+template <int OT, int KT, int EPI, bool STORE, bool DROP = false, bool FOLD = false, int WFOLD = 0, bool BUF = false>
 __device__ __forceinline__ void mlp_matrix(const f32x4* __restrict__ wp, const float* __restrict__ bias,
                                            const float* __restrict__ freq, const float* __restrict__ phase,
                                            const f32x16* in, const f32x16* res, f32x16* out, int lane, int h,
@@ -155,28 +155,30 @@ __device__ __forceinline__ void mlp_matrix(const f32x4* __restrict__ wp, const f
     constexpr int NG = OT * GPT;
     constexpr int EPG = GPT >= 16 ? 1 : 16 / GPT;     // epilogue elements handled per group
     constexpr int ESTEP = GPT >= 16 ? GPT / 16 : 1;   // ... every ESTEP-th group
+    const WeightStream<BUF> ws(wp, NG, lane);         // BUF: no vector address arithmetic between the MFMAs (field_common.hpp)
+    const ChanStream<BUF> bias_s(bias, OT * 32, h), freq_s(freq, OT * 32, h), phase_s(phase, OT * 32, h), ml_s(fold_ml, OT * 32, h);   // (unused ones cost nothing)
     f32x4 ring[RING];
 #pragma unroll
     for (int i = 0; i < RING; ++i)
-        if (i < NG) ring[i] = wp[i * 64 + lane];
+        if (i < NG) ring[i] = ws.group(i);
     f32x16 acc_prev, fr_prev, ph_prev, ml_prev, cos_t;
-    f32x16 bias_next = load_chan16(bias, 0, h);       // per-channel vectors are fetched one output tile ahead
+    f32x16 bias_next = bias_s.tile(0);                // per-channel vectors are fetched one output tile ahead
 #pragma unroll
     for (int t = 0; t < OT; ++t) {
         f32x16 acc = bias_next;
-        if (t + 1 < OT) bias_next = load_chan16(bias, t + 1, h);
+        if (t + 1 < OT) bias_next = bias_s.tile(t + 1);
         f32x16 fr, ph, ml;
         if (!WFOLD) {
-            fr = load_chan16(freq, t, h);
-            ph = load_chan16(phase, t, h);
+            fr = freq_s.tile(t);
+            ph = phase_s.tile(t);
         }
-        if (FOLD && !WFOLD) ml = load_chan16(fold_ml, t, h);
+        if (FOLD && !WFOLD) ml = ml_s.tile(t);
 #pragma unroll
         for (int gi = 0; gi < GPT; ++gi) {
             const int tk = gi >> 2, g = gi & 3;
             const int idx = t * GPT + gi;
             const f32x4 a = ring[idx % RING];
-            if (idx + RING < NG) ring[idx % RING] = wp[(idx + RING) * 64 + lane];
+            if (idx + RING < NG) ring[idx % RING] = ws.group(idx + RING);
 #pragma unroll
             for (int e = 0; e < 4; ++e)
                 acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a[e], in[tk][4 * g + e], acc, 0, 0, 0);
@@ -230,20 +232,21 @@ __device__ __forceinline__ void mlp_matrix(const f32x4* __restrict__ wp, const f
 
 
 // y[t] += W0[t, tile tk] * feat   for all NT output tiles (k-outer form of layer 0: any number of input tiles)
-template <int NT>
+template <int NT, bool BUF>
 __device__ __forceinline__ void layer0_accumulate(const f32x4* __restrict__ wp, int n_in, int tk, const f32x16& feat,
                                                   f32x16* y, int lane) {
     constexpr int NG = NT * 4;
-    auto addr = [&](int i) { return wp + ((size_t)((i >> 2) * n_in + tk) * 4 + (i & 3)) * 64 + lane; };
+    const WeightStream<BUF> ws(wp, (size_t)NG * n_in, lane);
+    auto load = [&](int i) { return ws.group_at((size_t)((i >> 2) * n_in + tk) * 4 + (i & 3)); };      // n_in, tk: scalars -- BUF: the group index is SALU work
     f32x4 ring[RING];
 #pragma unroll
     for (int i = 0; i < RING; ++i)
-        if (i < NG) ring[i] = *addr(i);
+        if (i < NG) ring[i] = load(i);
 #pragma unroll
     for (int i = 0; i < NG; ++i) {
         const int t = i >> 2, g = i & 3;
         const f32x4 aw = ring[i % RING];
-        if (i + RING < NG) ring[i % RING] = *addr(i + RING);
+        if (i + RING < NG) ring[i % RING] = load(i + RING);
 #pragma unroll
         for (int e = 0; e < 4; ++e) y[t] = __builtin_amdgcn_mfma_f32_32x32x2f32(aw[e], feat[4 * g + e], y[t], 0, 0, 0);
         __builtin_amdgcn_sched_barrier(0);
@@ -251,25 +254,26 @@ __device__ __forceinline__ void layer0_accumulate(const f32x4* __restrict__ wp, 
 }
 
 // x[t] = sin(freq * y[t] + phase) for all tiles (+ activation store)
-template <int NT, bool STORE, bool DROP = false, bool FOLD = false, int WFOLD = 0>
+template <int NT, bool STORE, bool DROP = false, bool FOLD = false, int WFOLD = 0, bool BUF = false>
 __device__ __forceinline__ void film_all(const f32x16* y, f32x16* x, const float* __restrict__ freq,
                                          const float* __restrict__ phase, int h, float* row_h, float* row_c,
                                          const FieldArgs* da = nullptr, unsigned long long drop_gp = 0,
                                          const float* __restrict__ fold_ml = nullptr) {
-    f32x16 fr_n = load_chan16(freq, 0, h), ph_n = load_chan16(phase, 0, h);      // per-channel vectors one tile ahead of their use
+    const ChanStream<BUF> freq_s(freq, NT * 32, h), phase_s(phase, NT * 32, h), ml_s(fold_ml, NT * 32, h);
+    f32x16 fr_n = freq_s.tile(0), ph_n = phase_s.tile(0);      // per-channel vectors one tile ahead of their use
 #pragma unroll
     for (int t = 0; t < NT; ++t) {
         const f32x16 fr = fr_n, ph = ph_n;
         if (t + 1 < NT) {
-            fr_n = load_chan16(freq, t + 1, h);
-            ph_n = load_chan16(phase, t + 1, h);
+            fr_n = freq_s.tile(t + 1);
+            ph_n = phase_s.tile(t + 1);
         }
         f32x16 o, cs;
         if (WFOLD) {
 #pragma unroll
             for (int r = 0; r < 16; ++r) o[r] = wfolded_sine<WFOLD>(y[t][r]);
         } else if (FOLD) {
-            const f32x16 ml = load_chan16(fold_ml, t, h);
+            const f32x16 ml = ml_s.tile(t);
 #pragma unroll
             for (int r = 0; r < 16; ++r) o[r] = folded_sine(y[t][r], fr[r], ml[r], ph[r]);
         } else {
@@ -334,6 +338,9 @@ __global__ __launch_bounds__(256) void field_tile_kernel(FieldArgs a) {
     const int j = lane & 31, h = lane >> 5;
     constexpr int H = NT * 32;
     constexpr size_t TILE4 = 4 * 64;   // float4 per (t, tk) pair
+    // weights and per-channel vectors through buffer descriptors (field_common.hpp): the plain forwards on folded weights.  In the
+    // storing, dropout and residual instantiations the descriptors' scalar registers enlarge the frame: those keep the flat loads.
+    constexpr bool BUF = WFOLD != 0 && !HAS_RES;
 
     // The head's weights (4x4x1 MFMA layout: NT*4 float4 per lane) are read in full by every wave for every tile -- as many
     // bytes as the lookups.  They are parked in LDS once per block instead of streamed from L2 once per tile.
@@ -344,7 +351,11 @@ __global__ __launch_bounds__(256) void field_tile_kernel(FieldArgs a) {
         __syncthreads();
     }
 
-    const TileRange tr = tile_range(a.total_tiles);
+    TileRange tr = tile_range(a.total_tiles);
+    if constexpr (BUF) {       // the wave's first tile in scalar registers: the tile loop, the image index and its division leave the vector ALUs
+        const unsigned long long bv = (unsigned long long)tr.begin;      // (wave-uniform: tile_range() derives it from threadIdx.x >> 6)
+        tr.begin = (long long)(((unsigned long long)__builtin_amdgcn_readfirstlane((unsigned)(bv >> 32)) << 32) | __builtin_amdgcn_readfirstlane((unsigned)bv));
+    }
     auto point_of = [&](long long tile, int& b_, long long& nn_, bool& valid_) {
         b_ = (int)(tile / a.tiles_per_image);
         const long long n = (tile - (long long)b_ * a.tiles_per_image) * 32 + j;  // point index inside image b
@@ -404,7 +415,7 @@ __global__ __launch_bounds__(256) void field_tile_kernel(FieldArgs a) {
             for (int g = 1; g < 4; ++g) *reinterpret_cast<f32x4*>(fo + 8 * g) = f32x4{0.f, 0.f, 0.f, 0.f};
         }
 #pragma unroll
-        for (int t = 0; t < NT; ++t) y.v[t] = load_chan16(bias, t, h);
+        for (int t = 0; t < NT; ++t) y.v[t] = ChanStream<BUF>(bias, H, h).tile(t);
         if constexpr (NOVOL) {
             layer0_xyz<NT>(wp, px, py, pz, y.v, h);
         } else
@@ -420,11 +431,11 @@ __global__ __launch_bounds__(256) void field_tile_kernel(FieldArgs a) {
                     *reinterpret_cast<f32x4*>(fo + 8 * g) = q;
                 }
             }
-            layer0_accumulate<NT>(wp, a.n_in, tk, feat, y.v, lane);
+            layer0_accumulate<NT, BUF>(wp, a.n_in, tk, feat, y.v, lane);
         }
         {
             const bool film = a.layer_kind[0] == CNERF_LAYER_FILM;
-            film_all<NT, STORE, DROP, FOLD, WFOLD>(y.v, x.v, (FOLD || film) ? freq : ones, (FOLD || film) ? phase : zeros, h, row_h, row_c, &a, drop_gp, fml);
+            film_all<NT, STORE, DROP, FOLD, WFOLD, BUF>(y.v, x.v, (FOLD || film) ? freq : ones, (FOLD || film) ? phase : zeros, h, row_h, row_c, &a, drop_gp, fml);
             if (STORE) {
                 row_h += act_layer;
                 row_c += act_layer;
@@ -443,7 +454,7 @@ __global__ __launch_bounds__(256) void field_tile_kernel(FieldArgs a) {
             if (!HAS_RES || kind != CNERF_LAYER_RES) {
                 const bool film = kind == CNERF_LAYER_FILM;
                 ++drop_d;
-                mlp_matrix<NT, NT, EPI_FILM, STORE, DROP, FOLD, WFOLD>(wp, bias, (FOLD || film) ? freq : ones, (FOLD || film) ? phase : zeros, x.v,
+                mlp_matrix<NT, NT, EPI_FILM, STORE, DROP, FOLD, WFOLD, BUF>(wp, bias, (FOLD || film) ? freq : ones, (FOLD || film) ? phase : zeros, x.v,
                                                                        nullptr, y.v, lane, h, row_h, row_c, &a, drop_gp, drop_d, fml);
                 if (STORE) {
                     row_h += act_layer;
@@ -461,7 +472,7 @@ __global__ __launch_bounds__(256) void field_tile_kernel(FieldArgs a) {
                 asm volatile("" :: "v"(x.v[0][0]), "v"(x.v[NT - 1][15]));
             } else {
                 // y = sin(W1 x + b1);  x = sin(x + W2 y + b2)   (tile t of x is dead once its own residual is added)
-                mlp_matrix<NT, NT, EPI_FILM, STORE, false, FOLD, WFOLD>(wp, bias, FOLD ? freq : ones, FOLD ? phase : zeros, x.v, nullptr, y.v, lane, h,
+                mlp_matrix<NT, NT, EPI_FILM, STORE, false, FOLD, WFOLD, BUF>(wp, bias, FOLD ? freq : ones, FOLD ? phase : zeros, x.v, nullptr, y.v, lane, h,
                                                                         row_h, row_c, nullptr, 0, 0, fml);
                 if (STORE) {
                     row_h += act_layer;
@@ -474,7 +485,7 @@ __global__ __launch_bounds__(256) void field_tile_kernel(FieldArgs a) {
                     phase += H;
                     fml += H;
                 }
-                mlp_matrix<NT, NT, EPI_FILM_RES, STORE, false, FOLD, WFOLD>(wp, bias, FOLD ? freq : ones, FOLD ? phase : zeros, y.v, x.v, x.v, lane, h,
+                mlp_matrix<NT, NT, EPI_FILM_RES, STORE, false, FOLD, WFOLD, BUF>(wp, bias, FOLD ? freq : ones, FOLD ? phase : zeros, y.v, x.v, x.v, lane, h,
                                                                             row_h, row_c, nullptr, 0, 0, fml);
                 if (FOLD) {
                     freq += H;
@@ -540,15 +551,16 @@ __global__ __launch_bounds__(256) void field_tile_kernel(FieldArgs a) {
 template <int KT>
 __device__ __forceinline__ f32x16 mfma_accumulate(const f32x4* __restrict__ wp, const f32x16* in, f32x16 acc, int lane) {
     constexpr int NG = KT * 4;
+    const WeightStream<true> ws(wp, NG, lane);
     f32x4 ring[RING];
 #pragma unroll
     for (int i = 0; i < RING; ++i)
-        if (i < NG) ring[i] = wp[i * 64 + lane];
+        if (i < NG) ring[i] = ws.group(i);
 #pragma unroll
     for (int i = 0; i < NG; ++i) {
         const int tk = i >> 2, g = i & 3;
         const f32x4 aw = ring[i % RING];
-        if (i + RING < NG) ring[i % RING] = wp[(i + RING) * 64 + lane];
+        if (i + RING < NG) ring[i % RING] = ws.group(i + RING);
 #pragma unroll
         for (int e = 0; e < 4; ++e) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(aw[e], in[tk][4 * g + e], acc, 0, 0, 0);
         __builtin_amdgcn_sched_barrier(0);
@@ -564,11 +576,12 @@ __device__ __forceinline__ void pfilm_layer(const f32x4* __restrict__ w_main, co
                                             float* __restrict__ row_y, float* __restrict__ row_c, size_t slab,
                                             const FieldArgs& a, unsigned long long drop_gp, int drop_d) {
     constexpr size_t TILE4 = 4 * 64;
+    const ChanStream<true> bm_s(b_main, NT * 32, h), bf_s(b_freq, NT * 32, h), bp_s(b_phase, NT * 32, h);
 #pragma unroll
     for (int t = 0; t < NT; ++t) {
-        f32x16 fr = mfma_accumulate<8>(w_freq + (size_t)t * 8 * TILE4, m, load_chan16(b_freq, t, h), lane);
-        f32x16 ph = mfma_accumulate<8>(w_phase + (size_t)t * 8 * TILE4, m, load_chan16(b_phase, t, h), lane);
-        f32x16 pre = mfma_accumulate<KT>(w_main + (size_t)t * KT * TILE4, x, load_chan16(b_main, t, h), lane);
+        f32x16 fr = mfma_accumulate<8>(w_freq + (size_t)t * 8 * TILE4, m, bf_s.tile(t), lane);
+        f32x16 ph = mfma_accumulate<8>(w_phase + (size_t)t * 8 * TILE4, m, bp_s.tile(t), lane);
+        f32x16 pre = mfma_accumulate<KT>(w_main + (size_t)t * KT * TILE4, x, bm_s.tile(t), lane);
         f32x16 o;
         if (STORE) {
             f32x16 cs, cf, cp;
@@ -631,8 +644,8 @@ __global__ __launch_bounds__(256) void field_pw_kernel(FieldArgs a) {
             const f32x16 feat = input_tile(a, b, 0, px, py, pz, h);
             if (st) store_tile_rows(a.act_feat + gpt * 32, 0, h, feat);
 #pragma unroll
-            for (int t = 0; t < 8; ++t) m.v[t] = load_chan16(bias, t, h);
-            layer0_accumulate<8>(wp, 1, 0, feat, m.v, lane);
+            for (int t = 0; t < 8; ++t) m.v[t] = ChanStream<true>(bias, 256, h).tile(t);
+            layer0_accumulate<8, true>(wp, 1, 0, feat, m.v, lane);
 #pragma unroll
             for (int t = 0; t < 8; ++t)
 #pragma unroll
@@ -703,14 +716,15 @@ __global__ __launch_bounds__(256) void field_pw_kernel(FieldArgs a) {
 //   atomic units run at full rate for: MI355X_MICROARCH.md "Global float atomics").
 // The same chaining as the forward applies: the accumulator registers of g_h are the B operands of the next product.
 // ---------------------------------------------------------------------------------------------------------------
-template <int OT, int KT>
+template <int OT, int KT, bool BUF>
 __device__ __forceinline__ void bwd_matrix(const f32x4* __restrict__ wp, const f32x16* in, f32x16* out, int lane) {
     constexpr int GPT = KT * 4;
     constexpr int NG = OT * GPT;
+    const WeightStream<BUF> ws(wp, NG, lane);
     f32x4 ring[RING];
 #pragma unroll
     for (int i = 0; i < RING; ++i)
-        if (i < NG) ring[i] = wp[i * 64 + lane];
+        if (i < NG) ring[i] = ws.group(i);
 #pragma unroll
     for (int t = 0; t < OT; ++t) {
         f32x16 acc;
@@ -721,7 +735,7 @@ __device__ __forceinline__ void bwd_matrix(const f32x4* __restrict__ wp, const f
             const int tk = gi >> 2, g = gi & 3;
             const int idx = t * GPT + gi;
             const f32x4 a = ring[idx % RING];
-            if (idx + RING < NG) ring[idx % RING] = wp[(idx + RING) * 64 + lane];
+            if (idx + RING < NG) ring[idx % RING] = ws.group(idx + RING);
 #pragma unroll
             for (int e = 0; e < 4; ++e)
                 acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a[e], in[tk][4 * g + e], acc, 0, 0, 0);
@@ -835,7 +849,7 @@ __global__ __launch_bounds__(256) void field_pw_backward_kernel(FieldArgs a) {
                 g.v[t] = gpre;
             }
             if (l > 0) {
-                bwd_matrix<NT, NT>(wp, g.v, g2.v, lane);
+                bwd_matrix<NT, NT, true>(wp, g.v, g2.v, lane);
                 wp += (size_t)NT * NT * TILE4;
 #pragma unroll
                 for (int t = 0; t < NT; ++t) g.v[t] = g2.v[t];
@@ -880,11 +894,11 @@ __global__ __launch_bounds__(256) void field_backward_kernel(FieldArgs a) {
                 // y = sin(W1 x + b1) [slab sub-1];  x' = sin(x + W2 y + b2) [slab sub]
                 float* row_gb = a.act_g + (size_t)sub * act_layer + gpt * H;
                 bwd_activation<NT>(g.v, a.act_c + (size_t)sub * act_layer + gpt * H, row_gb, ones, h, valid);  // g = g_arg_b
-                bwd_matrix<NT, NT>(wp, g.v, g2.v, lane);                                                       // g2 = W2^T g_arg_b
+                bwd_matrix<NT, NT, false>(wp, g.v, g2.v, lane);                                                // g2 = W2^T g_arg_b
                 wp += (size_t)NT * NT * TILE4;
                 bwd_activation<NT>(g2.v, a.act_c + (size_t)(sub - 1) * act_layer + gpt * H,
                                    a.act_g + (size_t)(sub - 1) * act_layer + gpt * H, ones, h, valid);         // g2 = g_arg_a
-                bwd_matrix<NT, NT>(wp, g2.v, g.v, lane);                                                       // g = W1^T g_arg_a
+                bwd_matrix<NT, NT, false>(wp, g2.v, g.v, lane);                                                // g = W1^T g_arg_a
                 wp += (size_t)NT * NT * TILE4;
 #pragma unroll
                 for (int t = 0; t < NT; ++t) {       // + the identity path: g_arg_b, re-read from the rows this lane just wrote
@@ -904,7 +918,7 @@ __global__ __launch_bounds__(256) void field_backward_kernel(FieldArgs a) {
             bwd_activation<NT>(g.v, a.act_c + (size_t)sub * act_layer + gpt * H, a.act_g + (size_t)sub * act_layer + gpt * H, fr, h, valid);
             --sub;
             if (l > 0) {
-                bwd_matrix<NT, NT>(wp, g.v, g2.v, lane);
+                bwd_matrix<NT, NT, false>(wp, g.v, g2.v, lane);
                 wp += (size_t)NT * NT * TILE4;
 #pragma unroll
                 for (int t = 0; t < NT; ++t) g.v[t] = g2.v[t];
@@ -919,7 +933,7 @@ __global__ __launch_bounds__(256) void field_backward_kernel(FieldArgs a) {
                 const int lvl = a.in_level[tk];
                 if (lvl < 0) continue;                              // no gradient flows to the sample positions
                 f32x16 gfeat;
-                bwd_matrix<1, NT>(wp + (size_t)tk * NT * TILE4, g.v, &gfeat, lane);
+                bwd_matrix<1, NT, false>(wp + (size_t)tk * NT * TILE4, g.v, &gfeat, lane);
                 const int V = a.lvl_V[lvl], C = a.lvl_C[lvl];
                 Corner8 cr;
                 trilinear_corners(px, py, pz, a.half_voxel, V, cr);
