@@ -143,6 +143,10 @@ __device__ __forceinline__ void store_tile_rows(float* __restrict__ row /* &buf[
 // scripts/ubench/mfma_valu_overlap.hip): VALU instructions do NOT hide under v_mfma_f32_32x32x2_f32 -- each adds its
 // full 2 cycles whether spread between the MFMAs or clumped, with one or two accumulator chains -- so for the fp32
 // path  time = MFMA + VALU + stalls  and the epilogue placement only matters for register pressure and load distance.
+// Which instantiations run this: the storing, dropout, unfolded and folded-constants forwards and every residual network.  The
+// epilogue of tile t-1 under the MFMAs of tile t keeps `in` live while `out` is produced, so the layer loop copies `out` back
+// (x = y); the plain forwards on folded weights without residual blocks (BUF && !STORE && !DROP in field_tile_kernel) run
+// hidden_matrix_inplace below instead, which activates behind the last MFMA and needs no copy.
 // DROP: the finished tile (and its cosine row) is multiplied by the dropout factors of layer `drop_d` at point `drop_gp`.
 template <int OT, int KT, int EPI, bool STORE, bool DROP = false, bool FOLD = false, int WFOLD = 0, bool BUF = false>
 __device__ __forceinline__ void mlp_matrix(const f32x4* __restrict__ wp, const float* __restrict__ bias,
@@ -253,12 +257,69 @@ __device__ __forceinline__ void layer0_accumulate(const f32x4* __restrict__ wp, 
     }
 }
 
+// WFOLD: x[t] = sin(2 pi y[t]) for all tiles -- y holds the arguments in revolutions (wfolded_sine above).  The activation
+// pass of layer 0 (film_all) and of hidden_matrix_inplace: y is dead behind it, tile by tile.
+template <int NT, int WFOLD>
+__device__ __forceinline__ void wfolded_activate(const f32x16* y, f32x16* x) {
+#pragma unroll
+    for (int t = 0; t < NT; ++t) {
+        f32x16 o;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) o[r] = wfolded_sine<WFOLD>(y[t][r]);
+        x[t] = o;
+        __builtin_amdgcn_sched_barrier(0);
+    }
+}
+
+// One hidden H x H matrix of a plain forward on folded weights (WFOLD, no store, no dropout, no residual), activated in
+// place:  y = K + W' x  with the accumulator of output tile t being y[t] itself, then  x = sin(2 pi y)  behind the last
+// MFMA, where x is dead -- the activation is written straight into the next matrix's B operands and nothing is copied.
+// mlp_matrix runs the epilogue of tile t-1 under the MFMAs of tile t, which keeps x live while activations are produced and
+// so needs a second array and a copy back; since vector instructions cost the same wherever they stand between fp32 MFMAs
+// (mlp_matrix's note), placing them behind the matrix loses nothing.  Weight ring (RING groups ahead, restarted per matrix),
+// descriptors, the starting values one tile ahead and the barrier per group are mlp_matrix's; so is the order of every MFMA
+// chain and the activation arithmetic: the outputs are bit-identical.
+template <int NT, int WFOLD, bool BUF>
+__device__ __forceinline__ void hidden_matrix_inplace(const f32x4* __restrict__ wp, const float* __restrict__ start,
+                                                      f32x16* x, f32x16* y, int lane, int h) {
+    constexpr int GPT = NT * 4;                       // groups (of 4 MFMAs) per output tile
+    constexpr int NG = NT * GPT;
+    const WeightStream<BUF> ws(wp, NG, lane);
+    const ChanStream<BUF> start_s(start, NT * 32, h);
+    f32x4 ring[RING];
+#pragma unroll
+    for (int i = 0; i < RING; ++i)
+        if (i < NG) ring[i] = ws.group(i);
+    y[0] = start_s.tile(0);
+#pragma unroll
+    for (int t = 0; t < NT; ++t) {
+        if (t + 1 < NT) y[t + 1] = start_s.tile(t + 1);       // the starting values are fetched one output tile ahead
+#pragma unroll
+        for (int gi = 0; gi < GPT; ++gi) {
+            const int tk = gi >> 2, g = gi & 3;
+            const int idx = t * GPT + gi;
+            const f32x4 a = ring[idx % RING];
+            if (idx + RING < NG) ring[idx % RING] = ws.group(idx + RING);
+#pragma unroll
+            for (int e = 0; e < 4; ++e)
+                y[t] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[e], x[tk][4 * g + e], y[t], 0, 0, 0);
+            __builtin_amdgcn_sched_barrier(0);
+        }
+    }
+    wfolded_activate<NT, WFOLD>(y, x);
+}
+
 // x[t] = sin(freq * y[t] + phase) for all tiles (+ activation store)
 template <int NT, bool STORE, bool DROP = false, bool FOLD = false, int WFOLD = 0, bool BUF = false>
 __device__ __forceinline__ void film_all(const f32x16* y, f32x16* x, const float* __restrict__ freq,
                                          const float* __restrict__ phase, int h, float* row_h, float* row_c,
                                          const FieldArgs* da = nullptr, unsigned long long drop_gp = 0,
                                          const float* __restrict__ fold_ml = nullptr) {
+    if constexpr (WFOLD != 0) {       // (never with STORE or DROP: launch_field_nt)
+        static_assert(!STORE && !DROP, "folded weights: plain forwards only");
+        wfolded_activate<NT, WFOLD>(y, x);
+        return;
+    }
     const ChanStream<BUF> freq_s(freq, NT * 32, h), phase_s(phase, NT * 32, h), ml_s(fold_ml, NT * 32, h);
     f32x16 fr_n = freq_s.tile(0), ph_n = phase_s.tile(0);      // per-channel vectors one tile ahead of their use
 #pragma unroll
@@ -269,10 +330,7 @@ __device__ __forceinline__ void film_all(const f32x16* y, f32x16* x, const float
             ph_n = phase_s.tile(t + 1);
         }
         f32x16 o, cs;
-        if (WFOLD) {
-#pragma unroll
-            for (int r = 0; r < 16; ++r) o[r] = wfolded_sine<WFOLD>(y[t][r]);
-        } else if (FOLD) {
+        if (FOLD) {
             const f32x16 ml = ml_s.tile(t);
 #pragma unroll
             for (int r = 0; r < 16; ++r) o[r] = folded_sine(y[t][r], fr[r], ml[r], ph[r]);
@@ -450,8 +508,14 @@ __global__ __launch_bounds__(256) void field_tile_kernel(FieldArgs a) {
         }
         asm volatile("" :: "v"(x.v[0][0]), "v"(x.v[NT - 1][15]));
         for (int l = 1; l < a.L; ++l) {
-            const int kind = a.layer_kind[l];
-            if (!HAS_RES || kind != CNERF_LAYER_RES) {
+            [[maybe_unused]] const int kind = a.layer_kind[l];
+            if constexpr (BUF && !STORE && !DROP) {
+                // plain forward on folded weights: y = K + W' x, x = sin(2 pi y) in place -- no second activation array to copy back
+                hidden_matrix_inplace<NT, WFOLD, BUF>(wp, bias, x.v, y.v, lane, h);
+                wp += (size_t)NT * NT * TILE4;
+                bias += H;
+                asm volatile("" :: "v"(x.v[0][0]), "v"(x.v[NT - 1][15]));
+            } else if (!HAS_RES || kind != CNERF_LAYER_RES) {
                 const bool film = kind == CNERF_LAYER_FILM;
                 ++drop_d;
                 mlp_matrix<NT, NT, EPI_FILM, STORE, DROP, FOLD, WFOLD, BUF>(wp, bias, (FOLD || film) ? freq : ones, (FOLD || film) ? phase : zeros, x.v,
