@@ -336,6 +336,25 @@ struct IsoEmitArgs {
 hipError_t launch_iso_count(const IsoCountArgs& a, hipStream_t stream);
 hipError_t launch_iso_emit(const IsoEmitArgs& a, hipStream_t stream);
 
+// nearest.hip: exact nearest target of every query, brute force (include/cnerf.h states the contract, DESIGN.md 3.20 the tiling)
+constexpr int NN_QPT = 4;                    // queries a lane owns in registers
+constexpr int NN_QUERIES = NN_QPT * 64;      // queries of a block (one wave): cnerf_nearest_points_tiling's queries_per_block
+constexpr int NN_TILE = 16;                  // targets a wave holds in scalar registers at a time: its targets_per_tile
+struct NearestArgs {
+    int B;
+    long long n, m;
+    int splits;                // >= 1: ranges the targets of an image are cut into
+    const float* queries;      // (B,n,3)
+    const float* targets;      // (B,m,3)
+    const int32_t* n_queries;  // (B) or null
+    const int32_t* n_targets;  // (B) or null
+    float* dist2;              // (B,n)
+    int32_t* idx;              // (B,n)
+    float* part_d;             // (B,splits,n), splits > 1 only
+    int32_t* part_j;           // (B,splits,n), splits > 1 only
+};
+hipError_t launch_nearest_points(const NearestArgs& a, hipStream_t stream);
+
 hipError_t launch_philox_fill(const PhiloxKey& k, uint32_t stream_id, long long n, int normal, float* out, hipStream_t stream);
 hipError_t launch_transpose_cl(int B, int C, int V, const float* src, float* dst, bool to_channel_last, hipStream_t stream);
 

@@ -803,6 +803,47 @@ def isosurface(values, level, lo=(0.0, 0.0, 0.0), pitch=1.0, attrs=None):
     return vertices, faces, vertex_attrs
 
 
+def _cloud_lengths(lengths, B, dev, what):
+    """Per-image lengths of a padded cloud -> contiguous int32 (B,) on `dev`, or None."""
+    if lengths is None:
+        return None
+    lengths = torch.as_tensor(lengths).detach().to(device=dev, dtype=torch.int32).contiguous()
+    if tuple(lengths.shape) != (B,):
+        raise L.CnerfError(f"nearest_points: {what} must be ({B},), got {tuple(lengths.shape)}")
+    return lengths
+
+
+def nearest_points(queries, targets, query_lengths=None, target_lengths=None, target_splits=0):
+    """cnerf_nearest_points: for every query the nearest target of the same image, exactly (brute force; include/cnerf.h states the
+    arithmetic, the lowest-index tie rule and the treatment of non-finite values).  queries (B,n,3), targets (B,m,3); query_lengths /
+    target_lengths (B,) say how many leading rows of each image count (clamped to [0,n] / [0,m]; None: all).
+    -> dist2 (B,n) float32 squared distances, idx (B,n) int32; (+inf, -1) where no target can be chosen and in rows beyond the length.
+    (n,3) and (m,3) are taken as one image and returned without the batch axis.  target_splits: 0 lets the library choose; the result
+    does not depend on it.  Inputs are detached: shape_metrics.chamfer_distance is the differentiable form."""
+    queries, targets = _f32(queries.detach()), _f32(targets.detach())
+    single = queries.dim() == 2 and targets.dim() == 2
+    if single:
+        queries, targets = queries.unsqueeze(0), targets.unsqueeze(0)
+    if queries.dim() != 3 or targets.dim() != 3 or queries.shape[-1] != 3 or targets.shape[-1] != 3 or queries.shape[0] != targets.shape[0]:
+        raise L.CnerfError(f"nearest_points: queries and targets must be (B,n,3) and (B,m,3) (or (n,3) and (m,3)), got {tuple(queries.shape)} "
+                           f"and {tuple(targets.shape)}")
+    if targets.device != queries.device:
+        raise L.CnerfError("nearest_points: queries and targets must be on the same device")
+    B, n, m = int(queries.shape[0]), int(queries.shape[1]), int(targets.shape[1])
+    dev = queries.device
+    nq = _cloud_lengths(query_lengths, B, dev, "query_lengths")
+    mt = _cloud_lengths(target_lengths, B, dev, "target_lengths")
+    lib = L.lib()
+    nb = C.c_size_t(0)
+    L.check(lib.cnerf_nearest_points_bytes(B, n, m, int(target_splits), C.byref(nb)), "cnerf_nearest_points_bytes")
+    ws = torch.empty(nb.value, dtype=torch.uint8, device=dev) if nb.value else None
+    dist2 = torch.empty((B, n), dtype=torch.float32, device=dev)
+    idx = torch.empty((B, n), dtype=torch.int32, device=dev)
+    L.check(lib.cnerf_nearest_points(B, n, m, L.ptr(queries), L.ptr(targets), L.ptr(nq), L.ptr(mt), int(target_splits), L.ptr(dist2), L.ptr(idx),
+                                     L.ptr(ws), _stream()), "cnerf_nearest_points")
+    return (dist2[0], idx[0]) if single else (dist2, idx)
+
+
 def render_rays_forward(net, levels, freq, phase, origins, dirs, o, rng=None, want_aux=False, aux_keys=None, occupancy=None, near=None, far=None):
     """cnerf_render_rays_forward on channel-last levels: origins / dirs (B,P,3) -> pixels (B,P,3), dist (B,P), aux dict.
     occupancy (an OccupancyGrid with one grid per image): cnerf_render_rays_masked_forward instead -- samples in cells whose bit is

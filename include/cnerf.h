@@ -675,6 +675,37 @@ int cnerf_isosurface_emit(int32_t n0, int32_t n1, int32_t n2, const float* value
                           float* vertices /* (max_vertices,3) */, float* vertex_attrs /* (max_vertices,C) or NULL */,
                           int32_t* triangles /* (max_triangles,3) */, const void* workspace /* as count left it */, void* stream);
 
+/* ---- nearest points: the nearest target of every query, between two batched clouds (added in ABI v10 without a version change:
+ * additive symbols only) --------------------------------------------------------------------------------------------------------------
+ * The primitive under the Chamfer distance and the F-score of a reconstruction (shape_metrics.py).  The search is exact and brute force:
+ * every query meets every target of its image, nothing n x m is stored.  The arithmetic and the tie rule are fixed here so that the
+ * result can be checked bit for bit.
+ *
+ * Distance.  Query q, target t, fp32, every operation rounded on its own, no fma:
+ *     dx = qx - tx, dy = qy - ty, dz = qz - tz,    d = (dx*dx + dy*dy) + dz*dz.
+ * Result.  Per image b: nq = clamp(n_queries[b], 0, n), mt = clamp(n_targets[b], 0, m); a NULL length array stands for n (m).
+ *   For query i < nq: idx[b,i] = the SMALLEST j < mt whose d is minimal among the d that are finite, dist2[b,i] = that d.  A d that is
+ *   NaN or +inf is never chosen: a NaN or an infinity in either point, or an overflow of the sum.  No target chosen (mt == 0 included):
+ *   dist2 = +inf, idx = -1.  Rows i >= nq are written as (+inf, -1) without a search.  Every element of both outputs is written.
+ * Reproducibility.  The outputs do not depend on target_splits, on the launch geometry or on the run; there are no atomics.
+ * target_splits.  S > 1 cuts the targets [0, mt) of an image into the S ranges [r mt / S, (r+1) mt / S) (integer division), searched by
+ *   different blocks; each writes a partial (d, j) per query into the workspace and a second kernel takes the ranges in ascending order
+ *   under the same rule.  Empty ranges (S > mt) are harmless.  It pays with few queries and many targets.  0: the library chooses, a pure
+ *   function of (B, n, m); cnerf_nearest_points_bytes with the same four numbers reports the workspace that choice needs.
+ *
+ *   cnerf_nearest_points_tiling   HOST: the search kernel's constants -- queries of a block, targets of a tile (sizes at which a test
+ *                                 should look for edges); either pointer may be NULL.
+ *   cnerf_nearest_points_bytes    workspace: 0 for one range, else 8 bytes x S x B x n (each half 256-byte aligned).
+ *   cnerf_nearest_points          asynchronous on `stream`, allocates nothing.
+ * CNERF_EINVAL before any launch: B < 1, n < 1, m < 1, m >= 2^31, B n >= 2^40; queries / targets / dist2 / idx NULL; target_splits
+ * outside [0,1024]; workspace NULL when the bytes entry reports more than 0. */
+int cnerf_nearest_points_tiling(int32_t* queries_per_block, int32_t* targets_per_tile);
+int cnerf_nearest_points_bytes(int32_t B, int64_t n, int64_t m, int32_t target_splits, size_t* workspace);
+int cnerf_nearest_points(int32_t B, int64_t n, int64_t m, const float* queries /* (B,n,3) */, const float* targets /* (B,m,3) */,
+                         const int32_t* n_queries /* (B) DEVICE or NULL = n */, const int32_t* n_targets /* (B) DEVICE or NULL = m */,
+                         int32_t target_splits /* 0 = chosen by the library, else 1..1024 */,
+                         float* dist2 /* (B,n) */, int32_t* idx /* (B,n) */, void* workspace, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
