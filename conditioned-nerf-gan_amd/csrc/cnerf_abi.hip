@@ -202,7 +202,7 @@ int fill_field_args(FieldArgs& a, const cnerf_cfg* c, const cnerf_volumes* vols,
     freq = (nc.n_film && freq) ? freq + (size_t)image0 * nc.n_film * c->H : freq;
     phase = (nc.n_film && phase) ? phase + (size_t)image0 * nc.n_film * c->H : phase;
     a.packed = packed;
-    a.bias = packed + pl.weight_floats;
+    a.bias = packed ? packed + pl.weight_floats : nullptr;      // (cnerf_scatter_patches has no weights)
     a.freq = nc.n_film ? freq : nullptr;
     a.phase = nc.n_film ? phase : nullptr;
     a.film_stride = nc.n_film * c->H;
@@ -833,6 +833,27 @@ int cnerf_field_backward_points(const cnerf_cfg* cfg, const cnerf_volumes* vols,
     if (int rc = points_args(fa, cfg, vols, grad_vols, packed, freq, phase, points, 0, cfg->B, n_per_image, drop_mask)) return rc;
     return field_backward_run(fa, cfg, (long long)cfg->B * n_per_image, packed_t, grad_rgb_sigma, saved_rgb_sigma, act_feat, act_h, act_c, act_g,
                               act_go, (hipStream_t)stream);
+}
+
+int cnerf_scatter_patches(const cnerf_cfg* cfg, int32_t pass, int32_t image0, int32_t n_images, const float* cam2world, const float* u_strat,
+                          const float* fine_z, const float* gin, const cnerf_grad_volumes* grad_vols, void* stream) {
+    g_err[0] = 0;
+    if (int rc = check_cfg(cfg, true)) return rc;
+    if (no_volume(cfg)) return fail(CNERF_EINVAL, "scatter_patches: CNERF_F_NO_VOLUME networks have no volume to scatter into");
+    if (pass != 0 && pass != 1) return fail(CNERF_EINVAL, "scatter_patches: pass must be 0 (coarse) or 1 (fine): explicit points are no pixel patches");
+    if (image0 < 0 || n_images < 1 || image0 + n_images > cfg->B) return fail(CNERF_EINVAL, "scatter_patches: image range out of [0,B)");
+    if (!cam2world || !gin || !grad_vols) return fail(CNERF_EINVAL, "scatter_patches: NULL argument");
+    if (int rc = check_grad_vols(cfg, grad_vols, "scatter_patches")) return rc;
+    if (pass == 1 && !fine_z) return fail(CNERF_EINVAL, "scatter_patches: the fine pass needs fine_z");
+    // the chunk's pass as cnerf_render_backward forms it for chunk16.  The scatter reads no volume, weight, freq or phase: the gradient
+    // volumes stand in for the levels pass_args wants to see (it offsets their addresses and dereferences nothing)
+    cnerf_volumes unread;
+    memset(&unread, 0, sizeof(unread));
+    for (int i = 0; i < n_levels_of(cfg); ++i) unread.level[i] = grad_vols->level[i];
+    FieldArgs fa;
+    if (int rc = pass_args(fa, cfg, pass, image0, n_images, &unread, grad_vols, nullptr, nullptr, nullptr, cam2world, u_strat, fine_z)) return rc;
+    if (hipError_t e = launch_scatter_patch(fa, gin, (hipStream_t)stream)) return hip_fail(e, "scatter_patch");
+    return CNERF_OK;
 }
 
 int cnerf_weight_grad16(int32_t n_images, int64_t tiles_per_image, int32_t n_rows, int32_t g_ct, int32_t x_ct, const void* G,

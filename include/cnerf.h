@@ -400,6 +400,19 @@ typedef struct cnerf_saved {
  * gradient chain add them itself (A/B runs and tests only): the same addends in another order. */
 int cnerf_backward_workspace_bytes(const cnerf_cfg* cfg, int32_t backward_precision, int32_t images_per_chunk, int32_t have_act16,
                                    size_t* bytes);
+
+/* Stage entry of that patch scatter, for hosts that sequence the stages themselves -- cnerf_render_backward runs it per pass and chunk
+ * behind the half-precision chain -- and what tests/test_gpu_scatter_patch.py holds to float64 voxel by voxel (added in ABI v10 without
+ * a version change: no struct changed):
+ * grad_vols[level] (images [image0, image0 + n_images)) += the trilinear scatter of gin with the weights of the sample positions of
+ * ray pass `pass` (0 coarse: u_strat or NULL = Philox; 1 fine: fine_z), formed as cnerf_field_backward forms them.
+ * gin: (feature input tiles of the network in layer-0 order, n_images * R*R*S, 32) fp32, the rows of the chunk's first image first;
+ * tile t of level i adds to channels [32 t, 32 t + 32) of that level; an xyz tile (CNERF_F_INPUT_XYZ) has no rows.  cam2world, u_strat,
+ * fine_z and grad_vols are the FULL tensors of the call described by cfg (the function offsets them); gin is 16-byte aligned.
+ * CNERF_EINVAL and no launch: pass 2 (explicit points are no pixel patches), CNERF_F_NO_VOLUME, a NULL cam2world / gin / grad_vols /
+ * level / fine_z of the fine pass, an image range outside [0, B). */
+int cnerf_scatter_patches(const cnerf_cfg* cfg, int32_t pass, int32_t image0, int32_t n_images, const float* cam2world,
+                          const float* u_strat, const float* fine_z, const float* gin, const cnerf_grad_volumes* grad_vols, void* stream);
 int cnerf_render_backward(const cnerf_cfg* cfg, int32_t backward_precision, int32_t images_per_chunk, const cnerf_volumes* vols,
                           const cnerf_field_params* params, const float* packed, const void* packed_bwd, const float* freq,
                           const float* phase, const float* cam2world, const cnerf_rng* rng, const cnerf_saved* saved,

@@ -1000,6 +1000,74 @@ def test_backward_ragged_shapes_vs_oracle_autograd(dev, shape, backward_precisio
     _ragged_backward_case(dev, shape, "SHORTSIREN_FG", backward_precision)
 
 
+def test_half_backward_sparse_volume_vs_oracle_autograd(dev, monkeypatch):
+    """B=2, R=11, S=10, V=40, H=64 in half precision: the shape that once left the ragged list because feature_volume missed the
+    max-norm gate (6.8e-2 against 5e-2) while its relative L2 was 7.1e-4.  Pixels are ~3 voxels apart in a 40^3 volume: half of the
+    voxels are touched by no sample, most of the others by one or two, so an entry's error is the fp16 rounding of one or two rows and
+    not an average over hundreds -- a metric that divides by the tensor's LARGEST entry has no derived value there and is not gated
+    for this shape.  What is gated, with the chain's own atomics (CNERF_SCATTER=chain) and with the sorted patch scatter (default):
+      (i)   every other tensor by the half-precision gates of _ragged_backward_case, feature_volume by their relative-L2 gate;
+      (ii)  a voxel channel no sample point can touch (no point's 4^3 neighbourhood holds it, oracle positions) is exactly 0;
+      (iii) r = |got - exact| / A per touched voxel channel, exact = the float64 oracle gradient, A = the float64 scatter of the rows
+            |d loss / d looked-up feature| (autograd in the float64 oracle): the error in units of what the voxel's addends could
+            carry.  The yardstick is the reference's own training numerics on the same inputs, r_ref of the oracle under
+            torch.autocast("cpu", float16):  max r_hip <= max r_ref, and r_hip <= r_ref at the voxel of largest |got - exact|.
+    Measured (MI355X); the chain's atomics and the sorted scatter print the same digits:
+        feature_volume relative L2 7.08e-4, max-norm metric 6.78e-2 (the old failure, reproduced in BOTH modes: the rows, not the scatter)
+        max r_hip 10.8, max r_ref 1163 (both at voxels a sample meets with a weight near zero, where an ulp of the position decides)
+        voxel of largest |got - exact|: image 0, voxel (11, 34, 23), channel 24: |err| 1.6e-5, r_hip 2.1e-3, r_ref 5.1e-2, 20 addends
+        reference under autocast: relative L2 4.2e-2, max-norm metric 2.65; fp32 oracle vs float64: relative L2 9.6e-5
+    tests/test_gpu_scatter_patch.py holds the sorted scatter itself to the float64 scatter of its input rows, so what the max-norm
+    metric shows here is the half-precision chain's rows in a sparse volume, not a lost or doubled point."""
+    import scatter_patch_common as P
+    from field_backward_stage_common import scatter64
+    shape = dict(B=2, R=11, S=10, V=40, H=64)
+    B, R, S, V = (shape[k] for k in "BRSV")
+    seen = {}
+
+    def inspect(backward_precision, got, want, exact, oracle_grads):
+        seen["got"] = got["feature_volume"].detach().double().cpu().numpy()
+        if "exact" in seen:
+            return
+        rows = []
+        exact64 = oracle_grads(torch.float64, rows=rows)[1]["feature_volume"]
+        assert exact64.dtype == np.float64 and len(rows) == 2 and rows[0][0].shape == (B, R * R * S, 3)
+        seen.update(exact=exact64, rows=rows, want=want["feature_volume"], floor_l2=rel_l2(want["feature_volume"], exact["feature_volume"]),
+                    amp=oracle_grads(torch.float32, autocast=True)[1]["feature_volume"].astype(np.float64))
+
+    got = {}
+    for mode in ("chain", "sorted"):
+        if mode == "chain":
+            monkeypatch.setenv("CNERF_SCATTER", "chain")
+        else:
+            monkeypatch.delenv("CNERF_SCATTER")
+        _ragged_backward_case(dev, shape, "SHORTSIREN_FG", "fp16", inspect=inspect, ungated_max_norm=("feature_volume",))      # (i)
+        got[mode] = seen["got"]
+    cl = lambda t: np.ascontiguousarray(np.transpose(t, (0, 2, 3, 4, 1)))          # (B, C, V, V, V) -> channel-last
+    exact, amp = cl(seen["exact"]), cl(seen["amp"])
+    A, count = np.zeros(exact.shape), np.zeros(exact.shape[:-1] + (1,))
+    for pts, g_feat in seen["rows"]:
+        A += scatter64(np.abs(g_feat), np.zeros(g_feat.shape), pts, V, R * R * S)[0]
+        count += P.addend_count(pts, V, R * R * S)
+    untouched = np.broadcast_to(count == 0, exact.shape)
+    touched = A > 0
+    assert untouched.mean() > 0.3 and (exact[untouched] == 0).all() and not (touched & untouched).any()
+    r_ref = np.where(touched, np.abs(amp - exact) / np.where(touched, A, 1.0), 0.0)
+    print(f"reference under fp16 autocast: max r {r_ref.max():.3e}, relative L2 {rel_l2(amp, exact):.2e}, max-norm metric {scaled_err(amp, exact):.2e}; "
+          f"fp32 oracle vs float64: relative L2 {seen['floor_l2']:.1e}")
+    for mode, g_ in got.items():
+        g_ = cl(g_)
+        assert (g_[untouched] == 0).all(), (mode, "a voxel channel no sample point can touch is not zero")                       # (ii)
+        err = np.abs(g_ - exact)
+        r_hip = np.where(touched, err / np.where(touched, A, 1.0), 0.0)
+        worst = tuple(int(i) for i in np.unravel_index(np.argmax(np.where(touched, err, -1.0)), err.shape))
+        print(f"{mode:6s}: max r_hip {r_hip.max():.3e}; at the voxel of largest |got - exact| {worst}: |err| {err[worst]:.3e}, r_hip {r_hip[worst]:.3e}, "
+              f"r_ref {r_ref[worst]:.3e}, addends {int(count[worst[:-1]][0])}; relative L2 {rel_l2(g_, cl(seen['want'])):.2e}, "
+              f"max-norm metric vs the fp32 oracle {scaled_err(g_, cl(seen['want'])):.2e}")
+        assert r_hip.max() <= r_ref.max(), (mode, r_hip.max(), r_ref.max())                                                       # (iii)
+        assert r_hip[worst] <= r_ref[worst], (mode, worst, r_hip[worst], r_ref[worst])
+
+
 @pytest.mark.parametrize("shape", [dict(B=2, R=5, S=7, V=9, H=64), dict(B=1, R=3, S=33, V=6, H=128), dict(B=3, R=4, S=9, V=5, H=256)])
 def test_backward_per_point_film_vs_oracle_autograd(dev, shape):
     """The same for TALLSIREN (per-point FiLM, siren.py:232-331): storing forward + gradient chain kernels, weight-gradient
@@ -1034,9 +1102,14 @@ def test_benchmarked_shape_backward_vs_oracle_autograd(dev):
     _ragged_backward_case(dev, dict(B=1, R=128, S=64, V=64, H=256), "SHORTSIREN_FG", ("fp32", "fp16"))
 
 
-def _ragged_backward_case(dev, shape, variant, backward_precisions, drop_p=0.0, loss=None, fine_z=None):
+def _ragged_backward_case(dev, shape, variant, backward_precisions, drop_p=0.0, loss=None, fine_z=None, inspect=None, ungated_max_norm=()):
     """loss(pixels, depth) -> scalar, applied on both sides (default: pixels.square().mean() + depth.mean()); fine_z(resampled depths
-    (B,P,S) of the oracle) -> the fine depths forced on both sides instead of the oracle's own resampled ones."""
+    (B,P,S) of the oracle) -> the fine depths forced on both sides instead of the oracle's own resampled ones.
+    inspect(backward_precision, got, want, exact, oracle_grads): a hook that sees the gradients of every backward precision before they
+    are gated -- got: the HIP tensors, want / exact: the oracle's fp32 / float64 gradients, oracle_grads(dtype, autocast=False, rows=None):
+    another oracle run on the same inputs and forced depths (autocast: under torch.autocast("cpu", float16); rows: a list that receives
+    (sample positions, d loss / d looked-up features) of the coarse and the fine pass, the gradients then stay in the run's dtype).
+    ungated_max_norm: tensors whose max-norm metric the half-precision gate leaves out (their L2 gate stays)."""
     import cnerf_amd
     from cnerf_amd.generators import ImplicitGenerator3d
     from cnerf_amd.generators.volumetric_rendering import sample_camera_positions, create_cam2world_matrix
@@ -1059,20 +1132,34 @@ def _ragged_backward_case(dev, shape, variant, backward_precisions, drop_p=0.0, 
     if drop_p:          # training mode: keep decisions of the two field passes, one (B, P*S, H) slab per FiLM / sine layer (not per residual block)
         n_drop = sum(1 for k in gen.siren.spec.layers if k != "res")
         drop = {k: (torch.rand(n_drop, B, P * S, H) >= drop_p).to(torch.uint8) for k in ("drop_coarse", "drop_fine")}
-    def oracle_grads(dtype):
-        c = lambda t: t.detach().clone().to(dtype)
+    def oracle_grads(dtype, autocast=False, rows=None):
+        c = lambda t: t.detach().cpu().clone().to(dtype)      # (the hook calls this after the network has moved to the GPU)
         params = {k: c(v).requires_grad_(True) for k, v in gen.siren.state_dict().items()}
         fv_r, gl_r = c(fvol).requires_grad_(True), (c(glob).requires_grad_(True) if has_glob else None)
+        looked_up, field_eval = [], O.field_eval
+
+        def recording(spec, params_, fvol_cf, global_feature, points, *a):      # render() calls it once per ray pass
+            out, feats = field_eval(spec, params_, fvol_cf, global_feature, points, *a)
+            looked_up.append((points, feats))
+            return out, feats
+
         torch.set_default_dtype(dtype)
+        O.field_eval = recording if rows is not None else field_eval
         try:
-            ref = O.render(variant, params, fv_r, gl_r, c(cam), R, 49.13, 0.25, 1.95, S, True, "softplus", 0.3, True, False,
-                           c(rng["u_strat"]), c(rng["eps_coarse"]), c(rng["u_fine"]), c(rng["eps_final"]),
-                           forced_fine_z=None if forced is None else forced.to(dtype), drop_p=drop_p, **drop)
+            with torch.autocast("cpu", dtype=torch.float16, enabled=autocast):
+                ref = O.render(variant, params, fv_r, gl_r, c(cam), R, 49.13, 0.25, 1.95, S, True, "softplus", 0.3, True, False,
+                               c(rng["u_strat"]), c(rng["eps_coarse"]), c(rng["u_fine"]), c(rng["eps_final"]),
+                               forced_fine_z=None if forced is None else forced.to(dtype), drop_p=drop_p, **drop)
+                value = loss(ref.pixels.float(), ref.depth.float()) if autocast else loss(ref.pixels, ref.depth)
         finally:
             torch.set_default_dtype(torch.float32)
+            O.field_eval = field_eval
         leaves = [fv_r] + ([gl_r] if has_glob else []) + list(params.values())
-        grads = torch.autograd.grad(loss(ref.pixels, ref.depth), leaves)
+        grads = torch.autograd.grad(value, leaves + [f for _, f in looked_up])
         names = ["feature_volume"] + (["global_feature"] if has_glob else []) + list(params.keys())
+        if rows is not None:
+            rows.extend((p.detach().numpy(), g_.numpy()) for (p, _), g_ in zip(looked_up, grads[len(leaves):]))
+            return ref, {k: v.numpy() for k, v in zip(names, grads)}
         return ref, {k: v.float().numpy() for k, v in zip(names, grads)}
 
     if loss is None:
@@ -1102,13 +1189,15 @@ def _ragged_backward_case(dev, shape, variant, backward_precisions, drop_p=0.0, 
         if has_glob:
             got["global_feature"] = gl.grad
         got.update({k: p.grad for k, p in gen.siren.named_parameters()})
+        if inspect is not None:
+            inspect(backward_precision, got, want, exact, oracle_grads)
         for k, w in want.items():
             floor = scaled_err(w, exact[k])
             e, l2 = scaled_err(got[k].cpu().numpy(), w), rel_l2(got[k].cpu().numpy(), w)
             if backward_precision == "fp32":
                 assert e < max(2e-3, 2.5 * floor), (backward_precision, k, e, floor)
             else:
-                assert l2 < max(2e-3, 2.5 * rel_l2(w, exact[k])) and e < max(5e-2, 2.5 * floor), (backward_precision, k, e, l2, floor)
+                assert l2 < max(2e-3, 2.5 * rel_l2(w, exact[k])) and (k in ungated_max_norm or e < max(5e-2, 2.5 * floor)), (backward_precision, k, e, l2, floor)
 
 
 @pytest.mark.parametrize("backward_precision", ["fp32", "fp16"])
@@ -1416,7 +1505,9 @@ def test_sorted_patch_scatter_matches_the_chain_scatter(dev, monkeypatch, shape,
     8-voxel window: the direct path), ragged patches / a ragged last quad / several images in a 12-voxel volume (everything inside one
     window, long runs), and a 64-voxel volume at 64 x 64 rays; with more than 64 samples per ray (the fine pass walks its depth quads in
     rounds of 16: a second round from S = 65 on) the direct path at 18 quads and everything inside one window at 32; oblique cameras; a
-    single level and the three-level pyramid."""
+    single level and the three-level pyramid.
+    These mode-to-mode gates (HIP against HIP) are backed per voxel by tests/test_gpu_scatter_patch.py, which holds the sorted scatter
+    to the float64 scatter of its input rows within a derived bound."""
     import cnerf_amd
     from cnerf_amd.generators import ImplicitGenerator3d
     from cnerf_amd.generators.volumetric_rendering import sample_camera_positions, create_cam2world_matrix
