@@ -6,8 +6,8 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libcnerf_hip.so")
-SOURCES = ["cnerf_abi.hip", "field_kernel.hip", "field_h3.hip", "field_pw16.hip", "ray_kernels.hip", "ray_batch.hip", "grad_kernels.hip", "bwd16.hip", "chain_pw16.hip", "scatter_patch.hip", "points_grad.hip", "pfilm_finish.hip", "occupancy.hip", "isosurface.hip", "nearest.hip"]
-HEADERS = ["cnerf_dev.hpp", "cnerf_kernels.hpp", "field_common.hpp", "bwd16.hpp", "h3_dev.hpp", os.path.join("..", "..", "include", "cnerf.h")]
+SOURCES = ["abi_common.hip", "abi_forward.hip", "abi_backward.hip", "abi_rays.hip", "abi_shapes.hip", "field_kernel.hip", "field_h3.hip", "field_pw16.hip", "ray_kernels.hip", "ray_batch.hip", "grad_kernels.hip", "bwd16.hip", "chain_pw16.hip", "scatter_patch.hip", "points_grad.hip", "pfilm_finish.hip", "occupancy.hip", "isosurface.hip", "nearest.hip"]
+HEADERS = ["abi_common.hpp", "cnerf_dev.hpp", "cnerf_kernels.hpp", "field_common.hpp", "bwd16.hpp", "h3_dev.hpp", os.path.join("..", "..", "include", "cnerf.h")]
 # -ffp-contract=off: a*b+c is two roundings unless fmaf() is written (see csrc/cnerf_dev.hpp)
 FLAGS = ["--offload-arch=gfx950", "-O3", "-fPIC", "-std=c++17", "-ffp-contract=off", "-Wall", "-Wno-unused-function"]
 
@@ -33,7 +33,7 @@ def build_library(force=False, verbose=False, extra_flags=()):
         objs.append(o)
         if force or _stale(o, [s] + hdrs):
             jobs.append([hipcc, *FLAGS, *defs, *extra_flags, "-c", s, "-o", o])
-    if jobs:      # the translation units are independent: compile them side by side (a handful of processes)
+    if jobs:      # the translation units are independent: compile them side by side (MAX_JOBS processes, else half the CPUs: 16 at most)
         from concurrent.futures import ThreadPoolExecutor
 
         def run(cmd):
@@ -41,7 +41,8 @@ def build_library(force=False, verbose=False, extra_flags=()):
                 print(" ".join(cmd), flush=True)
             subprocess.check_call(cmd)
 
-        with ThreadPoolExecutor(max_workers=min(len(jobs), max(1, (os.cpu_count() or 2) // 2))) as pool:
+        cap = min(16, int(os.environ.get("MAX_JOBS") or (os.cpu_count() or 2) // 2))
+        with ThreadPoolExecutor(max_workers=min(len(jobs), max(1, cap))) as pool:
             list(pool.map(run, jobs))
     if force or _stale(LIB, objs):
         cmd = [hipcc, "--offload-arch=gfx950", "-shared", "-fPIC", *objs, "-o", LIB]

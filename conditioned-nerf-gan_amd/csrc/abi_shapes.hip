@@ -1,0 +1,149 @@
+// C ABI (include/cnerf.h), shapes: isosurface meshes and nearest points.
+#include "abi_common.hpp"
+
+using namespace cnerf;
+
+// ---------------------------------------------------------------------------------------------------------------------
+// isosurfaces: marching tetrahedra on a scalar lattice (csrc/isosurface.hip)
+// ---------------------------------------------------------------------------------------------------------------------
+namespace {
+int check_iso_shape(int n0, int n1, int n2, const char* who) {
+    const int n[3] = {n0, n1, n2};
+    for (int c = 0; c < 3; ++c)
+        if (n[c] < 2 || n[c] > 1024) return fail(CNERF_EINVAL, "%s: n%d=%d out of range [2,1024]", who, c, n[c]);
+    if ((long long)n0 * n1 * n2 > (1LL << 27)) return fail(CNERF_EINVAL, "%s: n0 n1 n2 = %lld exceeds 2^27", who, (long long)n0 * n1 * n2);
+    return CNERF_OK;
+}
+// Workspace of cnerf_isosurface_count / _emit: code (n) uint8, voff (n) int32, toff (n) int32, block sums (2, blocks) int32
+struct IsoLayout {
+    size_t code, voff, toff, sums, total;
+};
+IsoLayout iso_layout(const IsoDims& d) {
+    IsoLayout W{};
+    Carver w;
+    W.code = w.take((size_t)d.n);
+    W.voff = w.take((size_t)d.n * sizeof(int32_t));
+    W.toff = w.take((size_t)d.n * sizeof(int32_t));
+    W.sums = w.take((size_t)2 * d.blocks * sizeof(int32_t));
+    W.total = w.off;
+    return W;
+}
+}  // namespace
+
+// ---------------------------------------------------------------------------------------------------------------------
+// nearest points: exact brute-force search between two batched clouds (csrc/nearest.hip)
+// ---------------------------------------------------------------------------------------------------------------------
+namespace {
+constexpr long long NN_FILL_WAVES = 4096;     // work items (one wave each) that fill the card: 256 CUs x 4 SIMDs x 4 waves
+constexpr long long NN_MIN_RANGE = 1024;      // targets a range keeps at least, so that a partial per query is paid for
+// target_splits == 0: a pure function of (B, n, m)
+int nearest_auto_splits(int B, long long n, long long m) {
+    const long long items = (long long)B * ((n + NN_QUERIES - 1) / NN_QUERIES);
+    long long s = (NN_FILL_WAVES + items - 1) / items;
+    const long long cap = (m + NN_MIN_RANGE - 1) / NN_MIN_RANGE;
+    if (s > cap) s = cap;
+    return (int)(s < 1 ? 1 : (s > 1024 ? 1024 : s));
+}
+int check_nearest_shape(int B, long long n, long long m, int target_splits, const char* who) {
+    if (B < 1) return fail(CNERF_EINVAL, "%s: B=%d must be >= 1", who, B);
+    if (n < 1) return fail(CNERF_EINVAL, "%s: n=%lld must be >= 1", who, n);
+    if (m < 1 || m >= (1LL << 31)) return fail(CNERF_EINVAL, "%s: m=%lld out of range [1,2^31)", who, m);
+    if (n > ((1LL << 40) - 1) / B) return fail(CNERF_EINVAL, "%s: B n = %d x %lld must be below 2^40", who, B, n);
+    if (target_splits < 0 || target_splits > 1024) return fail(CNERF_EINVAL, "%s: target_splits=%d out of range [0,1024]", who, target_splits);
+    return CNERF_OK;
+}
+// Workspace of cnerf_nearest_points with S > 1 ranges: partial distances (B,S,n) float, partial indices (B,S,n) int32
+struct NearestLayout {
+    int splits;
+    size_t part_d, part_j, total;
+};
+NearestLayout nearest_layout(int B, long long n, long long m, int target_splits) {
+    NearestLayout W{};
+    W.splits = target_splits ? target_splits : nearest_auto_splits(B, n, m);
+    if (W.splits > 1) {
+        const size_t part = align256((size_t)B * W.splits * n * sizeof(float));
+        W.part_j = part;
+        W.total = 2 * part;
+    }
+    return W;
+}
+}  // namespace
+
+extern "C" {
+
+int cnerf_isosurface_bytes(int32_t n0, int32_t n1, int32_t n2, size_t* workspace) {
+    g_err[0] = 0;
+    if (int rc = check_iso_shape(n0, n1, n2, "isosurface_bytes")) return rc;
+    if (workspace) *workspace = iso_layout(iso_dims(n0, n1, n2)).total;
+    return CNERF_OK;
+}
+
+int cnerf_isosurface_count(int32_t n0, int32_t n1, int32_t n2, const float* values, float level, int32_t* counts, void* workspace, void* stream) {
+    g_err[0] = 0;
+    const char* who = "isosurface_count";
+    if (int rc = check_iso_shape(n0, n1, n2, who)) return rc;
+    if (!values || !counts || !workspace) return fail(CNERF_EINVAL, "%s: NULL argument (values / counts / workspace)", who);
+    if (!(fabsf(level) < INFINITY)) return fail(CNERF_EINVAL, "%s: level=%g must be finite", who, (double)level);
+    const IsoDims d = iso_dims(n0, n1, n2);
+    const IsoLayout W = iso_layout(d);
+    char* ws = (char*)workspace;
+    const IsoCountArgs a{d, values, level, (uint8_t*)(ws + W.code), (int32_t*)(ws + W.voff), (int32_t*)(ws + W.toff), (int32_t*)(ws + W.sums), counts};
+    if (hipError_t e = launch_iso_count(a, (hipStream_t)stream)) return hip_fail(e, "iso_count");
+    return CNERF_OK;
+}
+
+int cnerf_isosurface_emit(int32_t n0, int32_t n1, int32_t n2, const float* values, float level, const float lo[3], float pitch, const float* attrs,
+                          int32_t n_attr, int64_t max_vertices, int64_t max_triangles, float* vertices, float* vertex_attrs, int32_t* triangles,
+                          const void* workspace, void* stream) {
+    g_err[0] = 0;
+    const char* who = "isosurface_emit";
+    if (int rc = check_iso_shape(n0, n1, n2, who)) return rc;
+    if (!values || !workspace || !vertices || !triangles || !lo) return fail(CNERF_EINVAL, "%s: NULL argument (values / lo / workspace / vertices / triangles)", who);
+    if (!(fabsf(level) < INFINITY)) return fail(CNERF_EINVAL, "%s: level=%g must be finite", who, (double)level);
+    if (!(pitch > 0.0f) || !(pitch < INFINITY)) return fail(CNERF_EINVAL, "%s: pitch=%g must be > 0 and finite", who, (double)pitch);
+    for (int c = 0; c < 3; ++c)
+        if (!(fabsf(lo[c]) < INFINITY)) return fail(CNERF_EINVAL, "%s: lo[%d]=%g must be finite", who, c, (double)lo[c]);
+    if ((attrs == nullptr) != (vertex_attrs == nullptr)) return fail(CNERF_EINVAL, "%s: attrs and vertex_attrs must both be given, or neither", who);
+    if (attrs && (n_attr < 1 || n_attr > 8)) return fail(CNERF_EINVAL, "%s: n_attr=%d out of range [1,8]", who, n_attr);
+    if (max_vertices < 0 || max_triangles < 0)
+        return fail(CNERF_EINVAL, "%s: max_vertices=%lld and max_triangles=%lld must be >= 0", who, (long long)max_vertices, (long long)max_triangles);
+    const IsoDims d = iso_dims(n0, n1, n2);
+    const IsoLayout W = iso_layout(d);
+    const char* ws = (const char*)workspace;
+    const IsoEmitArgs a{d, values, level, {lo[0], lo[1], lo[2]}, pitch, attrs, attrs ? n_attr : 0, (long long)max_vertices, (long long)max_triangles,
+                        vertices, vertex_attrs, triangles, (const uint8_t*)(ws + W.code), (const int32_t*)(ws + W.voff), (const int32_t*)(ws + W.toff),
+                        (const int32_t*)(ws + W.sums)};
+    if (hipError_t e = launch_iso_emit(a, (hipStream_t)stream)) return hip_fail(e, "iso_emit");
+    return CNERF_OK;
+}
+
+int cnerf_nearest_points_tiling(int32_t* queries_per_block, int32_t* targets_per_tile) {
+    g_err[0] = 0;
+    if (queries_per_block) *queries_per_block = NN_QUERIES;
+    if (targets_per_tile) *targets_per_tile = NN_TILE;
+    return CNERF_OK;
+}
+
+int cnerf_nearest_points_bytes(int32_t B, int64_t n, int64_t m, int32_t target_splits, size_t* workspace) {
+    g_err[0] = 0;
+    if (int rc = check_nearest_shape(B, (long long)n, (long long)m, target_splits, "nearest_points_bytes")) return rc;
+    if (workspace) *workspace = nearest_layout(B, (long long)n, (long long)m, target_splits).total;
+    return CNERF_OK;
+}
+
+int cnerf_nearest_points(int32_t B, int64_t n, int64_t m, const float* queries, const float* targets, const int32_t* n_queries,
+                         const int32_t* n_targets, int32_t target_splits, float* dist2, int32_t* idx, void* workspace, void* stream) {
+    g_err[0] = 0;
+    const char* who = "nearest_points";
+    if (int rc = check_nearest_shape(B, (long long)n, (long long)m, target_splits, who)) return rc;
+    if (!queries || !targets || !dist2 || !idx) return fail(CNERF_EINVAL, "%s: NULL argument (queries / targets / dist2 / idx)", who);
+    const NearestLayout W = nearest_layout(B, (long long)n, (long long)m, target_splits);
+    if (W.total && !workspace) return fail(CNERF_EINVAL, "%s: workspace is NULL, %zu bytes are needed (cnerf_nearest_points_bytes)", who, W.total);
+    char* ws = (char*)workspace;
+    const NearestArgs a{B, (long long)n, (long long)m, W.splits, queries, targets, n_queries, n_targets, dist2, idx,
+                        W.total ? (float*)(ws + W.part_d) : nullptr, W.total ? (int32_t*)(ws + W.part_j) : nullptr};
+    if (hipError_t e = launch_nearest_points(a, (hipStream_t)stream)) return hip_fail(e, "nearest_points");
+    return CNERF_OK;
+}
+
+}  // extern "C"

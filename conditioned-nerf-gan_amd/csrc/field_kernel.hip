@@ -1032,7 +1032,7 @@ __global__ __launch_bounds__(256) void field_backward_kernel(FieldArgs a) {
 }
 
 // ---------------------------------------------------------------------------------------------------------------
-// host-side launchers (called from cnerf_abi.hip)
+// host-side launchers (called from abi_*.hip)
 // ---------------------------------------------------------------------------------------------------------------
 // Transposed pack: the matrix M = W^T (rows = inputs of the layer, cols = outputs) in the same A-operand order:
 //   value[e] = M[32t + (lane&31)][32tk + 8g + 4(lane>>5) + e] = W[32tk + 8g + 4(lane>>5) + e][32t + (lane&31)]

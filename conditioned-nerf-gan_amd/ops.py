@@ -304,6 +304,21 @@ AUX_SHAPES = {
 HIER_ONLY = {"coarse_weights", "cdf", "inds", "fine_z", "fine_rgb_sigma", "sort_idx", "fine_points"}
 
 
+def _aux_buffers(want_aux, aux_keys, B, P, S, n, hier, dev):
+    """({key: tensor}, the cnerf_aux pointing at them or None) of the intermediates a render keeps: all of L.AUX_FIELDS (want_aux) or
+    aux_keys, without the hierarchical-only ones where there is no fine pass."""
+    aux_t, aux_s = {}, None
+    if want_aux or aux_keys:
+        aux_s = L.Aux()
+        for k in (L.AUX_FIELDS if want_aux else aux_keys):
+            if not hier and k in HIER_ONLY:
+                continue
+            shape, dt = AUX_SHAPES[k](B, P, S, n)
+            aux_t[k] = torch.empty(shape, dtype=dt, device=dev)
+            setattr(aux_s, k, aux_t[k].data_ptr())
+    return aux_t, aux_s
+
+
 def render_forward(net, fvol, freq, phase, cam2world, img_size, fov, ray_start, ray_end, num_steps, hierarchical,
                    clamp_mode, noise_std, white_back=False, last_back=False, rng: Optional[dict] = None,
                    want_aux=False, fvol_is_channel_last=False, field_events=None, aux_keys=None, act16=None):
@@ -324,15 +339,7 @@ def render_forward(net, fvol, freq, phase, cam2world, img_size, fov, ray_start, 
     pixels = torch.empty((B, 3, R, R), dtype=torch.float32, device=dev)
     depth = torch.empty((B, R, R), dtype=torch.float32, device=dev)
     r, keep = _rng_struct(rng or {}, ("u_strat", "eps_coarse", "u_fine", "eps_final", "fine_z", "drop_coarse", "drop_fine"))
-    aux_t, aux_s = {}, None
-    if want_aux or aux_keys:
-        aux_s = L.Aux()
-        for k in (L.AUX_FIELDS if want_aux else aux_keys):
-            if not hierarchical and k in HIER_ONLY:
-                continue
-            shape, dt = AUX_SHAPES[k](B, P, S, n)
-            aux_t[k] = torch.empty(shape, dtype=dt, device=dev)
-            setattr(aux_s, k, aux_t[k].data_ptr())
+    aux_t, aux_s = _aux_buffers(want_aux, aux_keys, B, P, S, n, hierarchical, dev)
     if field_events is not None:
         aux_s = aux_s if aux_s is not None else L.Aux()
         for i, ev in enumerate(field_events):
@@ -871,37 +878,26 @@ def render_rays_forward(net, levels, freq, phase, origins, dirs, o, rng=None, wa
     pixels = torch.empty((B, P, 3), dtype=torch.float32, device=dev)
     dist = torch.empty((B, P), dtype=torch.float32, device=dev)
     r, keep = _rng_struct(rng or {}, RAY_RNG_KEYS)
-    aux_t, aux_s = {}, None
-    if want_aux or aux_keys:
-        aux_s = L.Aux()
-        for k in (L.AUX_FIELDS if want_aux else aux_keys):
-            if not hier and k in HIER_ONLY:
-                continue
-            shape, dt = AUX_SHAPES[k](B, P, S, n)
-            aux_t[k] = torch.empty(shape, dtype=dt, device=dev)
-            setattr(aux_s, k, aux_t[k].data_ptr())
+    aux_t, aux_s = _aux_buffers(want_aux, aux_keys, B, P, S, n, hier, dev)
     vs, rs = volumes_struct(levels), _rays_struct(origins, dirs)
+    # one entry per combination of bounds and occupancy; their arguments differ in those pieces only
+    entry = "cnerf_render_rays_" + ("bounded_" if bounds is not None else "") + ("masked_" if occupancy is not None else "") + "forward"
+    args = [C.byref(cfg), C.byref(rs), P]
+    if bounds is not None:
+        args.append(C.byref(bounds))
     if occupancy is not None:
         oc = _occ_struct(occupancy, B)
         live = (C.c_int32 * (2 * B))()
-        tail = (C.byref(oc), C.byref(vs), L.ptr(packed), L.ptr(_f32(freq)), L.ptr(_f32(phase)), C.byref(r), L.ptr(pixels), L.ptr(dist),
-                C.byref(aux_s) if aux_s is not None else None, live, L.ptr(ws), _stream())
-        if bounds is None:
-            L.check(L.lib().cnerf_render_rays_masked_forward(C.byref(cfg), C.byref(rs), P, *tail), "cnerf_render_rays_masked_forward")
-        else:
-            L.check(L.lib().cnerf_render_rays_bounded_masked_forward(C.byref(cfg), C.byref(rs), P, C.byref(bounds), *tail),
-                    "cnerf_render_rays_bounded_masked_forward")
-        if want_aux or aux_keys:
-            aux_t["live_coarse"] = torch.tensor(live[:B], dtype=torch.int32)
-            if hier:
-                aux_t["live_fine"] = torch.tensor(live[B:], dtype=torch.int32)
-        return pixels, dist, aux_t
-    tail = (C.byref(vs), L.ptr(packed), L.ptr(_f32(freq)), L.ptr(_f32(phase)), C.byref(r), L.ptr(pixels), L.ptr(dist),
-            C.byref(aux_s) if aux_s is not None else None, L.ptr(ws), _stream())
-    if bounds is None:
-        L.check(L.lib().cnerf_render_rays_forward(C.byref(cfg), C.byref(rs), P, *tail), "cnerf_render_rays_forward")
-    else:
-        L.check(L.lib().cnerf_render_rays_bounded_forward(C.byref(cfg), C.byref(rs), P, C.byref(bounds), *tail), "cnerf_render_rays_bounded_forward")
+        args.append(C.byref(oc))
+    args += [C.byref(vs), L.ptr(packed), L.ptr(_f32(freq)), L.ptr(_f32(phase)), C.byref(r), L.ptr(pixels), L.ptr(dist),
+             C.byref(aux_s) if aux_s is not None else None]
+    if occupancy is not None:
+        args.append(live)
+    L.check(getattr(L.lib(), entry)(*args, L.ptr(ws), _stream()), entry)
+    if occupancy is not None and (want_aux or aux_keys):
+        aux_t["live_coarse"] = torch.tensor(live[:B], dtype=torch.int32)
+        if hier:
+            aux_t["live_fine"] = torch.tensor(live[B:], dtype=torch.int32)
     return pixels, dist, aux_t
 
 
