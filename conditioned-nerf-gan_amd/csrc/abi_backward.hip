@@ -579,41 +579,67 @@ int chunk32(const cnerf_cfg* cfg, const MatrixSet& ms, const BackwardLayout& L, 
     return CNERF_OK;
 }
 
-// half precision, FiLM / plain-sine / residual networks (bwd16.hip): the storing re-run (fp16x3 kernel) unless the activations are given,
-// the chain's dry run for the per-matrix scales, the chain, the patch scatter of the input-tile gradients (fc.gin set), one weight_grad16
-// per matrix.  fc: the chunk's pass with gradient volumes.
-int chunk16(const cnerf_cfg* cfg, const MatrixSet& ms, const BackwardLayout& L, char* ws, const void* packed_bwd, FieldArgs fc, const Chunk& k,
-            const float* g_out, const float* s_out, void* a_feat, void* a_h, void* a_c, bool store, const float* freq,
-            const cnerf_field_param_grads* G, float* grad_freq, float* grad_phase, uint32_t* saturated, hipStream_t stream) {
-    const int H = cfg->H, NT = H / 32;
-    const long long T = (long long)k.cnt * k.tpi;
+// The gradient chain of a half-precision chunk of cnt images of npi points (tpi tiles) each, FiLM / plain-sine / residual networks
+// (bwd16.hip), on the caller's buffers: the head's scale from the largest |d loss / d rgb_sigma| of the chunk, the chain's dry run over
+// every step-th tile group for the per-slab maxima, their scales, the chain.  ONE sequence for chunk16 and for the stage entry
+// cnerf_field_chain16.  fc: the chunk's pass; it adds to its gradient volumes or stores the rows fc.gin.  group_step: 0 = every 16th
+// tile group once there are plenty (groups / 2048, clamped to 1..16), k >= 1 = every k-th.  gmax: n_mats + 2 words; scales: 2 (n_mats + 1).
+// between(): what the caller launches behind the head's scale and in front of the dry run (chunk16: the storing re-run, where the render
+// has always launched it; the stage entry: nothing).
+extern "C++" template <class Between>
+int chain16_sequence(const cnerf_cfg* cfg, const void* packed_bwd, FieldArgs fc, int cnt, long long npi, long long tpi, const float* g_out,
+                     const float* s_out, const void* a_c, void* a_g, void* a_go, uint32_t* gmax, float* scales, int group_step, uint32_t* saturated,
+                     hipStream_t stream, Between&& between) {
+    const int H = cfg->H;
     Chain16Layout cl;
     if (int rc = chain16_layout(cfg, cl)) return rc;
     const char* base16 = (const char*)packed_bwd;
     const float* winv = (const float*)(base16 + cl.winv_off);
-    uint32_t* gmax = (uint32_t*)(ws + L.gmax);
-    float* scales = (float*)(ws + L.scales);
-    char* a_g = ws + L.a_g;
-    char* a_go = ws + L.a_go;
-    if (int rc = head_scales(g_out, (long long)k.cnt * k.npi * 4, gmax, L.n_mats + 2, gmax + L.n_mats + 1, scales, L.n_mats, stream)) return rc;
-    const long long groups = (long long)k.cnt * ((k.tpi + 3) / 4);
-    long long step = groups / 2048;                       // dry-run sampling: every 16th tile group once there are plenty
-    step = step < 1 ? 1 : (step > 16 ? 16 : step);
-    // the storing re-run and the dry run (fa) leave the gradient volumes alone; the chain (fc) adds to them
+    if (int rc = head_scales(g_out, (long long)cnt * npi * 4, gmax, cl.n_mats + 2, gmax + cl.n_mats + 1, scales, cl.n_mats, stream)) return rc;
+    long long step = group_step;
+    if (step < 1) {                                       // dry-run sampling: every 16th tile group once there are plenty
+        step = (long long)cnt * ((tpi + 3) / 4) / 2048;
+        step = step < 1 ? 1 : (step > 16 ? 16 : step);
+    }
+    if (int rc = between()) return rc;
+    // the dry run (fa) leaves the gradient volumes alone; the chain (fc) adds to them
     FieldArgs fa = fc;
     for (float*& g : fa.lvl_grad) g = nullptr;
     fa.gin = nullptr;
-    if (store)
-        if (hipError_t e = launch_field_h3(storing_args(fa, (long long)k.cnt * k.npi, a_feat, a_h, a_c, nullptr, a_g), H, stream))
-            return hip_fail(e, "field kernel (fp16 activation store)");
     fa.grad_out = fc.grad_out = g_out;
     fa.saved_out = fc.saved_out = s_out;
     if (hipError_t e = launch_chain16(fa, H, base16, base16 + cl.head_off, winv, scales, a_c, nullptr, nullptr, gmax, nullptr, cl.n_mats, 1, (int)step,
                                       stream))
         return hip_fail(e, "chain16 (dry run)");
-    if (hipError_t e = launch_pow2_scales(gmax, L.n_mats, scales, stream)) return hip_fail(e, "pow2_scales");
+    if (hipError_t e = launch_pow2_scales(gmax, cl.n_mats, scales, stream)) return hip_fail(e, "pow2_scales");
     if (hipError_t e = launch_chain16(fc, H, base16, base16 + cl.head_off, winv, scales, a_c, a_g, a_go, nullptr, saturated, cl.n_mats, 0, 1, stream))
         return hip_fail(e, "chain16");
+    return CNERF_OK;
+}
+
+// half precision, FiLM / plain-sine / residual networks (bwd16.hip): the chain's sequence above with the storing re-run (fp16x3 kernel)
+// in it unless the activations are given, the patch scatter of the input-tile gradients (fc.gin set), one weight_grad16 per matrix.  fc: the chunk's
+// pass with gradient volumes.
+int chunk16(const cnerf_cfg* cfg, const MatrixSet& ms, const BackwardLayout& L, char* ws, const void* packed_bwd, FieldArgs fc, const Chunk& k,
+            const float* g_out, const float* s_out, void* a_feat, void* a_h, void* a_c, bool store, const float* freq,
+            const cnerf_field_param_grads* G, float* grad_freq, float* grad_phase, uint32_t* saturated, hipStream_t stream) {
+    const int H = cfg->H, NT = H / 32;
+    const long long T = (long long)k.cnt * k.tpi;
+    float* scales = (float*)(ws + L.scales);
+    char* a_g = ws + L.a_g;
+    char* a_go = ws + L.a_go;
+    auto store_forward = [&]() -> int {      // the storing re-run leaves the gradient volumes alone
+        if (!store) return CNERF_OK;
+        FieldArgs fa = fc;
+        for (float*& g : fa.lvl_grad) g = nullptr;
+        fa.gin = nullptr;
+        if (hipError_t e = launch_field_h3(storing_args(fa, (long long)k.cnt * k.npi, a_feat, a_h, a_c, nullptr, a_g), H, stream))
+            return hip_fail(e, "field kernel (fp16 activation store)");
+        return CNERF_OK;
+    };
+    if (int rc = chain16_sequence(cfg, packed_bwd, fc, k.cnt, k.npi, k.tpi, g_out, s_out, a_c, a_g, a_go, (uint32_t*)(ws + L.gmax), scales, 0, saturated,
+                                  stream, store_forward))
+        return rc;
     if (fc.gin)
         if (hipError_t e = launch_scatter_patch(fc, fc.gin, stream)) return hip_fail(e, "scatter_patch");
     float* dwarg = (float*)(ws + L.dwarg);
@@ -729,6 +755,52 @@ int cnerf_backward_workspace_bytes(const cnerf_cfg* cfg, int32_t backward_precis
     if (int rc = backward_layout(cfg, backward_precision, images_per_chunk, have_act16 != 0, L)) return rc;
     if (bytes) *bytes = L.total;
     return CNERF_OK;
+}
+
+int cnerf_field_chain16(const cnerf_cfg* cfg, int32_t pass, int32_t image0, int32_t n_images, const void* packed16, const float* freq,
+                        const float* cam2world, const float* u_strat, const float* fine_z, const float* grad_rgb_sigma,
+                        const float* saved_rgb_sigma, const void* cos16, int32_t group_step, void* g16, void* go16, float* scales, uint32_t* gmax,
+                        float* gin, const cnerf_grad_volumes* grad_vols, uint32_t* saturated, void* stream_) {
+    g_err[0] = 0;
+    if (int rc = check_cfg(cfg, true)) return rc;
+    if (cfg->layer_kind[0] == CNERF_LAYER_PFILM)
+        return fail(CNERF_EINVAL, "field_chain16: FiLM / plain-sine / residual layers only (the per-point FiLM family has a chain of its own)");
+    if (cfg->precision != CNERF_PREC_FP16X3) return fail(CNERF_EINVAL, "field_chain16: a stage of the fp16 backward: cfg->precision must be CNERF_PREC_FP16X3");
+    if (pass < 0 || pass > 2) return fail(CNERF_EINVAL, "field_chain16: pass must be 0 (coarse), 1 (fine) or 2 (explicit points)");
+    if (image0 < 0 || n_images < 1 || image0 + n_images > cfg->B) return fail(CNERF_EINVAL, "field_chain16: image range out of [0,B)");
+    if (group_step < 0) return fail(CNERF_EINVAL, "field_chain16: group_step=%d must be 0 (the render's rule) or >= 1", group_step);
+    if (!packed16 || !grad_rgb_sigma || !saved_rgb_sigma || !cos16 || !g16 || !go16 || !scales || !gmax)
+        return fail(CNERF_EINVAL, "field_chain16: NULL argument (packed16, grad_rgb_sigma, saved_rgb_sigma, cos16, g16, go16, scales, gmax)");
+    if (counts_of(cfg).n_film && !freq) return fail(CNERF_EINVAL, "field_chain16: FiLM layers need freq");
+    // the chain forms the sample positions of every tile, whether or not it scatters them itself
+    if (pass != 2 && !cam2world) return fail(CNERF_EINVAL, "field_chain16: NULL argument (cam2world of a ray pass)");
+    if (pass == 1 && !fine_z) return fail(CNERF_EINVAL, "field_chain16: the fine pass needs fine_z");
+    const bool nv = no_volume(cfg);
+    if (!nv) {
+        if ((gin != nullptr) == (grad_vols != nullptr)) return fail(CNERF_EINVAL, "field_chain16: exactly one of gin and grad_vols receives the layer-0 gradients");
+        if (grad_vols)
+            if (int rc = check_grad_vols(cfg, grad_vols, "field_chain16")) return rc;
+    }
+    if (pass == 2 && !u_strat) return fail(CNERF_EINVAL, "field_chain16: pass 2 takes the points (B,R*R*S,3) in the u_strat argument");
+    // the chain reads no volume, no forward weights and (explicit points) no camera: packed16 stands in for the addresses pass_args wants
+    // to see (it offsets them and dereferences nothing); they are taken out again below
+    const float* stand_in = (const float*)packed16;
+    cnerf_volumes unread;
+    memset(&unread, 0, sizeof(unread));
+    for (int i = 0; i < n_levels_of(cfg); ++i) unread.level[i] = stand_in;
+    FieldArgs fc;
+    if (int rc = pass_args(fc, cfg, pass, image0, n_images, &unread, nv || gin ? nullptr : grad_vols, nullptr, freq, nullptr,
+                           pass == 2 ? stand_in : cam2world, u_strat, fine_z))
+        return rc;
+    for (const float*& v : fc.lvl_vol) v = nullptr;
+    if (pass == 2) fc.cam2world = nullptr;
+    fc.gin = nv ? nullptr : gin;
+    hipStream_t stream = (hipStream_t)stream_;
+    const long long npi = (long long)cfg->R * cfg->R * cfg->S, tpi = (npi + 31) / 32;
+    // only channels 0..3 of a row of the head gradient are ever written: the rest must read as zero (the render zeroes its buffer once per call)
+    if (hipError_t e = hipMemsetAsync(go16, 0, (size_t)n_images * tpi * 2048, stream)) return hip_fail(e, "memset");
+    return chain16_sequence(cfg, packed16, fc, n_images, npi, tpi, grad_rgb_sigma + (size_t)image0 * npi * 4, saved_rgb_sigma + (size_t)image0 * npi * 4,
+                            cos16, g16, go16, gmax, scales, group_step, saturated, stream, [] { return (int)CNERF_OK; });
 }
 
 int cnerf_render_backward(const cnerf_cfg* cfg, int32_t bprec, int32_t cnt_max, const cnerf_volumes* vols, const cnerf_field_params* P,

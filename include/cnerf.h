@@ -413,6 +413,37 @@ int cnerf_backward_workspace_bytes(const cnerf_cfg* cfg, int32_t backward_precis
  * level / fine_z of the fine pass, an image range outside [0, B). */
 int cnerf_scatter_patches(const cnerf_cfg* cfg, int32_t pass, int32_t image0, int32_t n_images, const float* cam2world,
                           const float* u_strat, const float* fine_z, const float* gin, const cnerf_grad_volumes* grad_vols, void* stream);
+
+/* Stage entry of the half-precision gradient chain (csrc/bwd16.hip, chain16_kernel; FiLM / plain-sine / residual networks), for hosts
+ * that sequence the stages themselves and what tests/test_gpu_chain16.py holds to float64 row by row (added in ABI v10 without a version
+ * change: no struct changed).  On the caller's buffers it runs the launches cnerf_render_backward runs per pass and chunk between the
+ * storing forward and the reductions -- the head's scale from the largest |grad_rgb_sigma| of the chunk, the chain's dry run over the
+ * sampled tile groups, the per-slab scales, the chain -- for images [image0, image0 + n_images) of ray pass `pass` (0 / 1 / 2 as
+ * cnerf_field_backward; pass 2: u_strat carries the points (B, R*R*S, 3)); tiles = n_images * ceil(R*R*S / 32), n_mats = the network's
+ * matrices before the head (a residual block: fc1, fc2).
+ *   packed16        cnerf_pack_field_chain16.  freq: the call's FULL (B, n_film * H) tensor (NULL without FiLM layers).
+ *   cam2world, u_strat, fine_z: the FULL tensors; the chain forms the sample positions of every tile (it scatters with them when gin is NULL).
+ *   grad_rgb_sigma, saved_rgb_sigma: the FULL (B, R*R*S, 4) tensors of the pass.
+ *   cos16           cos(arg) of every slab for the chunk's tiles, fp16, fragment-major (COS16 of csrc/bwd16.hpp):
+ *                   element (slab m, tile T, channel 32 t + 8 g + 4 h + e of point j) -> ((((m * tiles + T) * NT + t) * 4 + g) * 64 + j + 32 h) * 4 + e.
+ *   group_step      0: the render's rule (every (groups / 2048)-th group of four tiles, 1..16); k >= 1: the dry run samples every k-th.
+ * Outputs:
+ *   g16             TB16 (n_mats, tiles, NT, 32, 32): d loss / d (sine argument) of slab m times scales[2 m]; rows past an image's end are 0.
+ *   go16            TB16 (tiles, 1, 32, 32): d loss / d (head pre-activation) times scales[2 n_mats] in channels 0..3, zeros elsewhere.
+ *   scales          2 (n_mats + 1) floats: {S, 1 / S} per slab, then the head's.
+ *   gmax            n_mats + 2 words, the bits of non-negative floats: per slab the largest sampled |gradient| in true units, the largest
+ *                   sampled head gradient, the largest |grad_rgb_sigma| of the chunk.
+ *   gin             (feature input tiles, n_images * R*R*S, 32) fp32, true units, the layout cnerf_scatter_patches reads -- or NULL, and
+ *   grad_vols       (the FULL gradient volumes) is ACCUMULATED INTO by the chain's own atomics.  Exactly one of the two for a network
+ *                   with a volume; neither is touched for CNERF_F_NO_VOLUME.
+ *   saturated       optional, as in cnerf_render_backward: += 1 per (tile, slab) whose stored gradients were clamped to fp16's range.
+ * CNERF_EINVAL and no launch: per-point FiLM networks, cfg->precision != CNERF_PREC_FP16X3, pass outside 0..2, an image range outside
+ * [0, B), group_step < 0, a NULL required argument (freq of a FiLM network, cam2world of a ray pass, fine_z of the fine pass, the points
+ * of pass 2 among them), both or neither of gin / grad_vols for a network with a volume, a NULL level of grad_vols. */
+int cnerf_field_chain16(const cnerf_cfg* cfg, int32_t pass, int32_t image0, int32_t n_images, const void* packed16, const float* freq,
+                        const float* cam2world, const float* u_strat, const float* fine_z, const float* grad_rgb_sigma,
+                        const float* saved_rgb_sigma, const void* cos16, int32_t group_step, void* g16, void* go16, float* scales, uint32_t* gmax,
+                        float* gin, const cnerf_grad_volumes* grad_vols, uint32_t* saturated, void* stream);
 int cnerf_render_backward(const cnerf_cfg* cfg, int32_t backward_precision, int32_t images_per_chunk, const cnerf_volumes* vols,
                           const cnerf_field_params* params, const float* packed, const void* packed_bwd, const float* freq,
                           const float* phase, const float* cam2world, const cnerf_rng* rng, const cnerf_saved* saved,
