@@ -657,35 +657,30 @@ int chunk16(const cnerf_cfg* cfg, const MatrixSet& ms, const BackwardLayout& L, 
                     (float*)(ws + L.csh), 0, H, nullptr, 0, nullptr, nullptr, G->w_final, G->b_final, nullptr, nullptr, stream);
 }
 
-// half precision, per-point FiLM family: storing forward (field_pw16.hip) unless the activations are given, the two chain kernels with
-// their dry runs (chain_pw16.hip), one weight_grad16 reduction per matrix: dW_l = g_pre_l^T y_{l-1}, dWm2 rows = (g_fr_l | g_ph_l)^T m,
-// dWm1 = g_mpre^T feat, head.  fa: the chunk's pass with gradient volumes.
-int chunk_pw16(const cnerf_cfg* cfg, const BackwardLayout& L, char* ws, const void* packed_bwd, FieldArgs fa, const Chunk& k, const float* g_out,
-               const float* s_out, char* a_feat, char* a_h, char* a_c, float* a_amax, bool store, const cnerf_field_param_grads* G, uint32_t* saturated,
-               hipStream_t stream) {
-    const int H = cfg->H, NT = H / 32, Lc = cfg->L, n_slots = 3 * Lc + 2;
-    const long long T = (long long)k.cnt * k.tpi;
+// The two gradient-chain kernels of a half-precision per-point FiLM chunk of cnt images of npi points (tpi tiles) each (chain_pw16.hip), on
+// the caller's buffers: the head's scale from the largest |d loss / d rgb_sigma| of the chunk, chain_pre's dry run over every step-th tile
+// group for the g_y maxima, their scales, the largest stored derivative per layer (r_l, To_l and the three slab scales), chain_pre; then
+// pw_gm's dry run for g_mpre's scale and pw_gm, which adds to fa's gradient volume.  ONE sequence for chunk_pw16 and for the stage entry
+// cnerf_field_chain_pw16.  group_step: 0 = groups / 1024 clamped to 1..32 (at least 1024 tile groups -- 131 k points -- are sampled, every
+// 32nd at most), k >= 1 = every k-th.  gmax: 5 L + 2 words; scales: 2 (4 L + 2) + 2 L floats, `lay` = {r_l, To_l} per layer at the end.
+int chain_pw16_sequence(const cnerf_cfg* cfg, const void* packed_bwd, FieldArgs fa, int cnt, long long npi, long long tpi, const float* g_out,
+                        const float* s_out, const void* a_c, const float* a_amax, const void* m16, void* a_gy, void* a_g, void* a_go, uint32_t* gmax,
+                        float* scales, int group_step, uint32_t* saturated, hipStream_t stream) {
+    const int H = cfg->H, Lc = cfg->L, n_slots = 3 * Lc + 2;
+    const long long T = (long long)cnt * tpi;
     const PwChainLayout cl = pw_chain_layout(cfg);
     const char* base16 = (const char*)packed_bwd;
-    uint32_t* gmax = (uint32_t*)(ws + L.gmax);
-    float* scales = (float*)(ws + L.scales);
-    char* a_g = ws + L.a_g;
-    char* a_go = ws + L.a_go;
-    float* dwarg = (float*)(ws + L.dwarg);
-    float* cs = (float*)(ws + L.cs);
-    if (store)
-        if (hipError_t e = launch_field_pw3(storing_args(fa, (long long)k.cnt * k.npi, a_feat, a_h, a_c, a_amax, a_g), H, stream))
-            return hip_fail(e, "field kernel (fp16 activation store)");
     fa.grad_out = g_out;
     fa.saved_out = s_out;
-    if (int rc = head_scales(fa.grad_out, (long long)k.cnt * k.npi * 4, gmax, 5 * Lc + 2, gmax + n_slots - 1, scales, n_slots - 1, stream)) return rc;
-    const size_t slabH = (size_t)T * NT * 2048;            // bytes per (tiles, NT, 32, 32) slab
+    if (int rc = head_scales(fa.grad_out, (long long)cnt * npi * 4, gmax, 5 * Lc + 2, gmax + n_slots - 1, scales, n_slots - 1, stream)) return rc;
     float* lay = scales + 2 * (4 * Lc + 2);
     PwChainBuffers cb{base16, base16 + cl.m_off, base16 + cl.head_off, (const float*)(base16 + cl.winv_off), (const float*)(base16 + cl.anorm_off),
-                      scales, lay, a_c, a_amax, a_h + (size_t)Lc * slabH, ws + L.a_gy, a_g, a_go, gmax, nullptr};
-    const long long groups = (long long)k.cnt * ((k.tpi + 3) / 4);
-    long long step = groups / 1024;                       // dry-run sampling: at least 1024 tile groups (131 k points), every 32nd at most
-    step = step < 1 ? 1 : (step > 32 ? 32 : step);
+                      scales, lay, a_c, a_amax, m16, a_gy, a_g, a_go, gmax, nullptr};
+    long long step = group_step;
+    if (step < 1) {                                       // dry-run sampling: at least 1024 tile groups (131 k points), every 32nd at most
+        step = (long long)cnt * ((tpi + 3) / 4) / 1024;
+        step = step < 1 ? 1 : (step > 32 ? 32 : step);
+    }
     // g_y through the layer matrices (dry run -> its scales), then the stored slabs and the mapping products (dry run -> g_mpre's scale)
     for (int m = 0; m < Lc; ++m)
         if (hipError_t e = launch_fill(scales + 2 * (3 * Lc + 2 + m), 1.0f, 2, stream)) return hip_fail(e, "fill");
@@ -701,6 +696,29 @@ int chunk_pw16(const cnerf_cfg* cfg, const BackwardLayout& L, char* ws, const vo
     if (hipError_t e = launch_pow2_scales(gmax + 3 * Lc, 1, scales + 2 * (3 * Lc), stream)) return hip_fail(e, "pow2_scales");
     cb.sat = saturated;
     if (hipError_t e = launch_pw_gm(fa, H, cb, 0, 1, stream)) return hip_fail(e, "pw_gm");
+    return CNERF_OK;
+}
+
+// half precision, per-point FiLM family: storing forward (field_pw16.hip) unless the activations are given, the chain's sequence above
+// (chain_pw16.hip), one weight_grad16 reduction per matrix: dW_l = g_pre_l^T y_{l-1}, dWm2 rows = (g_fr_l | g_ph_l)^T m,
+// dWm1 = g_mpre^T feat, head.  fa: the chunk's pass with gradient volumes.
+int chunk_pw16(const cnerf_cfg* cfg, const BackwardLayout& L, char* ws, const void* packed_bwd, FieldArgs fa, const Chunk& k, const float* g_out,
+               const float* s_out, char* a_feat, char* a_h, char* a_c, float* a_amax, bool store, const cnerf_field_param_grads* G, uint32_t* saturated,
+               hipStream_t stream) {
+    const int H = cfg->H, NT = H / 32, Lc = cfg->L, n_slots = 3 * Lc + 2;
+    const long long T = (long long)k.cnt * k.tpi;
+    float* scales = (float*)(ws + L.scales);
+    char* a_g = ws + L.a_g;
+    char* a_go = ws + L.a_go;
+    float* dwarg = (float*)(ws + L.dwarg);
+    float* cs = (float*)(ws + L.cs);
+    if (store)
+        if (hipError_t e = launch_field_pw3(storing_args(fa, (long long)k.cnt * k.npi, a_feat, a_h, a_c, a_amax, a_g), H, stream))
+            return hip_fail(e, "field kernel (fp16 activation store)");
+    const size_t slabH = (size_t)T * NT * 2048;            // bytes per (tiles, NT, 32, 32) slab
+    if (int rc = chain_pw16_sequence(cfg, packed_bwd, fa, k.cnt, k.npi, k.tpi, g_out, s_out, a_c, a_amax, a_h + (size_t)Lc * slabH, ws + L.a_gy, a_g, a_go,
+                                     (uint32_t*)(ws + L.gmax), scales, 0, saturated, stream))
+        return rc;
     // one reduction per matrix: G (n_rows of slab `slot`) against X (x_ct channel tiles), k_real columns from column k0 on
     auto reduce = [&](const void* Gs, int g_ct, int n_rows, int slot, const void* X, int x_ct, int k0, int k_real, float* dW, float* db) {
         return reduce16(k.cnt, k.tpi, n_rows, g_ct, x_ct, Gs, X, scales + 2 * slot + 1, dwarg, cs, k0, k_real, nullptr, 0, nullptr, nullptr, dW, db,
@@ -801,6 +819,45 @@ int cnerf_field_chain16(const cnerf_cfg* cfg, int32_t pass, int32_t image0, int3
     if (hipError_t e = hipMemsetAsync(go16, 0, (size_t)n_images * tpi * 2048, stream)) return hip_fail(e, "memset");
     return chain16_sequence(cfg, packed16, fc, n_images, npi, tpi, grad_rgb_sigma + (size_t)image0 * npi * 4, saved_rgb_sigma + (size_t)image0 * npi * 4,
                             cos16, g16, go16, gmax, scales, group_step, saturated, stream, [] { return (int)CNERF_OK; });
+}
+
+int cnerf_field_chain_pw16(const cnerf_cfg* cfg, int32_t pass, int32_t image0, int32_t n_images, const void* packed16, const float* cam2world,
+                           const float* u_strat, const float* fine_z, const float* grad_rgb_sigma, const float* saved_rgb_sigma, const void* cos16,
+                           const float* amax, const void* m16, int32_t group_step, void* gy16, void* g16, void* go16, float* scales, uint32_t* gmax,
+                           const cnerf_grad_volumes* grad_vols, uint32_t* saturated, void* stream_) {
+    g_err[0] = 0;
+    if (int rc = check_cfg(cfg, true)) return rc;
+    if (cfg->layer_kind[0] != CNERF_LAYER_PFILM)
+        return fail(CNERF_EINVAL, "field_chain_pw16: per-point FiLM networks only (FiLM / plain-sine / residual layers: cnerf_field_chain16)");
+    if (cfg->C != 32 || cfg->n_levels > 1) return fail(CNERF_EINVAL, "field_chain_pw16: single 32-channel volume only");
+    if (cfg->precision != CNERF_PREC_FP16X3) return fail(CNERF_EINVAL, "field_chain_pw16: a stage of the fp16 backward: cfg->precision must be CNERF_PREC_FP16X3");
+    if (pass < 0 || pass > 2) return fail(CNERF_EINVAL, "field_chain_pw16: pass must be 0 (coarse), 1 (fine) or 2 (explicit points)");
+    if (image0 < 0 || n_images < 1 || image0 + n_images > cfg->B) return fail(CNERF_EINVAL, "field_chain_pw16: image range out of [0,B)");
+    if (group_step < 0) return fail(CNERF_EINVAL, "field_chain_pw16: group_step=%d must be 0 (the render's rule) or >= 1", group_step);
+    if (!packed16 || !grad_rgb_sigma || !saved_rgb_sigma || !cos16 || !amax || !m16 || !gy16 || !g16 || !go16 || !scales || !gmax || !grad_vols)
+        return fail(CNERF_EINVAL,
+                    "field_chain_pw16: NULL argument (packed16, grad_rgb_sigma, saved_rgb_sigma, cos16, amax, m16, gy16, g16, go16, scales, gmax, grad_vols)");
+    if (int rc = check_grad_vols(cfg, grad_vols, "field_chain_pw16")) return rc;
+    if (pass != 2 && !cam2world) return fail(CNERF_EINVAL, "field_chain_pw16: NULL argument (cam2world of a ray pass)");
+    if (pass == 1 && !fine_z) return fail(CNERF_EINVAL, "field_chain_pw16: the fine pass needs fine_z");
+    if (pass == 2 && !u_strat) return fail(CNERF_EINVAL, "field_chain_pw16: pass 2 takes the points (B,R*R*S,3) in the u_strat argument");
+    // the chain reads no volume, no forward weights and (explicit points) no camera: packed16 stands in for the addresses pass_args wants
+    // to see (it offsets them and dereferences nothing); they are taken out again below
+    const float* stand_in = (const float*)packed16;
+    cnerf_volumes unread;
+    memset(&unread, 0, sizeof(unread));
+    unread.level[0] = stand_in;
+    FieldArgs fa;
+    if (int rc = pass_args(fa, cfg, pass, image0, n_images, &unread, grad_vols, nullptr, nullptr, nullptr, pass == 2 ? stand_in : cam2world, u_strat, fine_z))
+        return rc;
+    fa.lvl_vol[0] = nullptr;
+    if (pass == 2) fa.cam2world = nullptr;
+    hipStream_t stream = (hipStream_t)stream_;
+    const long long npi = (long long)cfg->R * cfg->R * cfg->S, tpi = (npi + 31) / 32;
+    // only channels 0..3 of a row of the head gradient are ever written: the rest must read as zero (the render zeroes its buffer once per call)
+    if (hipError_t e = hipMemsetAsync(go16, 0, (size_t)n_images * tpi * 2048, stream)) return hip_fail(e, "memset");
+    return chain_pw16_sequence(cfg, packed16, fa, n_images, npi, tpi, grad_rgb_sigma + (size_t)image0 * npi * 4, saved_rgb_sigma + (size_t)image0 * npi * 4,
+                               cos16, amax, m16, gy16, g16, go16, gmax, scales, group_step, saturated, stream);
 }
 
 int cnerf_render_backward(const cnerf_cfg* cfg, int32_t bprec, int32_t cnt_max, const cnerf_volumes* vols, const cnerf_field_params* P,

@@ -33,7 +33,8 @@ struct RescaleNo { static constexpr bool value = false; };
 //                    a tile are consumed as soon as its epilogue has produced them), g_m resident in 8 accumulator tiles and moved to the next
 //                    layer's units tile by tile, then the tail (g_mpre, Wm1^T, volume scatter).  Operands carry per-LAYER scales here (the stored
 //                    g_y has no per-point one): a point whose gradient is 2^-20 of the largest contributes nothing to g_m -- or to any sum over
-//                    points.  The stored slabs see two fp16 roundings (g_y, then the product) instead of one.
+//                    points.  The stored slabs see two fp16 roundings (g_y, then the product) instead of one.  The operands are not clamped:
+//                    chain_pre_kernel counts in `saturated` every (tile, layer) in which one could pass fp16's range.
 struct PreArgs {
     FieldArgs f;
     const f16x8* units;       // Y units: stages L-2 .. 0, NT units of KCH pieces each
@@ -41,6 +42,7 @@ struct PreArgs {
     const float* winv;        // 1 / s: [W_l^T: L (entry 0 unused) | Wm2 pair of layer l: L | Wm1^T | head^T]
     const float* anorm;       // ||W_l||_1: L (entry 0 unused), then the head's
     const float* scales;      // {S, 1 / S}: index 3 L + 1: go; 3 L + 2 + l: g_y of layer l
+    const float* lay;         // per layer {r_l, To_l}: read by the storing launch only (the dry run comes before pw_split_scales)
     const _Float16* cos16;    // 3 L COS16 slabs; this kernel reads cos f (slab 3 l + 1)
     const float* amax;
     _Float16* gy16;           // TB16: L slabs (tiles, NT, 32, 32)
@@ -223,7 +225,10 @@ __global__ __launch_bounds__(256) void chain_pre_kernel(PreArgs A) {
 #pragma unroll
                 for (int d = 32; d >= 1; d >>= 1) m4 = fmaxf(m4, __shfl_xor(m4, d, WAVE));
                 if (lane == 0) atomicMax(A.gmax + 3 * L + 2 + lam, __float_as_uint(m4));
-            } else if (A.sat && live && __any(my * USy > 65504.0f) && lane == 0) {
+            } else if (A.sat && live && __any(my * USy > 65504.0f || (my * USy) * (am * A.lay[2 * lam + 1]) > 65472.0f) && lane == 0) {
+                // the stored g_y was clamped, or pw_gm_kernel's operands fp16(gy16 d To_l) of this point can pass fp16's range: |gy16| <= my USy
+                // (1 + 2^-11) and |d| <= amax, so up to 65472 the product stays below 65520, where the conversion turns to +-inf (a point of an
+                // unsampled group is stored unclamped up to 32 x the sampled maximum, and pw_gm_kernel does not clamp: its fmaxf would drop the NaN)
                 atomicAdd(A.sat, 1u);
             }
             gpremax_prev = mp * U;
@@ -582,6 +587,7 @@ hipError_t launch_chain_pre(const FieldArgs& f, int H, const PwChainBuffers& c, 
     A.winv = c.winv;
     A.anorm = c.anorm;
     A.scales = c.scales;
+    A.lay = c.lay;
     A.cos16 = (const _Float16*)c.cos16;
     A.amax = c.amax;
     A.gy16 = (_Float16*)c.gy16;

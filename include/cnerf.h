@@ -444,6 +444,45 @@ int cnerf_field_chain16(const cnerf_cfg* cfg, int32_t pass, int32_t image0, int3
                         const float* cam2world, const float* u_strat, const float* fine_z, const float* grad_rgb_sigma,
                         const float* saved_rgb_sigma, const void* cos16, int32_t group_step, void* g16, void* go16, float* scales, uint32_t* gmax,
                         float* gin, const cnerf_grad_volumes* grad_vols, uint32_t* saturated, void* stream);
+
+/* Stage entry of the half-precision gradient chain of the per-point FiLM family (csrc/chain_pw16.hip: chain_pre_kernel, pw_gm_kernel),
+ * the counterpart of cnerf_field_chain16 and what tests/test_gpu_chain_pw16.py holds to float64 row by row (added in ABI v10 without a
+ * version change: no struct changed).  On the caller's buffers it runs the launches cnerf_render_backward runs per pass and chunk between
+ * the storing forward and the reductions: the head's scale, chain_pre's dry run over the sampled tile groups, the g_y scales, the largest
+ * stored derivative per layer (r_l, To_l, the three slab scales), chain_pre, pw_gm's dry run, g_mpre's scale, pw_gm.  pass / image0 /
+ * n_images / cam2world / u_strat / fine_z / grad_rgb_sigma / saved_rgb_sigma as for cnerf_field_chain16; tiles = n_images * ceil(R*R*S / 32),
+ * L = cfg->L, NT = H / 32.
+ *   packed16   cnerf_pack_field_chain16 of the per-point FiLM network.
+ *   cos16      3 L COS16 slabs (the layout of cnerf_field_chain16's cos16) of the chunk's tiles: per layer cos, cos f, cos 15 pre.
+ *   amax       (L, tiles * 32) fp32: per point and layer the largest |stored derivative| of the three rows (it bounds the operand scale T of
+ *              the point and, through its maximum over ALL tiles * 32 entries of a layer, r_l).
+ *   m16        TB16 (tiles, 8, 32, 32): the mapping network's hidden activation LeakyReLU_0.2(Wm1 feat + bm1); only its sign is read.
+ *   Rows past an image's end (padded lanes of a last tile) of cos16 / m16 may hold any finite values: they reach no output.  Those of amax
+ *   enter the layer maximum r_l comes from: finite, >= 0 and below 3e38 (a larger value reads as "no maximum": r_l = 1); the storing
+ *   forward writes the image's last point there.
+ *   group_step 0: the render's rule (every (groups / 1024)-th group of four tiles, 1..32); k >= 1: both dry runs sample every k-th.
+ * Outputs (rows past an image's end are 0 in every TB16 slab):
+ *   gy16       TB16 (L, tiles, NT, 32, 32): d loss / d y_l times S_y,l = scales[2 (3 L + 2 + l)].
+ *   g16        TB16 (3 L, tiles, NT, 32, 32): per layer g_pre = g_y cos f, g_fr = g_y cos 15 pre, g_ph = g_y cos, each exactly
+ *              fp16(gy16 * derivative * r_l), i.e. times scales[2 (3 l + s)] = S_y,l r_l; then g_mpre TB16 (tiles, 8, 32, 32) times scales[2 (3 L)].
+ *   go16       TB16 (tiles, 1, 32, 32): d loss / d (head pre-activation) times scales[2 (3 L + 1)] in channels 0..3, zeros elsewhere.
+ *   scales     2 (4 L + 2) + 2 L floats: {S, 1 / S} for slots 3 l + s (s = 0 g_pre, 1 g_fr, 2 g_ph), 3 L (g_mpre), 3 L + 1 (go), 3 L + 2 + l
+ *              (g_y of layer l); then `lay`: {r_l, To_l = 8 r_l} per layer, r_l = 2^-ceil(log2 max(1, largest amax of layer l)).
+ *   gmax       5 L + 2 words, the bits of non-negative floats: slots 0 .. 3 L - 1 unused (0), 3 L: largest sampled |g_mpre|, 3 L + 1: largest
+ *              sampled head gradient, 3 L + 2 + l: largest sampled |g_y_l|, 4 L + 2 + l: largest amax of layer l; the head's scale comes
+ *              from the largest |grad_rgb_sigma| of the chunk, which passes through slot 3 L + 1 before the dry run overwrites it.
+ *   grad_vols  the FULL gradient volume, ACCUMULATED INTO by pw_gm's own atomics (g_feat = Wm1^T g_mpre, trilinear weights).
+ *   saturated  optional: += 1 per (tile, layer) with a point whose stored g_y was clamped to fp16's range or whose operands of the mapping
+ *              products fp16(gy16 * derivative * To_l) can pass it ((max |g_y| S_y,l) * amax * To_l > 65472: such operands are +-inf, the
+ *              point's g_mpre and the voxels it reaches may hold NaN), and per tile whose g_mpre was clamped: non-zero means repeat in
+ *              fp32, as in cnerf_render_backward.
+ * CNERF_EINVAL and no launch: another layer family, a volume other than one 32-channel level, cfg->precision != CNERF_PREC_FP16X3, pass
+ * outside 0..2, an image range outside [0, B), group_step < 0, a NULL required argument (cam2world of a ray pass, fine_z of the fine pass,
+ * the points of pass 2, grad_vols and its level among them). */
+int cnerf_field_chain_pw16(const cnerf_cfg* cfg, int32_t pass, int32_t image0, int32_t n_images, const void* packed16, const float* cam2world,
+                           const float* u_strat, const float* fine_z, const float* grad_rgb_sigma, const float* saved_rgb_sigma, const void* cos16,
+                           const float* amax, const void* m16, int32_t group_step, void* gy16, void* g16, void* go16, float* scales, uint32_t* gmax,
+                           const cnerf_grad_volumes* grad_vols, uint32_t* saturated, void* stream);
 int cnerf_render_backward(const cnerf_cfg* cfg, int32_t backward_precision, int32_t images_per_chunk, const cnerf_volumes* vols,
                           const cnerf_field_params* params, const float* packed, const void* packed_bwd, const float* freq,
                           const float* phase, const float* cam2world, const cnerf_rng* rng, const cnerf_saved* saved,
