@@ -9,5 +9,6 @@ The directory name contains hyphens, so import it through the alias module at th
 from . import _lib, ops  # noqa: F401
 from .generators import ImplicitGenerator3d  # noqa: F401
 from . import shape_metrics  # noqa: F401,E402
+from . import voxels  # noqa: F401,E402
 
-__all__ = ["ImplicitGenerator3d", "ops", "generators", "shape_metrics"]
+__all__ = ["ImplicitGenerator3d", "ops", "generators", "shape_metrics", "voxels"]

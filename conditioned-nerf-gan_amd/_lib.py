@@ -159,6 +159,11 @@ PROTOTYPES = {
     "cnerf_nearest_points_bytes": (C.c_int, [C.c_int32, C.c_int64, C.c_int64, C.c_int32, C.POINTER(C.c_size_t)]),
     "cnerf_nearest_points": (C.c_int, [C.c_int32, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p,
                                        C.c_void_p, C.c_void_p, C.c_void_p]),
+    "cnerf_voxelize_bytes": (C.c_int, [C.c_int32, C.c_int32, C.POINTER(C.c_size_t)]),
+    "cnerf_voxelize": (C.c_int, [C.c_int32, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(C.c_float), C.c_float, C.c_float,
+                                 C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "cnerf_voxel_first_hit": (C.c_int, [C.c_int32, C.c_int64, C.POINTER(Rays), C.c_void_p, C.c_int32, C.POINTER(C.c_float), C.c_float, C.c_int32,
+                                        C.c_float, C.c_float, C.c_int32, C.POINTER(C.c_float), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
 }
 
 _lib = None

@@ -1,4 +1,4 @@
-// C ABI (include/cnerf.h), shapes: isosurface meshes and nearest points.
+// C ABI (include/cnerf.h), shapes: isosurface meshes, nearest points, voxel grids of point clouds.
 #include "abi_common.hpp"
 
 using namespace cnerf;
@@ -69,7 +69,89 @@ NearestLayout nearest_layout(int B, long long n, long long m, int target_splits)
 }
 }  // namespace
 
+// ---------------------------------------------------------------------------------------------------------------------
+// voxel grids of coloured point clouds and their first-hit pictures (csrc/voxelize.hip)
+// ---------------------------------------------------------------------------------------------------------------------
+namespace {
+int check_voxel_grid(int B, int G, const char* who) {
+    if (B < 1) return fail(CNERF_EINVAL, "%s: B=%d must be >= 1", who, B);
+    if (G < 2 || G > 256) return fail(CNERF_EINVAL, "%s: G=%d out of range [2,256]", who, G);
+    return CNERF_OK;
+}
+int check_voxel_cube(int G, const float* lo, float side, int layout, const char* who) {
+    if (!lo) return fail(CNERF_EINVAL, "%s: lo is NULL", who);
+    if (!(side > 0.0f) || !(side < INFINITY)) return fail(CNERF_EINVAL, "%s: side=%g must be > 0 and finite", who, (double)side);
+    if (!((float)G / side < INFINITY))       // a denormal side: every cell coordinate would be an infinity or a NaN
+        return fail(CNERF_EINVAL, "%s: side=%g is too small: (float)G / side is not finite", who, (double)side);
+    for (int c = 0; c < 3; ++c)
+        if (!(fabsf(lo[c]) < INFINITY)) return fail(CNERF_EINVAL, "%s: lo[%d]=%g must be finite", who, c, (double)lo[c]);
+    if (layout != 0 && layout != 1) return fail(CNERF_EINVAL, "%s: layout=%d must be 0 (B,4,G,G,G) or 1 (B,G,G,G,4)", who, layout);
+    return CNERF_OK;
+}
+// four 64-bit integers per cell
+size_t voxelize_bytes(int B, int G) { return align256((size_t)B * G * G * G * 4 * sizeof(unsigned long long)); }
+}  // namespace
+
 extern "C" {
+
+int cnerf_voxelize_bytes(int32_t B, int32_t G, size_t* workspace) {
+    g_err[0] = 0;
+    if (int rc = check_voxel_grid(B, G, "voxelize_bytes")) return rc;
+    if (workspace) *workspace = voxelize_bytes(B, G);
+    return CNERF_OK;
+}
+
+int cnerf_voxelize(int32_t B, int64_t n, int32_t stride, const float* points, const int32_t* n_points, int32_t G, const float lo[3], float side,
+                   float clip_margin, int32_t layout, float* voxels, int32_t* counts, void* workspace, void* stream) {
+    g_err[0] = 0;
+    const char* who = "voxelize";
+    if (int rc = check_voxel_grid(B, G, who)) return rc;
+    if (n < 1 || n >= (1LL << 28)) return fail(CNERF_EINVAL, "%s: n=%lld out of range [1,2^28)", who, (long long)n);
+    if (stride < 6) return fail(CNERF_EINVAL, "%s: stride=%d must be >= 6 (xyz rgb)", who, stride);
+    if (int rc = check_voxel_cube(G, lo, side, layout, who)) return rc;
+    if (clip_margin != clip_margin) return fail(CNERF_EINVAL, "%s: clip_margin is NaN (>= 0 clips, < 0 does not)", who);
+    if (clip_margin >= 0.0f && !(2.0f * clip_margin < side))
+        return fail(CNERF_EINVAL, "%s: clip_margin=%g leaves nothing of side=%g (2 clip_margin must be < side)", who, (double)clip_margin, (double)side);
+    if (!points || !voxels || !workspace) return fail(CNERF_EINVAL, "%s: NULL argument (points / voxels / workspace)", who);
+    if (((uintptr_t)workspace & 15) || (layout == 1 && ((uintptr_t)voxels & 15)))
+        return fail(CNERF_EINVAL, "%s: workspace (and voxels in layout 1) must be 16-byte aligned", who);
+    VoxelizeArgs a{};
+    a.B = B, a.n = (long long)n, a.stride = stride, a.points = points, a.n_points = n_points, a.G = G;
+    a.inv = (float)G / side;
+    a.clip = clip_margin >= 0.0f;
+    for (int c = 0; c < 3; ++c) {
+        a.lo[c] = lo[c];
+        const float hi = lo[c] + side;
+        a.clip_lo[c] = a.clip ? lo[c] + clip_margin : 0.0f;
+        a.clip_hi[c] = a.clip ? hi - clip_margin : 0.0f;
+    }
+    a.layout = layout, a.voxels = voxels, a.counts = counts, a.acc = (unsigned long long*)workspace;
+    if (hipError_t e = launch_voxelize(a, (hipStream_t)stream)) return hip_fail(e, "voxelize");
+    return CNERF_OK;
+}
+
+int cnerf_voxel_first_hit(int32_t B, int64_t rays_per_image, const cnerf_rays* rays, const float* voxels, int32_t G, const float lo[3], float side,
+                          int32_t layout, float t_min, float t_max, int32_t S, const float background[3], float* pixels, float* hit_t, int32_t* hit_cell,
+                          void* stream) {
+    g_err[0] = 0;
+    const char* who = "voxel_first_hit";
+    if (int rc = check_voxel_grid(B, G, who)) return rc;
+    if (rays_per_image < 1 || rays_per_image > (1LL << 38) / B)
+        return fail(CNERF_EINVAL, "%s: rays_per_image=%lld must be >= 1 (and B * rays_per_image <= 2^38)", who, (long long)rays_per_image);
+    if (int rc = check_voxel_cube(G, lo, side, layout, who)) return rc;
+    if (S < 2 || S > 1024) return fail(CNERF_EINVAL, "%s: S=%d out of range [2,1024]", who, S);
+    if (!(fabsf(t_min) < INFINITY) || !(fabsf(t_max) < INFINITY)) return fail(CNERF_EINVAL, "%s: t_min=%g and t_max=%g must be finite", who, (double)t_min, (double)t_max);
+    if (!(t_min < t_max)) return fail(CNERF_EINVAL, "%s: t_max=%g must be greater than t_min=%g", who, (double)t_max, (double)t_min);
+    if (!rays || !rays->origins || !rays->dirs) return fail(CNERF_EINVAL, "%s: NULL argument (rays / rays.origins / rays.dirs)", who);
+    if (!voxels || !background || !pixels) return fail(CNERF_EINVAL, "%s: NULL argument (voxels / background / pixels)", who);
+    VoxelHitArgs a{};
+    a.B = B, a.P = (long long)rays_per_image, a.origins = rays->origins, a.dirs = rays->dirs, a.voxels = voxels, a.G = G;
+    a.inv = (float)G / side;
+    for (int c = 0; c < 3; ++c) a.lo[c] = lo[c], a.background[c] = background[c];
+    a.layout = layout, a.t_min = t_min, a.t_max = t_max, a.S = S, a.pixels = pixels, a.hit_t = hit_t, a.hit_cell = hit_cell;
+    if (hipError_t e = launch_voxel_first_hit(a, (hipStream_t)stream)) return hip_fail(e, "voxel_first_hit");
+    return CNERF_OK;
+}
 
 int cnerf_isosurface_bytes(int32_t n0, int32_t n1, int32_t n2, size_t* workspace) {
     g_err[0] = 0;

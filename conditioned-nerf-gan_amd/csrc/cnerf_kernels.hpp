@@ -355,6 +355,43 @@ struct NearestArgs {
 };
 hipError_t launch_nearest_points(const NearestArgs& a, hipStream_t stream);
 
+// voxelize.hip: voxel grids of coloured point clouds and their first-hit pictures (include/cnerf.h states the contracts, DESIGN.md 3.21 the design)
+struct VoxelizeArgs {
+    int B;
+    long long n;               // rows per image, < 2^28
+    int stride;                // floats per row, >= 6: xyz rgb first
+    const float* points;       // (B,n,stride)
+    const int32_t* n_points;   // (B) or null
+    int G;
+    float lo[3];
+    float inv;                 // (float)G / side, rounded once on the host
+    int clip;                  // 1: coordinates are clamped into [clip_lo, clip_hi] first and no point is outside
+    float clip_lo[3], clip_hi[3];      // lo + m, (lo + side) - m, each operation rounded on the host
+    int layout;                // 0: [b, ch, iz, iy, ix]   1: [b, ix, iy, iz, ch]
+    float* voxels;
+    int32_t* counts;           // (B,G,G,G) in the layout's spatial order, or null
+    unsigned long long* acc;   // workspace (B, G^3, 4): count, sum r, sum g, sum b per cell in the layout's cell order
+};
+struct VoxelHitArgs {
+    int B;
+    long long P;
+    const float* origins;      // (B,P,3)
+    const float* dirs;         // (B,P,3)
+    const float* voxels;       // a grid per image in `layout`
+    int G;
+    float lo[3];
+    float inv;
+    int layout;
+    float t_min, t_max;
+    int S;
+    float background[3];
+    float* pixels;             // (B,P,3)
+    float* hit_t;              // (B,P) or null
+    int32_t* hit_cell;         // (B,P) or null
+};
+hipError_t launch_voxelize(const VoxelizeArgs& a, hipStream_t stream);
+hipError_t launch_voxel_first_hit(const VoxelHitArgs& a, hipStream_t stream);
+
 hipError_t launch_philox_fill(const PhiloxKey& k, uint32_t stream_id, long long n, int normal, float* out, hipStream_t stream);
 hipError_t launch_transpose_cl(int B, int C, int V, const float* src, float* dst, bool to_channel_last, hipStream_t stream);
 

@@ -810,13 +810,13 @@ def isosurface(values, level, lo=(0.0, 0.0, 0.0), pitch=1.0, attrs=None):
     return vertices, faces, vertex_attrs
 
 
-def _cloud_lengths(lengths, B, dev, what):
+def _cloud_lengths(lengths, B, dev, what, who="nearest_points"):
     """Per-image lengths of a padded cloud -> contiguous int32 (B,) on `dev`, or None."""
     if lengths is None:
         return None
     lengths = torch.as_tensor(lengths).detach().to(device=dev, dtype=torch.int32).contiguous()
     if tuple(lengths.shape) != (B,):
-        raise L.CnerfError(f"nearest_points: {what} must be ({B},), got {tuple(lengths.shape)}")
+        raise L.CnerfError(f"{who}: {what} must be ({B},), got {tuple(lengths.shape)}")
     return lengths
 
 
@@ -849,6 +849,91 @@ def nearest_points(queries, targets, query_lengths=None, target_lengths=None, ta
     L.check(lib.cnerf_nearest_points(B, n, m, L.ptr(queries), L.ptr(targets), L.ptr(nq), L.ptr(mt), int(target_splits), L.ptr(dist2), L.ptr(idx),
                                      L.ptr(ws), _stream()), "cnerf_nearest_points")
     return (dist2[0], idx[0]) if single else (dist2, idx)
+
+
+VOXEL_LAYOUTS = {"encoder": 0, "npz": 1}
+
+
+def _voxel_layout(layout, who):
+    if layout not in VOXEL_LAYOUTS:
+        raise L.CnerfError(f"{who}: layout must be 'encoder' (B,4,G,G,G) or 'npz' (B,G,G,G,4), got {layout!r}")
+    return VOXEL_LAYOUTS[layout]
+
+
+def _cube_lo(lo):
+    lo = (lo, lo, lo) if isinstance(lo, (int, float)) else tuple(lo)
+    return (C.c_float * 3)(*(float(v) for v in lo))
+
+
+def voxelize(points, G, lo, side, lengths=None, clip_margin=1e-4, layout="encoder", want_counts=False):
+    """cnerf_voxelize: a coloured cloud points (B,n,stride >= 6) = [x, y, z, r, g, b, ...] -> the voxel grid [occupancy, r, g, b] over the
+    cube with corner lo (a number or three) and edge side, G cells per axis: occupancy 1 where a point fell, the mean of the points'
+    colours (clamped to [0,1]) beside it, 0 in empty cells.  layout "encoder": (B,4,G,G,G) indexed [b, ch, iz, iy, ix], what the U-Net
+    takes; "npz": (B,G,G,G,4) indexed [b, ix, iy, iz, ch], the order of voxel.npz.  lengths (B,): how many leading rows of each image
+    count (clamped to [0,n]; None: all).  clip_margin >= 0 clamps coordinates into [lo + m, lo + side - m] first (the reference's 1e-4);
+    None or < 0: points outside the cube are skipped.  A point with a NaN coordinate is always skipped.
+    -> voxels float32, and counts int32 (B,G,G,G) in the layout's spatial order with want_counts.  (n,stride) is taken as one image and
+    returned without the batch axis.  The colour sums are exact integers (include/cnerf.h): two calls give the same bits.
+    Forward only: the input is detached, the outputs carry no gradient."""
+    if not points.is_cuda:
+        raise L.CnerfError("voxelize: points must be on the GPU (there is no CPU fallback)")
+    points = _f32(points.detach())
+    single = points.dim() == 2
+    if single:
+        points = points.unsqueeze(0)
+    if points.dim() != 3 or points.shape[-1] < 6:
+        raise L.CnerfError(f"voxelize: points must be (B,n,6 or more) (or (n,6 or more)), got {tuple(points.shape)}")
+    code = _voxel_layout(layout, "voxelize")
+    B, n, stride = (int(s) for s in points.shape)
+    G = int(G)
+    dev = points.device
+    np_ = _cloud_lengths(lengths, B, dev, "lengths", "voxelize")
+    lib = L.lib()
+    nb = C.c_size_t(0)
+    L.check(lib.cnerf_voxelize_bytes(B, G, C.byref(nb)), "cnerf_voxelize_bytes")
+    ws = torch.empty(nb.value, dtype=torch.uint8, device=dev)
+    voxels = torch.empty((B, 4, G, G, G) if code == 0 else (B, G, G, G, 4), dtype=torch.float32, device=dev)
+    counts = torch.empty((B, G, G, G), dtype=torch.int32, device=dev) if want_counts else None
+    margin = -1.0 if clip_margin is None else float(clip_margin)
+    L.check(lib.cnerf_voxelize(B, n, stride, L.ptr(points), L.ptr(np_), G, _cube_lo(lo), float(side), margin, code, L.ptr(voxels), L.ptr(counts),
+                               L.ptr(ws), _stream()), "cnerf_voxelize")
+    if single:
+        voxels, counts = voxels[0], (counts[0] if want_counts else None)
+    return (voxels, counts) if want_counts else voxels
+
+
+def voxel_first_hit(voxels, origins, dirs, lo, side, t_min, t_max, num_steps, background=(1.0, 1.0, 1.0), layout="encoder"):
+    """cnerf_voxel_first_hit: the picture of a voxel grid.  Along every ray o + t d, at the num_steps depths of
+    torch.linspace(t_min, t_max, num_steps), the colour of the first sample that lies in a cell with occupancy != 0; the background
+    where there is none.  A sample outside the cube sees nothing.  voxels (B,4,G,G,G) ("encoder") or (B,G,G,G,4) ("npz"); origins, dirs
+    (B,P,3), directions not normalised.
+    -> pixels (B,P,3) in the grid's own colour range, hit_t (B,P) float32 (+inf: no hit), hit_cell (B,P) int32 = (ix G + iy) G + iz
+    (-1: no hit).  A single grid with (P,3) rays is taken as one image and returned without the batch axis.
+    Forward only: the inputs are detached, the outputs carry no gradient."""
+    if not (voxels.is_cuda and origins.is_cuda and dirs.is_cuda):
+        raise L.CnerfError("voxel_first_hit: voxels, origins and dirs must be on the GPU (there is no CPU fallback)")
+    voxels, origins, dirs = _f32(voxels.detach()), _f32(origins.detach()), _f32(dirs.detach())
+    code = _voxel_layout(layout, "voxel_first_hit")
+    single = voxels.dim() == 4 and origins.dim() == 2
+    if single:
+        voxels, origins, dirs = voxels.unsqueeze(0), origins.unsqueeze(0), dirs.unsqueeze(0)
+    ok = voxels.dim() == 5 and voxels.shape[1 if code == 0 else 4] == 4 and len({int(voxels.shape[k]) for k in ((2, 3, 4) if code == 0 else (1, 2, 3))}) == 1
+    if not ok:
+        raise L.CnerfError(f"voxel_first_hit: voxels must be (B,4,G,G,G) ('encoder') or (B,G,G,G,4) ('npz'), got {tuple(voxels.shape)} as {layout!r}")
+    if origins.dim() != 3 or origins.shape[-1] != 3 or dirs.shape != origins.shape or origins.shape[0] != voxels.shape[0]:
+        raise L.CnerfError(f"voxel_first_hit: origins and dirs must both be (B={voxels.shape[0]},P,3), got {tuple(origins.shape)} and {tuple(dirs.shape)}")
+    if origins.device != voxels.device or dirs.device != voxels.device:
+        raise L.CnerfError("voxel_first_hit: voxels, origins and dirs must be on the same device")
+    B, P, G = int(origins.shape[0]), int(origins.shape[1]), int(voxels.shape[2])
+    dev = voxels.device
+    pixels = torch.empty((B, P, 3), dtype=torch.float32, device=dev)
+    hit_t = torch.empty((B, P), dtype=torch.float32, device=dev)
+    hit_cell = torch.empty((B, P), dtype=torch.int32, device=dev)
+    rs = _rays_struct(origins, dirs)
+    bg = (C.c_float * 3)(*(float(v) for v in background))
+    L.check(L.lib().cnerf_voxel_first_hit(B, P, C.byref(rs), L.ptr(voxels), G, _cube_lo(lo), float(side), code, float(t_min), float(t_max),
+                                          int(num_steps), bg, L.ptr(pixels), L.ptr(hit_t), L.ptr(hit_cell), _stream()), "cnerf_voxel_first_hit")
+    return (pixels[0], hit_t[0], hit_cell[0]) if single else (pixels, hit_t, hit_cell)
 
 
 def render_rays_forward(net, levels, freq, phase, origins, dirs, o, rng=None, want_aux=False, aux_keys=None, occupancy=None, near=None, far=None):

@@ -132,6 +132,12 @@ class GanTrainer:
         # one latent per object instead of the U-Net encoding sample["voxel"]
         self.load_pcl = bool(metadata.get("dataset", {}).get("load_pcl", False))
         self.input_key = "pcl" if self.load_pcl else "voxel"
+        # metadata["dataset"]["voxelize_pcl"] (default off; U-Net encoder only): the batch carries clouds, sample["pcl"] (B, T, 6), and
+        # every step voxelises them on the device at metadata["voxel_resolution"] (voxels.voxelize_cloud) -- the reference's offline
+        # pcl2voxel.py, with its noise_xyz / noise_color augmentation drawn afresh per step, over the 1.2 cube of the reference's files
+        self.voxelize_pcl = bool(metadata.get("dataset", {}).get("voxelize_pcl", False))
+        if self.voxelize_pcl and self.load_pcl:
+            raise ValueError("metadata['dataset']: voxelize_pcl feeds the voxel encoder and load_pcl the point-cloud encoder: set one of them")
         if "encoder" in modules:
             self.encoder = modules["encoder"].to(device)
         elif self.load_pcl:
@@ -198,6 +204,16 @@ class GanTrainer:
         self.alpha = min(1.0, (step - step_last_upsample) / self.metadata["fade_steps"]) if self.metadata["fade_steps"] > 0 else 1.0
         self.metadata["nerf_noise"] = max(0.0, 1.0 - step / 5000.0)
 
+    def _with_voxels(self, sample):
+        """voxelize_pcl: `sample` with "voxel" (B,4,V,V,V) made from sample["pcl"], V = metadata["voxel_resolution"]; a sample that
+        already has its grids, and every sample with the switch off, is returned as it is."""
+        if not self.voxelize_pcl or "voxel" in sample:
+            return sample
+        from ..voxels import voxelize_cloud
+        md = self.metadata
+        vox = voxelize_cloud(sample["pcl"].to(self.device), md.get("voxel_resolution", 64), 1.2, md.get("noise_xyz", 0.0), md.get("noise_color", 0.0))
+        return {**sample, "voxel": vox}
+
     def _encode(self, voxels):
         """The 3D U-Net.  metadata["encoder_autocast"] = "bf16" / "fp16" runs its convolutions under torch.autocast, as the
         reference's GPU training does with the whole step (utils.py:327,643: autocast + GradScaler; bf16 needs no scaler); the
@@ -227,6 +243,7 @@ class GanTrainer:
     # utils.py:743-842
     def train_discriminator(self, sample):
         md = self.metadata
+        sample = self._with_voxels(sample)
         real = sample["img"].to(self.device).requires_grad_(True)
         voxels = sample[self.input_key].to(self.device)
         n = real.shape[0]
@@ -257,6 +274,7 @@ class GanTrainer:
     # utils.py:621-741
     def train_generator(self, sample):
         md = self.metadata
+        sample = self._with_voxels(sample)
         imgs, cams, voxels = (sample[k].to(self.device) for k in ("img", "cam2world", self.input_key))
         chunks = self._chunks(imgs.shape[0])
         g_acc = p_acc = r_acc = 0.0
@@ -315,6 +333,7 @@ class GanTrainer:
         ranks after a barrier: MIOpen keeps its find results in the user database (MIOPEN_USER_DB_PATH, one directory per
         node), so ranks 1..N-1 read rank 0's results instead of each repeating the search concurrently."""
         md = self.metadata
+        sample = self._with_voxels(sample)
         n = sample["img"].shape[0]
         c = self._chunks(n)[0]
         if not self.load_pcl:      # (a PointNet has no convolutions)
@@ -340,6 +359,7 @@ class GanTrainer:
         DDP the last of several chunks is left out: its forward must be the one directly followed by the backward that all-reduces."""
         self.set_alpha()
         self._z = {}
+        sample = self._with_voxels(sample)       # voxelize_pcl: once per step, so both passes see the same grids (and the same noise draw)
         if self.metadata["enable_discriminator"] and self.metadata.get("reuse_encoder_output", True):
             voxels = sample[self.input_key].to(self.device)
             chunks = self._chunks(voxels.shape[0])

@@ -789,6 +789,59 @@ int cnerf_nearest_points(int32_t B, int64_t n, int64_t m, const float* queries /
                          int32_t target_splits /* 0 = chosen by the library, else 1..1024 */,
                          float* dist2 /* (B,n) */, int32_t* idx /* (B,n) */, void* workspace, void* stream);
 
+/* ---- voxel grids of coloured point clouds, and their first-hit pictures (added in ABI v10 without a version change: additive symbols
+ * only) ---------------------------------------------------------------------------------------------------------------------------
+ * Every feature-volume generator is conditioned on a grid (B,4,G,G,G) = [occupancy, r, g, b] that the 3D U-Net encodes.  The reference
+ * makes it offline (feature_volume/pcl2voxel.py: open3d's VoxelGrid and a Python loop, one file per resolution) and pictures it with
+ * feature_volume/voxel2img.py.  These entries do both on the device, from the cloud the other shape entries already take.
+ *
+ * Layouts.  layout 0: voxels (B,4,G,G,G) indexed [b, ch, iz, iy, ix] -- what the encoder takes, the reference's .permute(3,2,1,0) --
+ *   counts (B,G,G,G) indexed [b, iz, iy, ix].  layout 1: voxels (B,G,G,G,4) indexed [b, ix, iy, iz, ch] -- the order of voxel.npz --
+ *   counts [b, ix, iy, iz]; voxels 16-byte aligned.  ch = occupancy, r, g, b; (x, y, z, r, g, b) are columns 0..5 of a point's row.
+ * Cube.  Corner lo[3], edge side > 0, G cells per axis, G in [2,256]; inv = (float)G / side, formed once on the host.
+ *
+ * cnerf_voxelize.  points (B,n,stride) fp32, stride >= 6, n < 2^28; n_points (B) DEVICE int32 clamped to [0,n], NULL = n (as in
+ *   cnerf_nearest_points): rows at or beyond it are not read.  fp32, every operation rounded on its own:
+ *     - a point with a NaN in x, y or z is skipped;
+ *     - clip_margin = m >= 0 (the reference: 1e-4): per axis p' = fminf(fmaxf(p, lo + m), (lo + side) - m), t = (p' - lo) * inv, the
+ *       cell is floor(t) clamped into [0, G-1]: no other point is skipped, an infinite coordinate lands in a border cell;
+ *     - clip_margin < 0: no clipping, t = (p - lo) * inv, a point with t outside [0, G) on any axis is skipped (an infinity with it),
+ *       otherwise the cell is floor(t) -- the rule of cnerf_occupancy_compact;
+ *     - colour per channel q = (uint32) rintf(fminf(fmaxf(c, 0), 1) * 16777216.0f), a NaN colour counts as 0.
+ *   Per cell the count of its points and the three sums S_c of their q are EXACT integers (64-bit, below 2^52).  Output per cell:
+ *   occupancy = count > 0 ? 1 : 0, colour = (float)((double)S_c / ((double)count * 16777216.0)), 0 in an empty cell.  Every element
+ *   of voxels is written; counts (may be NULL) gets the count.
+ *   Reproducibility.  Integer sums do not depend on the order of addition, so the outputs are the same bits for every launch geometry
+ *   and every run, although the sums are formed by atomics.  That is the point of the fixed-point form: a float atomic sum depends on
+ *   the order in which the adds arrive.  The quantisation moves a colour by at most 2^-25.
+ *   cnerf_voxelize_bytes: the workspace, 32 bytes per cell and image (four 64-bit integers), 16-byte aligned; its contents are scratch.
+ *   CNERF_EINVAL before any launch: B < 1, n < 1, n >= 2^28, stride < 6, G outside [2,256], side not finite or <= 0 (or so small
+ *   that inv is not finite), a non-finite lo,
+ *   a NaN clip_margin, 2 clip_margin >= side, layout outside {0,1}, points / voxels / workspace / lo NULL, a misaligned buffer.
+ *
+ * cnerf_voxel_first_hit.  The picture of a grid: along each ray the colour of the first occupied cell among S samples, else the
+ *   background.  voxels in either layout; rays (B,P,3) origins and dirs, directions not normalised (t in units of |dir|); S in [2,1024].
+ *     t_s = element s of torch.linspace(t_min, t_max, S) as ATen computes it in fp32 (the coarse depths of cnerf_render_rays_forward);
+ *     p = o + d * t_s per component, the product rounded, then the sum, no fma;  t = (p - lo) * inv per axis;
+ *     the sample is INSIDE iff 0 <= t < G on all three axes (a NaN is not inside), its cell is floor(t); it is OCCUPIED iff it is inside
+ *     and the cell's occupancy value != 0 (so a NaN occupancy is occupied).
+ *   The first occupied sample in ascending s gives pixels = the cell's (r, g, b) as stored -- the grid's own range, NOT 2 rgb - 1 --,
+ *   hit_t = t_s, hit_cell = (ix G + iy) G + iz (in both layouts).  None: pixels = background, hit_t = +inf, hit_cell = -1.
+ *   A sample outside the cube sees nothing.  The reference's grid_sample(padding_mode="border") smears the border voxels over all of
+ *   space; that is NOT reproduced.  Inside the cube, away from the cell faces, floor(t) is the reference's nearest voxel
+ *   (mode="nearest", align_corners=False: rint(t - 0.5)).
+ *   One lane per ray, no atomics; the outputs depend on nothing but the inputs.  hit_t / hit_cell may be NULL.
+ *   CNERF_EINVAL before the launch: the B, G, lo, side, layout checks above; rays_per_image < 1; S outside [2,1024]; t_min or t_max not
+ *   finite, t_max <= t_min; rays / origins / dirs / voxels / background / pixels NULL.
+ * All are asynchronous on `stream`, allocate nothing and synchronise nothing.  Forward only. */
+int cnerf_voxelize_bytes(int32_t B, int32_t G, size_t* workspace);
+int cnerf_voxelize(int32_t B, int64_t n, int32_t stride, const float* points /* (B,n,stride) */, const int32_t* n_points /* (B) DEVICE or NULL = n */,
+                   int32_t G, const float lo[3], float side, float clip_margin /* >= 0 clips, < 0 does not */, int32_t layout,
+                   float* voxels, int32_t* counts /* (B,G,G,G) or NULL */, void* workspace, void* stream);
+int cnerf_voxel_first_hit(int32_t B, int64_t rays_per_image, const cnerf_rays* rays, const float* voxels, int32_t G, const float lo[3], float side,
+                          int32_t layout, float t_min, float t_max, int32_t S, const float background[3],
+                          float* pixels /* (B,P,3) */, float* hit_t /* (B,P) or NULL */, int32_t* hit_cell /* (B,P) or NULL */, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -31,6 +31,9 @@ def main():
                          "whole batch at once (0.218 s/step against 0.267 with 4 chunks at batch 8)")
     ap.add_argument("--voxel-res", type=int, default=64)
     ap.add_argument("--pcl-points", type=int, default=2048, help="points per synthetic cloud (B, T, 6) of the point-cloud setting (--siren-type SHORTSIREN)")
+    ap.add_argument("--voxelize-clouds", action="store_true",
+                    help="feed a voxel-conditioned generator from point clouds: the batch carries (B, T, 6) clouds (--pcl-points) and every step "
+                         "voxelises them on the GPU at --voxel-res (metadata dataset.voxelize_pcl), instead of reading ready-made grids")
     ap.add_argument("--siren-type", default="SHORTSIREN_FG")
     ap.add_argument("--hidden", type=int, default=256)
     ap.add_argument("--precision", default="fp16x3", choices=["fp32", "fp16x3"],
@@ -76,6 +79,12 @@ def main():
     md["render_precision"] = args.precision
     md["backward_precision"] = args.backward_precision
     pcl_points = args.pcl_points if md.get("dataset", {}).get("load_pcl") else 0
+    if args.voxelize_clouds:
+        if pcl_points:
+            raise SystemExit("--voxelize-clouds feeds the voxel encoder: not available with the point-cloud setting")
+        md.setdefault("dataset", {})["voxelize_pcl"] = True
+        md["voxel_resolution"] = args.voxel_res
+        pcl_points = args.pcl_points
     md["encoder_autocast"] = args.encoder_autocast
     md["enable_discriminator"] = not args.no_discriminator
     for k in ("gen_lr", "disc_lr", "enc_lr"):
@@ -95,7 +104,7 @@ def main():
         from cnerf_amd.training.encoder import UNet3D
         torch.manual_seed(4321)                       # the same teacher on every rank
         if pcl_points:
-            raise SystemExit("--teacher renders voxel grids: not available with the point-cloud setting")
+            raise SystemExit("--teacher renders voxel grids: not available with the point-cloud setting or --voxelize-clouds")
         t_enc = UNet3D(**md["unet"]).to(dev).eval()
         t_gen = ImplicitGenerator3d(**md["generator"]).to(dev).eval()
         t_gen.set_device(dev)
