@@ -10,5 +10,6 @@ from . import _lib, ops  # noqa: F401
 from .generators import ImplicitGenerator3d  # noqa: F401
 from . import shape_metrics  # noqa: F401,E402
 from . import voxels  # noqa: F401,E402
+from . import views  # noqa: F401,E402
 
-__all__ = ["ImplicitGenerator3d", "ops", "generators", "shape_metrics", "voxels"]
+__all__ = ["ImplicitGenerator3d", "ops", "generators", "shape_metrics", "voxels", "views"]

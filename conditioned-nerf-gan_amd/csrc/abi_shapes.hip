@@ -1,4 +1,4 @@
-// C ABI (include/cnerf.h), shapes: isosurface meshes, nearest points, voxel grids of point clouds.
+// C ABI (include/cnerf.h), shapes: isosurface meshes, nearest points, voxel grids of point clouds, depth maps <-> clouds.
 #include "abi_common.hpp"
 
 using namespace cnerf;
@@ -92,7 +92,87 @@ int check_voxel_cube(int G, const float* lo, float side, int layout, const char*
 size_t voxelize_bytes(int B, int G) { return align256((size_t)B * G * G * G * 4 * sizeof(unsigned long long)); }
 }  // namespace
 
+// ---------------------------------------------------------------------------------------------------------------------
+// depth maps <-> clouds: back-projection and the z-buffered splat (csrc/reproject.hip)
+// ---------------------------------------------------------------------------------------------------------------------
+namespace {
+// views (per image: B = 1 for the back-projection) of R x R pixels
+int check_view_grid(int B, int V, int R, const char* who) {
+    if (B < 1) return fail(CNERF_EINVAL, "%s: B=%d must be >= 1", who, B);
+    if (V < 1) return fail(CNERF_EINVAL, "%s: V=%d must be >= 1", who, V);
+    if (R < 2 || R > 2048) return fail(CNERF_EINVAL, "%s: R=%d out of range [2,2048]", who, R);
+    if ((long long)V * R * R >= (1LL << 31) / B) return fail(CNERF_EINVAL, "%s: B V R R = %d x %d x %d x %d must be below 2^31", who, B, V, R, R);
+    return CNERF_OK;
+}
+int check_pinhole(float focal, float z_min, float z_max, const char* who) {
+    if (!(focal > 0.0f) || !(focal < INFINITY)) return fail(CNERF_EINVAL, "%s: focal=%g must be > 0 and finite", who, (double)focal);
+    if (!(z_min >= 0.0f) || !(z_min < INFINITY)) return fail(CNERF_EINVAL, "%s: z_min=%g must be >= 0 and finite", who, (double)z_min);
+    if (!(z_max > z_min) || !(z_max < INFINITY)) return fail(CNERF_EINVAL, "%s: z_max=%g must be finite and greater than z_min=%g", who, (double)z_max, (double)z_min);
+    return CNERF_OK;
+}
+// the chunk counts of every view, then the total
+size_t backproject_bytes(int V, int R) { return align256(((size_t)V * bp_chunks(R) + 1) * sizeof(int32_t)); }
+// one 64-bit key per pixel
+size_t splat_bytes(int B, int V, int R) { return align256((size_t)B * V * R * R * sizeof(unsigned long long)); }
+}  // namespace
+
 extern "C" {
+
+int cnerf_backproject_bytes(int32_t V, int32_t R, size_t* workspace) {
+    g_err[0] = 0;
+    if (int rc = check_view_grid(1, V, R, "backproject_bytes")) return rc;
+    if (workspace) *workspace = backproject_bytes(V, R);
+    return CNERF_OK;
+}
+
+int cnerf_backproject(int32_t V, int32_t R, const float* depth, const float* colors, int32_t color_layout, const float* mask, float mask_min,
+                      const float* cam2world, float focal, float z_min, float z_max, float color_scale, float color_offset, float* points,
+                      int32_t* counts, int32_t* pixel, int32_t* rank, void* workspace, void* stream) {
+    g_err[0] = 0;
+    const char* who = "backproject";
+    if (int rc = check_view_grid(1, V, R, who)) return rc;
+    if (int rc = check_pinhole(focal, z_min, z_max, who)) return rc;
+    if (mask_min != mask_min) return fail(CNERF_EINVAL, "%s: mask_min is NaN", who);
+    if (color_scale != color_scale || color_offset != color_offset) return fail(CNERF_EINVAL, "%s: color_scale / color_offset is NaN", who);
+    if (color_layout != 0 && color_layout != 1) return fail(CNERF_EINVAL, "%s: color_layout=%d must be 0 (V,3,R,R) or 1 (V,R,R,3)", who, color_layout);
+    if (!depth || !cam2world || !points || !workspace) return fail(CNERF_EINVAL, "%s: NULL argument (depth / cam2world / points / workspace)", who);
+    BackprojectArgs a{};
+    a.V = V, a.R = R, a.chunks = bp_chunks(R), a.depth = depth, a.colors = colors, a.color_layout = color_layout, a.mask = mask, a.cam2world = cam2world;
+    a.focal = focal, a.z_min = z_min, a.z_max = z_max, a.mask_min = mask_min, a.color_scale = color_scale, a.color_offset = color_offset;
+    a.points = points, a.out_stride = colors ? 6 : 3, a.counts = counts, a.pixel = pixel, a.rank = rank, a.chunk_counts = (int32_t*)workspace;
+    if (hipError_t e = launch_backproject(a, (hipStream_t)stream)) return hip_fail(e, "backproject");
+    return CNERF_OK;
+}
+
+int cnerf_splat_points_bytes(int32_t B, int32_t V, int32_t R, size_t* workspace) {
+    g_err[0] = 0;
+    if (int rc = check_view_grid(B, V, R, "splat_points_bytes")) return rc;
+    if (workspace) *workspace = splat_bytes(B, V, R);
+    return CNERF_OK;
+}
+
+int cnerf_splat_points(int32_t B, int64_t n, int32_t stride, const float* points, const int32_t* n_points, int32_t V, const float* cam2world, int32_t R,
+                       float focal, float z_min, float z_max, int32_t radius, const float background[3], float* depth, int32_t* index, float* pixels,
+                       void* workspace, void* stream) {
+    g_err[0] = 0;
+    const char* who = "splat_points";
+    if (int rc = check_view_grid(B, V, R, who)) return rc;
+    if (n < 1 || n >= (1LL << 28)) return fail(CNERF_EINVAL, "%s: n=%lld out of range [1,2^28)", who, (long long)n);
+    if (stride < 3) return fail(CNERF_EINVAL, "%s: stride=%d must be >= 3 (xyz)", who, stride);
+    if (pixels && stride < 6) return fail(CNERF_EINVAL, "%s: pixels need stride >= 6 (xyz rgb), got stride=%d", who, stride);
+    if (radius < 0 || radius > 8) return fail(CNERF_EINVAL, "%s: radius=%d out of range [0,8]", who, radius);
+    if (int rc = check_pinhole(focal, z_min, z_max, who)) return rc;
+    if (!points || !cam2world || !workspace) return fail(CNERF_EINVAL, "%s: NULL argument (points / cam2world / workspace)", who);
+    if (pixels && !background) return fail(CNERF_EINVAL, "%s: background is NULL and pixels are asked for", who);
+    if ((uintptr_t)workspace & 7) return fail(CNERF_EINVAL, "%s: workspace must be 8-byte aligned", who);
+    SplatArgs a{};
+    a.B = B, a.n = (long long)n, a.stride = stride, a.points = points, a.n_points = n_points, a.V = V, a.R = R, a.cam2world = cam2world;
+    a.focal = focal, a.z_min = z_min, a.z_max = z_max, a.radius = radius;
+    for (int c = 0; c < 3; ++c) a.background[c] = background ? background[c] : 0.0f;
+    a.depth = depth, a.index = index, a.pixels = pixels, a.keys = (unsigned long long*)workspace;
+    if (hipError_t e = launch_splat_points(a, (hipStream_t)stream)) return hip_fail(e, "splat_points");
+    return CNERF_OK;
+}
 
 int cnerf_voxelize_bytes(int32_t B, int32_t G, size_t* workspace) {
     g_err[0] = 0;

@@ -392,6 +392,44 @@ struct VoxelHitArgs {
 hipError_t launch_voxelize(const VoxelizeArgs& a, hipStream_t stream);
 hipError_t launch_voxel_first_hit(const VoxelHitArgs& a, hipStream_t stream);
 
+// reproject.hip: depth maps -> one fused cloud, and the z-buffered picture of a cloud (include/cnerf.h states the contracts, DESIGN.md 3.22 the design)
+constexpr int BP_CHUNK = 256;        // pixels of a view one block counts and emits, one per lane
+inline int bp_chunks(int R) { return (R * R + BP_CHUNK - 1) / BP_CHUNK; }
+struct BackprojectArgs {
+    int V, R;
+    int chunks;                // bp_chunks(R): blocks per view
+    const float* depth;        // (V,R,R)
+    const float* colors;       // (V,3,R,R) in layout 0, (V,R,R,3) in layout 1, or null
+    int color_layout;
+    const float* mask;         // (V,R,R) or null
+    const float* cam2world;    // (V,16)
+    float focal, z_min, z_max, mask_min, color_scale, color_offset;
+    float* points;             // (V R R, out_stride): the valid pixels' rows at the front, in ascending (v, row, col)
+    int out_stride;            // 6 with colours, else 3
+    int32_t* counts;           // (V) or null
+    int32_t* pixel;            // (V R R) or null: (v R + row) R + col of every row of the cloud
+    int32_t* rank;             // (V,R,R) or null: the pixel's row in the cloud, -1 = not valid
+    int32_t* chunk_counts;     // workspace (V chunks + 1): valid pixels per chunk, then their exclusive offsets and the total
+};
+struct SplatArgs {
+    int B;
+    long long n;               // rows per image, < 2^28
+    int stride;                // floats per row, >= 3; 6 or more with pixels
+    const float* points;       // (B,n,stride)
+    const int32_t* n_points;   // (B) or null
+    int V, R;
+    const float* cam2world;    // (B,V,16)
+    float focal, z_min, z_max;
+    int radius;
+    float background[3];
+    float* depth;              // (B,V,R,R) or null
+    int32_t* index;            // (B,V,R,R) or null
+    float* pixels;             // (B,V,R,R,3) or null
+    unsigned long long* keys;  // workspace (B,V,R,R): bits(z) << 32 | point index of the nearest point so far
+};
+hipError_t launch_backproject(const BackprojectArgs& a, hipStream_t stream);
+hipError_t launch_splat_points(const SplatArgs& a, hipStream_t stream);
+
 hipError_t launch_philox_fill(const PhiloxKey& k, uint32_t stream_id, long long n, int normal, float* out, hipStream_t stream);
 hipError_t launch_transpose_cl(int B, int C, int V, const float* src, float* dst, bool to_channel_last, hipStream_t stream);
 

@@ -936,6 +936,105 @@ def voxel_first_hit(voxels, origins, dirs, lo, side, t_min, t_max, num_steps, ba
     return (pixels[0], hit_t[0], hit_cell[0]) if single else (pixels, hit_t, hit_cell)
 
 
+COLOR_LAYOUTS = {"chw": 0, "hwc": 1}
+
+
+def _cams16(cam2worlds, lead, who):
+    """cam2world matrices (*lead,4,4) or (*lead,16) -> contiguous float32 (*lead,16)."""
+    c = _f32(cam2worlds.detach())
+    if tuple(c.shape) == tuple(lead) + (4, 4):
+        c = c.reshape(*lead, 16)
+    if tuple(c.shape) != tuple(lead) + (16,):
+        raise L.CnerfError(f"{who}: cam2worlds must be {tuple(lead) + (4, 4)}, got {tuple(cam2worlds.shape)}")
+    return c.contiguous()
+
+
+def backproject(depth, cam2worlds, focal, z_min, z_max, colors=None, color_layout="chw", color_scale=1.0, color_offset=0.0, mask=None, mask_min=0.0,
+                want_pixel=False, want_rank=False):
+    """cnerf_backproject: V depth maps (V,R,R) with their cameras (V,4,4) -> ONE cloud in world space.  A pixel is valid iff
+    z_min < depth < z_max (both strict, a NaN is not) and, with mask (V,R,R), mask > mask_min; a valid pixel gives the row
+    [x, y, z] -- [x, y, z, r, g, b] with colors, (V,3,R,R) as "chw" (the generator's pixels) or (V,R,R,3) as "hwc", each channel
+    c * color_scale + color_offset -- and the rows come in ascending (view, row, col).  focal: 1 / tan(fov / 2) in fp32, as
+    volumetric_rendering.pinhole_rays forms it.
+    -> points (n, 6 or 3) float32, counts (V,) int32 on the device (valid pixels per view, summing to n), then with want_pixel
+    pixel (n,) int32 = (v R + row) R + col of every row, and with want_rank rank (V,R,R) int32 = the pixel's row in the cloud or -1.
+    Reading n back is the one synchronisation.  Forward only: the inputs are detached, the outputs carry no gradient."""
+    if not (depth.is_cuda and cam2worlds.is_cuda):
+        raise L.CnerfError("backproject: depth and cam2worlds must be on the GPU (there is no CPU fallback)")
+    depth = _f32(depth.detach())
+    if depth.dim() != 3 or depth.shape[1] != depth.shape[2]:
+        raise L.CnerfError(f"backproject: depth must be (V,R,R), got {tuple(depth.shape)}")
+    if color_layout not in COLOR_LAYOUTS:
+        raise L.CnerfError(f"backproject: color_layout must be 'chw' (V,3,R,R) or 'hwc' (V,R,R,3), got {color_layout!r}")
+    code = COLOR_LAYOUTS[color_layout]
+    V, R = int(depth.shape[0]), int(depth.shape[1])
+    dev = depth.device
+    cams = _cams16(cam2worlds, (V,), "backproject")
+    if colors is not None:
+        colors = _f32(colors.detach())
+        if tuple(colors.shape) != ((V, 3, R, R) if code == 0 else (V, R, R, 3)):
+            raise L.CnerfError(f"backproject: colors must be {(V, 3, R, R) if code == 0 else (V, R, R, 3)} as {color_layout!r}, got {tuple(colors.shape)}")
+    if mask is not None:
+        mask = _f32(mask.detach())
+        if mask.shape != depth.shape:
+            raise L.CnerfError(f"backproject: mask must be {tuple(depth.shape)}, got {tuple(mask.shape)}")
+    if any(t is not None and t.device != dev for t in (cams, colors, mask)):
+        raise L.CnerfError("backproject: all tensors must be on the same device")
+    lib = L.lib()
+    nb = C.c_size_t(0)
+    L.check(lib.cnerf_backproject_bytes(V, R, C.byref(nb)), "cnerf_backproject_bytes")
+    ws = torch.empty(nb.value, dtype=torch.uint8, device=dev)
+    points = torch.empty((V * R * R, 6 if colors is not None else 3), dtype=torch.float32, device=dev)
+    counts = torch.empty((V,), dtype=torch.int32, device=dev)
+    pixel = torch.empty((V * R * R,), dtype=torch.int32, device=dev) if want_pixel else None
+    rank = torch.empty((V, R, R), dtype=torch.int32, device=dev) if want_rank else None
+    L.check(lib.cnerf_backproject(V, R, L.ptr(depth), L.ptr(colors), code, L.ptr(mask), float(mask_min), L.ptr(cams), float(focal), float(z_min),
+                                  float(z_max), float(color_scale), float(color_offset), L.ptr(points), L.ptr(counts), L.ptr(pixel), L.ptr(rank),
+                                  L.ptr(ws), _stream()), "cnerf_backproject")
+    n = int(counts.sum().item())
+    out = (points[:n], counts)
+    if want_pixel:
+        out += (pixel[:n],)
+    if want_rank:
+        out += (rank,)
+    return out
+
+
+def splat_points(points, cam2worlds, R, focal, z_min, z_max, radius=0, lengths=None, background=(1.0, 1.0, 1.0), want_pixels=True):
+    """cnerf_splat_points: the z-buffered picture of a cloud.  points (B,n,stride >= 3) = [x, y, z, (r, g, b, ...)] in world space,
+    cam2worlds (B,V,4,4) with rotations in their 3x3 blocks.  A point with camera-space depth z_min < z < z_max lands on the pixel
+    nearest to its projection and covers the (2 radius + 1)^2 pixels around it; per pixel the nearest point wins, at equal depth the
+    lowest index.  lengths (B,): how many leading rows of each cloud count.
+    -> depth (B,V,R,R) float32, 0 where nothing landed; index (B,V,R,R) int32, the winner's row or -1; pixels (B,V,R,R,3), the
+    winner's colour as stored or `background` (None with want_pixels=False; colours need stride >= 6).  The result is the same
+    bits on every run.  Forward only: the inputs are detached, the outputs carry no gradient."""
+    if not (points.is_cuda and cam2worlds.is_cuda):
+        raise L.CnerfError("splat_points: points and cam2worlds must be on the GPU (there is no CPU fallback)")
+    points = _f32(points.detach())
+    if points.dim() != 3 or points.shape[-1] < 3:
+        raise L.CnerfError(f"splat_points: points must be (B,n,3 or more), got {tuple(points.shape)}")
+    B, n, stride = (int(s) for s in points.shape)
+    if cam2worlds.dim() < 3 or cam2worlds.shape[0] != B:
+        raise L.CnerfError(f"splat_points: cam2worlds must be (B={B},V,4,4), got {tuple(cam2worlds.shape)}")
+    V, R = int(cam2worlds.shape[1]), int(R)
+    cams = _cams16(cam2worlds, (B, V), "splat_points")
+    dev = points.device
+    if cams.device != dev:
+        raise L.CnerfError("splat_points: points and cam2worlds must be on the same device")
+    np_ = _cloud_lengths(lengths, B, dev, "lengths", "splat_points")
+    lib = L.lib()
+    nb = C.c_size_t(0)
+    L.check(lib.cnerf_splat_points_bytes(B, V, R, C.byref(nb)), "cnerf_splat_points_bytes")
+    ws = torch.empty(nb.value, dtype=torch.uint8, device=dev)
+    depth = torch.empty((B, V, R, R), dtype=torch.float32, device=dev)
+    index = torch.empty((B, V, R, R), dtype=torch.int32, device=dev)
+    pixels = torch.empty((B, V, R, R, 3), dtype=torch.float32, device=dev) if want_pixels else None
+    bg = (C.c_float * 3)(*(float(v) for v in background))
+    L.check(lib.cnerf_splat_points(B, n, stride, L.ptr(points), L.ptr(np_), V, L.ptr(cams), R, float(focal), float(z_min), float(z_max), int(radius), bg,
+                                   L.ptr(depth), L.ptr(index), L.ptr(pixels), L.ptr(ws), _stream()), "cnerf_splat_points")
+    return depth, index, pixels
+
+
 def render_rays_forward(net, levels, freq, phase, origins, dirs, o, rng=None, want_aux=False, aux_keys=None, occupancy=None, near=None, far=None):
     """cnerf_render_rays_forward on channel-last levels: origins / dirs (B,P,3) -> pixels (B,P,3), dist (B,P), aux dict.
     occupancy (an OccupancyGrid with one grid per image): cnerf_render_rays_masked_forward instead -- samples in cells whose bit is

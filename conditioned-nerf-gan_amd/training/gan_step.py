@@ -102,6 +102,15 @@ def default_metadata(img_size=128, num_steps=64, batch_size=8, batch_split=4, si
     }
 
 
+def loss_depth(gt, pred):
+    """The reference's depth term (utils.py:96-99): the mean squared difference over the foreground pixels of the target, gt != 0
+    (0 is "no surface here": a background pixel of a depth image).  No such pixel: 0, connected to pred (the reference's mean over
+    nothing is a NaN)."""
+    fg = gt != 0
+    d = (gt - pred)[fg]
+    return d.square().mean() if d.numel() else pred.sum() * 0.0
+
+
 class GanTrainer:
     """metadata["discriminator"] names the class (ProgressiveDiscriminator, the reference's default, or CCSDiscriminator);
     `modules` lets a caller hand in ready-made generator / encoder / discriminator modules (tests: a CPU stand-in generator
@@ -138,6 +147,13 @@ class GanTrainer:
         self.voxelize_pcl = bool(metadata.get("dataset", {}).get("voxelize_pcl", False))
         if self.voxelize_pcl and self.load_pcl:
             raise ValueError("metadata['dataset']: voxelize_pcl feeds the voxel encoder and load_pcl the point-cloud encoder: set one of them")
+        # metadata["depth_loss"] (default off) with ["depth_loss_weight"] (default 1): the reference's depth term in the generator step
+        # (utils.py:684-705), loss_depth between the target and the rendered depth.  The target is sample["depth"] (B,R,R) where the
+        # batch has one -- the reference's EXR files -- and otherwise the z-buffered depth image of the clouds the scenes are conditioned on,
+        # sample["pcl"], from the batch's cameras (views.splat_cloud, footprint metadata["depth_splat_radius"], default 1), made once
+        # per step under no_grad.  That image is a PROXY: where the footprints of a sparse cloud do not close the surface, a pixel sees
+        # the object's far side, so the radius must suit the cloud's density at img_size.
+        self.depth_loss = bool(metadata.get("depth_loss", False))
         if "encoder" in modules:
             self.encoder = modules["encoder"].to(device)
         elif self.load_pcl:
@@ -214,6 +230,18 @@ class GanTrainer:
         vox = voxelize_cloud(sample["pcl"].to(self.device), md.get("voxel_resolution", 64), 1.2, md.get("noise_xyz", 0.0), md.get("noise_color", 0.0))
         return {**sample, "voxel": vox}
 
+    def _depth_target(self, sample, cams):
+        """depth_loss: the target (B,R,R) of the generator step -- sample["depth"], or the splat of sample["pcl"] (see __init__)."""
+        if "depth" in sample:
+            return sample["depth"].to(self.device)
+        if "pcl" not in sample:
+            raise ValueError("metadata['depth_loss'] needs sample['depth'] (B,R,R) or sample['pcl'] (B,T,6) in the batch")
+        from ..views import splat_cloud
+        md = self.metadata
+        with torch.no_grad():
+            return splat_cloud(sample["pcl"].to(self.device), cams, md["img_size"], md["fov"], md["ray_start"], md["ray_end"],
+                               radius=md.get("depth_splat_radius", 1))[1][:, 0]
+
     def _encode(self, voxels):
         """The 3D U-Net.  metadata["encoder_autocast"] = "bf16" / "fp16" runs its convolutions under torch.autocast, as the
         reference's GPU training does with the whole step (utils.py:327,643: autocast + GradScaler; bf16 needs no scaler); the
@@ -277,7 +305,8 @@ class GanTrainer:
         sample = self._with_voxels(sample)
         imgs, cams, voxels = (sample[k].to(self.device) for k in ("img", "cam2world", self.input_key))
         chunks = self._chunks(imgs.shape[0])
-        g_acc = p_acc = r_acc = 0.0
+        g_acc = p_acc = r_acc = d_acc = 0.0
+        depth_gt = self._depth_target(sample, cams) if self.depth_loss else None
         d_params = [p for p in self.discriminator.parameters() if p.requires_grad]
         for p in d_params:                  # see _disc(frozen=True)
             p.requires_grad_(False)
@@ -290,7 +319,7 @@ class GanTrainer:
                         ctx.enter_context(m.no_sync())
                 with ctx:
                     with self._phase("g_render_fwd" if i in self._z else "g_encoder_render_fwd"):
-                        gen_imgs, _ = self._render(voxels[c], cams[c], i, "g")
+                        gen_imgs, gen_depth = self._render(voxels[c], cams[c], i, "g")
                     with self._phase("g_disc_loss_fwd"):
                         if md["enable_discriminator"]:
                             loss_g = F.softplus(-self._disc(gen_imgs, frozen=True)).mean()
@@ -298,6 +327,10 @@ class GanTrainer:
                             loss_g = gen_imgs.new_zeros(())
                         photo = F.mse_loss(gen_imgs, imgs[c]) if md["photo_loss"] else gen_imgs.new_zeros(())
                     loss = loss_g + photo
+                    if self.depth_loss:    # utils.py:684-705
+                        depth_term = loss_depth(depth_gt[c], gen_depth)
+                        loss = loss + md.get("depth_loss_weight", 1.0) * depth_term
+                        d_acc += depth_term.item()
                     if self.load_pcl:      # utils.py:694-706: the latents' mean norm, weighted
                         loss = loss + md["z_reg_weight"] * self._z_reg
                         r_acc += self._z_reg.item()
@@ -318,6 +351,8 @@ class GanTrainer:
         self.last.update(g_loss=g_acc / len(chunks), photo_loss=p_acc / len(chunks))
         if self.load_pcl:
             self.last.update(z_reg=r_acc / len(chunks), z_reg_loss=md["z_reg_weight"] * r_acc / len(chunks))
+        if self.depth_loss:
+            self.last.update(depth_loss=d_acc / len(chunks))
         # half-precision render backward: (tile, matrix) blocks whose stored gradients left fp16's range and were clamped -- the
         # per-matrix scale comes from a sampled maximum (include/cnerf.h, cnerf_render_backward).  Non-zero: outlier gradients were
         # cut; train with backward_precision "fp32" if that matters.

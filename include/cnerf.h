@@ -842,6 +842,64 @@ int cnerf_voxel_first_hit(int32_t B, int64_t rays_per_image, const cnerf_rays* r
                           int32_t layout, float t_min, float t_max, int32_t S, const float background[3],
                           float* pixels /* (B,P,3) */, float* hit_t /* (B,P) or NULL */, int32_t* hit_cell /* (B,P) or NULL */, void* stream);
 
+/* ---- between depth images and world-space points: back-projection and the z-buffered splat (added in ABI v10 without a version
+ * change: additive symbols only) -----------------------------------------------------------------------------------------------
+ * cnerf_backproject fuses V rendered depth maps into one coloured cloud (the reference's Inferencer.render_pcl, inference.py:541-559,
+ * without its host code); cnerf_splat_points pictures a cloud from cameras with a z-buffer and returns the camera-space depth image
+ * that the reference's render_pcl_masked and loss_depth read from files.  Everything is fp32 and every operation is rounded on its own
+ * (no fma).  focal = fp32 1 / tan(fov / 2), formed by the caller as the render path forms it (2.187719 at 49.13 degrees; the
+ * reference's literal is 2.1875).  A cam2world is 16 floats, row-major 4x4, M[i][j]; its 3x3 block MUST be a rotation (a look-at
+ * matrix is): the splat inverts it by transposing.  This is not checked.  R in [2,2048], B V R R < 2^31.
+ *
+ * cnerf_backproject.  depth (V,R,R); colors NULL or (V,3,R,R) in color_layout 0 -- the generator's pixels -- / (V,R,R,3) in layout 1;
+ *   mask NULL or (V,R,R) fp32; cam2world (V,16).  Pixel (v,row,col) with z = depth[v,row,col] is VALID iff z_min < z && z < z_max
+ *   (both strict; a NaN is not valid) and, with a mask, mask[v,row,col] > mask_min (the reference: depth_gt > 1e-4).  For a valid pixel
+ *     xn = (float)(2 col - (R-1)) / (float)(R-1), yn likewise from row;   xc = (xn / focal) * z, yc = (yn / focal) * z;
+ *     world_i = ((M[i][0] xc + M[i][1] yc) + M[i][2] z) + M[i][3], i = 0..2;   colour_c = c * color_scale + color_offset
+ *   (the reference un-normalises with 0.5, 0.5).  points (V R R, 6) -- (V R R, 3) without colors -- gets the valid pixels' rows packed
+ *   at the front in ascending (v,row,col): ONE cloud over all views, the reference's torch.cat; the rows behind them are not written.
+ *   counts (V) int32 on the device: valid pixels per view (their sum is the cloud's length); pixel (V R R) int32: (v R + row) R + col
+ *   of every row of the cloud; rank (V,R,R) int32: the pixel's row in the cloud, -1 where it is not valid.  Each of the three may be NULL.
+ *   Count, scan, emit with ballots and popcounts over the flat pixel sequence; no atomics: the order is the pixels' own and the outputs
+ *   are the same bits for every launch geometry and every run.
+ *   cnerf_backproject_bytes: the workspace, one int32 per 256 pixels of every view and one more; its contents are scratch.
+ *   CNERF_EINVAL before any launch: V < 1, R outside [2,2048], V R R >= 2^31, focal not finite or <= 0, z_min not finite or < 0, z_max
+ *   not finite or <= z_min, a NaN mask_min / color_scale / color_offset, color_layout outside {0,1}, depth / cam2world / points /
+ *   workspace NULL.
+ *
+ * cnerf_splat_points.  points (B,n,stride) fp32, stride >= 3 (x, y, z first; r, g, b are columns 3..5 and need stride >= 6), n < 2^28;
+ *   n_points (B) DEVICE int32 clamped to [0,n], NULL = n (as in cnerf_voxelize); cam2world (B,V,16); radius in [0,8].  Per point i and
+ *   view, with t = (M[0][3], M[1][3], M[2][3]):
+ *     q = p - t;   cam_j = (q0 M[0][j] + q1 M[1][j]) + q2 M[2][j] (the transposed rotation);   z = cam_2;
+ *     the point is skipped unless z_min < z && z < z_max (a NaN coordinate fails).  z_min >= 0, so every kept z is a positive finite
+ *     float, and the bit patterns of positive floats order like their values;
+ *     half = 0.5f * (float)(R-1);   u = ((cam_0 * focal) / z) * half + half, v likewise from cam_1;
+ *     the point is skipped unless -(radius+1) < u && u < R + radius and the same for v (float compares: a NaN fails);
+ *     col = (int)rintf(u), row = (int)rintf(v);  the point covers the pixels (row + dr, col + dc), |dr|, |dc| <= radius, that lie in the
+ *     image, all with the point's own z.
+ *   Per pixel the winner is the smallest 64-bit key ((uint64)bits(z) << 32) | (uint32)i: the nearest point, at exactly equal z the
+ *   lowest index.  depth (B,V,R,R) = the winner's z, 0 where nothing landed (the reference's "0 = background": loss_depth's gt != 0 and
+ *   the mask's > 1e-4 rely on it); index (B,V,R,R) int32 = the winner's i, or -1; pixels (B,V,R,R,3) = the winner's columns 3..5 as
+ *   stored, or background[3].  Each of the three may be NULL.
+ *   Reproducibility.  The keys are reduced by 64-bit unsigned atomic minima.  A minimum does not depend on the order in which its
+ *   operands arrive, so the outputs are the same bits for every launch geometry and every run, although the order of the atomics is
+ *   not fixed.  (A float z-buffer without the index in the key would leave ties to the order of arrival.)
+ *   cnerf_splat_points_bytes: the workspace, 8 bytes per (b,view,row,col), 8-byte aligned; the entry sets it to all ones itself.
+ *   CNERF_EINVAL before any launch: B, V or n < 1, n >= 2^28, R outside [2,2048], B V R R >= 2^31, stride < 3, pixels with stride < 6,
+ *   radius outside [0,8], the focal / z_min / z_max checks above, points / cam2world / workspace NULL, background NULL with pixels.
+ * All are asynchronous on `stream`, allocate nothing and synchronise nothing.  Forward only. */
+int cnerf_backproject_bytes(int32_t V, int32_t R, size_t* workspace);
+int cnerf_backproject(int32_t V, int32_t R, const float* depth /* (V,R,R) */, const float* colors /* NULL, (V,3,R,R) or (V,R,R,3) */,
+                      int32_t color_layout, const float* mask /* (V,R,R) or NULL */, float mask_min, const float* cam2world /* (V,16) */,
+                      float focal, float z_min, float z_max, float color_scale, float color_offset,
+                      float* points /* (V R R, 6 or 3) */, int32_t* counts /* (V) DEVICE or NULL */, int32_t* pixel /* (V R R) or NULL */,
+                      int32_t* rank /* (V,R,R) or NULL */, void* workspace, void* stream);
+int cnerf_splat_points_bytes(int32_t B, int32_t V, int32_t R, size_t* workspace);
+int cnerf_splat_points(int32_t B, int64_t n, int32_t stride, const float* points /* (B,n,stride) */, const int32_t* n_points /* (B) DEVICE or NULL = n */,
+                       int32_t V, const float* cam2world /* (B,V,16) */, int32_t R, float focal, float z_min, float z_max, int32_t radius,
+                       const float background[3], float* depth /* (B,V,R,R) or NULL */, int32_t* index /* (B,V,R,R) or NULL */,
+                       float* pixels /* (B,V,R,R,3) or NULL */, void* workspace, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

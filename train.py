@@ -34,6 +34,11 @@ def main():
     ap.add_argument("--voxelize-clouds", action="store_true",
                     help="feed a voxel-conditioned generator from point clouds: the batch carries (B, T, 6) clouds (--pcl-points) and every step "
                          "voxelises them on the GPU at --voxel-res (metadata dataset.voxelize_pcl), instead of reading ready-made grids")
+    ap.add_argument("--depth-loss", action="store_true",
+                    help="add the reference's depth term to the generator step (metadata depth_loss): MSE between the rendered depth and the "
+                         "z-buffered depth image of the batch's clouds from the batch's cameras; needs clouds in the batch (--voxelize-clouds "
+                         "or the point-cloud setting)")
+    ap.add_argument("--depth-loss-weight", type=float, default=1.0, help="weight of the depth term (metadata depth_loss_weight)")
     ap.add_argument("--siren-type", default="SHORTSIREN_FG")
     ap.add_argument("--hidden", type=int, default=256)
     ap.add_argument("--precision", default="fp16x3", choices=["fp32", "fp16x3"],
@@ -85,6 +90,10 @@ def main():
         md.setdefault("dataset", {})["voxelize_pcl"] = True
         md["voxel_resolution"] = args.voxel_res
         pcl_points = args.pcl_points
+    if args.depth_loss:
+        if not pcl_points:
+            raise SystemExit("--depth-loss takes its target from the batch's clouds: use --voxelize-clouds or the point-cloud setting")
+        md["depth_loss"], md["depth_loss_weight"] = True, args.depth_loss_weight
     md["encoder_autocast"] = args.encoder_autocast
     md["enable_discriminator"] = not args.no_discriminator
     for k in ("gen_lr", "disc_lr", "enc_lr"):
@@ -167,7 +176,7 @@ def main():
         if rank == 0 and step % args.print_freq == 0:
             d_loss = trainer.losses["d"][-1] if trainer.losses["d"] else float("nan")        # (no D step without a discriminator)
             print(f"step {step}: D {d_loss:.4f}  G {trainer.losses['g'][-1]:.4f}  photo {trainer.losses['photo'][-1]:.4f}  "
-                  f"alpha {trainer.alpha:.3f}  nerf_noise {md['nerf_noise']:.3f}  sec/step {dt:.3f}  "
+                  f"{'depth %.4f  ' % trainer.last['depth_loss'] if 'depth_loss' in trainer.last else ''}alpha {trainer.alpha:.3f}  nerf_noise {md['nerf_noise']:.3f}  sec/step {dt:.3f}  "
                   f"({world * args.batch * args.img_size ** 2 * 2 / dt / 1e6:.2f} M rays/s rendered, D + G passes)", flush=True)
             if trainer.last.get("render_bwd_clamped_blocks"):
                 print(f"  warning: the fp16 render backward clamped gradients in {trainer.last['render_bwd_clamped_blocks']} (tile, matrix) blocks "
