@@ -1,4 +1,4 @@
-// C ABI (include/cnerf.h), shapes: isosurface meshes, nearest points, voxel grids of point clouds, depth maps <-> clouds.
+// C ABI (include/cnerf.h), shapes: isosurface meshes, nearest points, voxel grids of point clouds, depth maps <-> clouds, depth maps -> a TSDF lattice.
 #include "abi_common.hpp"
 
 using namespace cnerf;
@@ -171,6 +171,35 @@ int cnerf_splat_points(int32_t B, int64_t n, int32_t stride, const float* points
     for (int c = 0; c < 3; ++c) a.background[c] = background ? background[c] : 0.0f;
     a.depth = depth, a.index = index, a.pixels = pixels, a.keys = (unsigned long long*)workspace;
     if (hipError_t e = launch_splat_points(a, (hipStream_t)stream)) return hip_fail(e, "splat_points");
+    return CNERF_OK;
+}
+
+int cnerf_tsdf_integrate(int32_t n0, int32_t n1, int32_t n2, const float lo[3], float pitch, int32_t V, int32_t R, const float* depth, const float* colors,
+                         int32_t color_layout, float color_scale, float color_offset, const float* cam2world, float focal, float z_min, float z_max,
+                         float trunc, int32_t carve, int32_t hidden_min, float unseen, float* tsdf, int32_t* weight, float* rgb, void* stream) {
+    g_err[0] = 0;
+    const char* who = "tsdf_integrate";
+    if (int rc = check_iso_shape(n0, n1, n2, who)) return rc;
+    if (int rc = check_view_grid(1, V, R, who)) return rc;
+    if (!lo || !depth || !cam2world || !tsdf) return fail(CNERF_EINVAL, "%s: NULL argument (lo / depth / cam2world / tsdf)", who);
+    if (!(pitch > 0.0f) || !(pitch < INFINITY)) return fail(CNERF_EINVAL, "%s: pitch=%g must be > 0 and finite", who, (double)pitch);
+    for (int c = 0; c < 3; ++c)
+        if (!(fabsf(lo[c]) < INFINITY)) return fail(CNERF_EINVAL, "%s: lo[%d]=%g must be finite", who, c, (double)lo[c]);
+    if (!(trunc > 0.0f) || !(trunc < INFINITY)) return fail(CNERF_EINVAL, "%s: trunc=%g must be > 0 and finite", who, (double)trunc);
+    if (int rc = check_pinhole(focal, z_min, z_max, who)) return rc;
+    if (!(fabsf(unseen) < INFINITY)) return fail(CNERF_EINVAL, "%s: unseen=%g must be finite", who, (double)unseen);
+    if (!(fabsf(color_scale) < INFINITY)) return fail(CNERF_EINVAL, "%s: color_scale=%g must be finite", who, (double)color_scale);
+    if (!(fabsf(color_offset) < INFINITY)) return fail(CNERF_EINVAL, "%s: color_offset=%g must be finite", who, (double)color_offset);
+    if (color_layout != 0 && color_layout != 1) return fail(CNERF_EINVAL, "%s: color_layout=%d must be 0 (V,3,R,R) or 1 (V,R,R,3)", who, color_layout);
+    if (carve != 0 && carve != 1) return fail(CNERF_EINVAL, "%s: carve=%d must be 0 or 1", who, carve);
+    if (hidden_min < 0) return fail(CNERF_EINVAL, "%s: hidden_min=%d must be >= 0", who, hidden_min);
+    if (rgb && !colors) return fail(CNERF_EINVAL, "%s: rgb is asked for and colors is NULL", who);
+    TsdfArgs a{};
+    a.n0 = n0, a.n1 = n1, a.n2 = n2, a.pitch = pitch, a.V = V, a.R = R, a.depth = depth, a.colors = colors, a.color_layout = color_layout;
+    for (int c = 0; c < 3; ++c) a.lo[c] = lo[c];
+    a.color_scale = color_scale, a.color_offset = color_offset, a.cam2world = cam2world, a.focal = focal, a.z_min = z_min, a.z_max = z_max, a.trunc = trunc;
+    a.carve = carve, a.hidden_min = hidden_min, a.unseen = unseen, a.tsdf = tsdf, a.weight = weight, a.rgb = rgb;
+    if (hipError_t e = launch_tsdf_integrate(a, (hipStream_t)stream)) return hip_fail(e, "tsdf_integrate");
     return CNERF_OK;
 }
 

@@ -430,6 +430,26 @@ struct SplatArgs {
 hipError_t launch_backproject(const BackprojectArgs& a, hipStream_t stream);
 hipError_t launch_splat_points(const SplatArgs& a, hipStream_t stream);
 
+// tsdf.hip: V depth maps -> a truncated signed distance lattice (include/cnerf.h states the contract, DESIGN.md 3.23 the design)
+struct TsdfArgs {
+    int n0, n1, n2;            // lattice, axis c = world axis c; n0 n1 n2 <= 2^27
+    float lo[3], pitch;        // point i sits at (float)i_c * pitch + lo[c]
+    int V, R;
+    const float* depth;        // (V,R,R)
+    const float* colors;       // (V,3,R,R) in layout 0, (V,R,R,3) in layout 1, or null
+    int color_layout;
+    float color_scale, color_offset;
+    const float* cam2world;    // (V,16)
+    float focal, z_min, z_max, trunc;
+    int carve;                 // 1: a background pixel is an observation of -1
+    int hidden_min;            // > 0: a voxel no view saw free and this many saw behind a surface is 1
+    float unseen;
+    float* tsdf;               // (n0,n1,n2)
+    int32_t* weight;           // (n0,n1,n2) or null
+    float* rgb;                // (n0,n1,n2,3) or null
+};
+hipError_t launch_tsdf_integrate(const TsdfArgs& a, hipStream_t stream);
+
 hipError_t launch_philox_fill(const PhiloxKey& k, uint32_t stream_id, long long n, int normal, float* out, hipStream_t stream);
 hipError_t launch_transpose_cl(int B, int C, int V, const float* src, float* dst, bool to_channel_last, hipStream_t stream);
 

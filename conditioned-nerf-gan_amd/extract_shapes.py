@@ -12,7 +12,11 @@ The surface itself, which the reference leaves to outside tools:
     write_ply("car.ply", vertices, faces, colors)
 
 extract_mesh keeps the grid's four field channels on the device and hands them to ops.isosurface (marching tetrahedra in HIP,
-include/cnerf.h states the algorithm); nothing but the two counts crosses to the host."""
+include/cnerf.h states the algorithm); nothing but the two counts crosses to the host.
+
+A mesh without a density level to guess, from the rendered depth of a ring of views fused into a TSDF volume (cnerf_tsdf_integrate):
+
+    vertices, faces, colors = extract_mesh_tsdf(generator, z, cam2worlds, img_size, fov, ray_start, ray_end, num_steps)"""
 import numpy as np
 import torch
 
@@ -71,6 +75,26 @@ def extract_mesh(generator, z, voxel_resolution=256, voxel_origin=(0, 0, 0), cub
     attrs = field[..., :3].contiguous() if colors else None
     lo = (float(corner[2]), float(corner[1]), float(corner[0]))
     return ops.isosurface(sigma, level, lo=lo, pitch=pitch, attrs=attrs)
+
+
+def extract_mesh_tsdf(generator, z, cam2worlds, img_size, fov, ray_start, ray_end, num_steps, voxel_resolution=256, cube_length=1.2,
+                      voxel_origin=(0, 0, 0), trunc=None, colors=True, views_per_batch=None, **render_kwargs):
+    """The surface the RENDERED DEPTH of one conditioned scene describes, with no density threshold to guess: views.render_views from the
+    cameras cam2worlds (V,4,4), views.tsdf_volume of the depth maps over the cube of edge cube_length about voxel_origin, and the zero
+    level of that volume by ops.isosurface.  -> vertices (Nv,3) float32, faces (Nt,3) int32, colors (Nv,3) float32 in [0,1] (the mean of
+    the rendered pixels that saw the surface; None with colors=False), device tensors like extract_mesh's, ready for write_ply.  Here
+    lattice axis c is world axis c (not extract_mesh's reversed columns), and the normals point out of the shape.
+
+    What to choose.  Cameras all around the object: a side no view looks at is closed by the visual hull of the others, not by its own
+    depth.  A cube no larger than the views cover: a voxel that only a view or two see, behind the object, counts as solid (the hidden
+    rule, include/cnerf.h) and shows as a blob in a corner of the cube.  trunc (None: three pitches) of at least two or three pitches:
+    with less, the inside end of a crossed edge may lie beyond the band in every view and have no colour (it then pulls the vertex's
+    colour toward black), and the surface follows single pixels.  render_kwargs go to the generator's forward."""
+    from . import views
+    pixels, depth = views.render_views(generator, z, cam2worlds, img_size, fov, ray_start, ray_end, num_steps, views_per_batch, **render_kwargs)
+    tsdf, _, rgb, lo, pitch = views.tsdf_volume(pixels if colors else None, depth, cam2worlds, fov, ray_start, ray_end, resolution=voxel_resolution,
+                                                cube_length=cube_length, origin=voxel_origin, trunc=trunc)
+    return ops.isosurface(tsdf, 0.0, lo=lo, pitch=pitch, attrs=rgb)
 
 
 def write_ply(path, vertices, faces, colors=None):

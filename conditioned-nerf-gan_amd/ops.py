@@ -1035,6 +1035,51 @@ def splat_points(points, cam2worlds, R, focal, z_min, z_max, radius=0, lengths=N
     return depth, index, pixels
 
 
+def tsdf_integrate(depth, cam2worlds, focal, z_min, z_max, shape, lo, pitch, trunc, colors=None, color_layout="chw", color_scale=1.0, color_offset=0.0,
+                   carve=True, hidden_min=1, unseen=-1.0, want_weight=False):
+    """cnerf_tsdf_integrate: V depth maps (V,R,R) with their cameras (V,4,4) -> a truncated signed distance lattice of `shape`
+    (n0,n1,n2), point (i0,i1,i2) at i * pitch + lo with lattice axis c = world axis c -- the lattice rule of ops.isosurface, not
+    extract_mesh's reversed columns.  Every voxel is projected into every view and reads the nearest pixel's depth d: with
+    z_min < d < z_max the view observes s = (z - d) / trunc clamped below at -1 (positive BEHIND the surface), or counts the voxel as
+    hidden when s > 1; any other depth but a NaN is background and, with carve, observes -1.  tsdf is the mean of the observations;
+    without one it is 1 where at least hidden_min > 0 views hid the voxel, else `unseen`.  include/cnerf.h states the arithmetic.
+    colors: (V,3,R,R) as "chw" (the generator's pixels) or (V,R,R,3) as "hwc", each channel c * color_scale + color_offset.
+    -> tsdf (n0,n1,n2) float32; weight (n0,n1,n2) int32 with want_weight, else None: the observations, or minus the hiding views, 0 where
+    no view says anything; rgb (n0,n1,n2,3) float32 with colors, else None: the mean colour of the observations within the band, 0
+    where there is none.  ops.isosurface(tsdf, 0.0, lo, pitch, attrs=rgb) meshes it, normals outward.  The same bits on every run; no
+    synchronisation.  Forward only: the inputs are detached, the outputs carry no gradient."""
+    if not (depth.is_cuda and cam2worlds.is_cuda):
+        raise L.CnerfError("tsdf_integrate: depth and cam2worlds must be on the GPU (there is no CPU fallback)")
+    depth = _f32(depth.detach())
+    if depth.dim() != 3 or depth.shape[1] != depth.shape[2]:
+        raise L.CnerfError(f"tsdf_integrate: depth must be (V,R,R), got {tuple(depth.shape)}")
+    if color_layout not in COLOR_LAYOUTS:
+        raise L.CnerfError(f"tsdf_integrate: color_layout must be 'chw' (V,3,R,R) or 'hwc' (V,R,R,3), got {color_layout!r}")
+    code = COLOR_LAYOUTS[color_layout]
+    V, R = int(depth.shape[0]), int(depth.shape[1])
+    dev = depth.device
+    cams = _cams16(cam2worlds, (V,), "tsdf_integrate")
+    if colors is not None:
+        colors = _f32(colors.detach())
+        if tuple(colors.shape) != ((V, 3, R, R) if code == 0 else (V, R, R, 3)):
+            raise L.CnerfError(f"tsdf_integrate: colors must be {(V, 3, R, R) if code == 0 else (V, R, R, 3)} as {color_layout!r}, got {tuple(colors.shape)}")
+    if any(t is not None and t.device != dev for t in (cams, colors)):
+        raise L.CnerfError("tsdf_integrate: all tensors must be on the same device")
+    shape = tuple(int(s) for s in shape)
+    if len(shape) != 3:
+        raise L.CnerfError(f"tsdf_integrate: shape must be (n0,n1,n2), got {shape}")
+    # refusals come before any allocation: a lattice of a refused shape is never sized
+    if any(s < 2 or s > 1024 for s in shape) or shape[0] * shape[1] * shape[2] > 1 << 27:
+        raise L.CnerfError(f"tsdf_integrate: shape {shape} must have every n in [2,1024] and at most 2^27 points")
+    tsdf = torch.empty(shape, dtype=torch.float32, device=dev)
+    weight = torch.empty(shape, dtype=torch.int32, device=dev) if want_weight else None
+    rgb = torch.empty(shape + (3,), dtype=torch.float32, device=dev) if colors is not None else None
+    L.check(L.lib().cnerf_tsdf_integrate(*shape, _cube_lo(lo), float(pitch), V, R, L.ptr(depth), L.ptr(colors), code, float(color_scale),
+                                         float(color_offset), L.ptr(cams), float(focal), float(z_min), float(z_max), float(trunc), int(bool(carve)),
+                                         int(hidden_min), float(unseen), L.ptr(tsdf), L.ptr(weight), L.ptr(rgb), _stream()), "cnerf_tsdf_integrate")
+    return tsdf, weight, rgb
+
+
 def render_rays_forward(net, levels, freq, phase, origins, dirs, o, rng=None, want_aux=False, aux_keys=None, occupancy=None, near=None, far=None):
     """cnerf_render_rays_forward on channel-last levels: origins / dirs (B,P,3) -> pixels (B,P,3), dist (B,P), aux dict.
     occupancy (an OccupancyGrid with one grid per image): cnerf_render_rays_masked_forward instead -- samples in cells whose bit is

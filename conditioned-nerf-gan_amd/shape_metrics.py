@@ -6,6 +6,7 @@ mesh, and the end-to-end score of a conditioned scene against the cloud it was c
     f, precision, recall = f_score(a, b, tau=0.01)
     points, face_idx, bary = sample_surface(vertices, faces, 100_000)
     scores = reconstruction_metrics(generator, z, cloud, voxel_resolution=256)
+    scores = mesh_metrics(vertices, faces, cloud)                # the same scores of any mesh, such as extract_mesh_tsdf's
 
 The nearest-point search is ops.nearest_points (cnerf_nearest_points: exact, brute force, in HIP; include/cnerf.h states its contract);
 nothing n x m is ever stored.  Everything above it is PyTorch plumbing.
@@ -181,20 +182,19 @@ def sample_surface(vertices, faces, n, u=None, generator=None, attrs=None):
 METRIC_KEYS = ("chamfer_mesh_to_cloud", "chamfer_cloud_to_mesh", "chamfer", "f_score", "precision", "recall")
 
 
-def reconstruction_metrics(generator, z, cloud, voxel_resolution=128, cube_length=1.2, level=10.0, n_samples=100_000, tau=0.01, u=None,
-                           return_samples=False):
-    """How far the surface of one conditioned scene lies from a point cloud (the one it was conditioned on): extract_mesh at `level`,
-    n_samples area-weighted points of the mesh (sample_surface; u (n_samples,3) fixes the draw), then chamfer_distance (squared) and
-    f_score at tau between those samples and cloud[..., :3] ((N,>=3) or (1,N,>=3); further columns, such as colours, are ignored).
+def mesh_metrics(vertices, faces, cloud, n_samples=100_000, tau=0.01, u=None, return_samples=False):
+    """How far a triangle mesh lies from a point cloud: n_samples area-weighted points of the mesh (sample_surface; u (n_samples,3) fixes
+    the draw), then chamfer_distance (squared) and f_score at tau between those samples and cloud[..., :3] ((N,>=3) or (1,N,>=3); further
+    columns, such as colours, are ignored).  vertices (Nv,3) and faces (Nt,3) on the GPU, as ops.isosurface returns them: a density mesh
+    (extract_mesh) and a TSDF mesh (extract_mesh_tsdf) are scored by the same code.
     -> dict of Python floats: chamfer_mesh_to_cloud, chamfer_cloud_to_mesh, chamfer (their sum), f_score, precision (of the mesh's
     samples), recall (of the cloud), and the ints vertices, triangles.  An empty mesh gives nan metrics and zero counts.
     return_samples=True: (dict, samples (n_samples,3) on the device; (0,3) for an empty mesh)."""
-    vertices, faces, _ = extract_shapes.extract_mesh(generator, z, voxel_resolution=voxel_resolution, cube_length=cube_length, level=level, colors=False)
     cloud = torch.as_tensor(cloud).detach().to(device=vertices.device, dtype=torch.float32)
     if cloud.dim() == 3 and cloud.shape[0] == 1:
         cloud = cloud[0]
     if cloud.dim() != 2 or cloud.shape[-1] < 3:
-        raise L.CnerfError(f"reconstruction_metrics: cloud must be (N,>=3) or (1,N,>=3), got {tuple(cloud.shape)}")
+        raise L.CnerfError(f"mesh_metrics: cloud must be (N,>=3) or (1,N,>=3), got {tuple(cloud.shape)}")
     cloud = cloud[:, :3].contiguous()
     out = {k: math.nan for k in METRIC_KEYS}
     out["vertices"], out["triangles"] = int(vertices.shape[0]), int(faces.shape[0])
@@ -207,3 +207,11 @@ def reconstruction_metrics(generator, z, cloud, voxel_resolution=128, cube_lengt
         out.update(chamfer_mesh_to_cloud=float(ab), chamfer_cloud_to_mesh=float(ba), chamfer=float(ab) + float(ba), f_score=float(f),
                    precision=float(p), recall=float(r))
     return (out, samples) if return_samples else out
+
+
+def reconstruction_metrics(generator, z, cloud, voxel_resolution=128, cube_length=1.2, level=10.0, n_samples=100_000, tau=0.01, u=None,
+                           return_samples=False):
+    """How far the surface of one conditioned scene lies from a point cloud (the one it was conditioned on): extract_mesh at `level`,
+    then mesh_metrics of that mesh against the cloud, which states the samples, the scores and what is returned."""
+    vertices, faces, _ = extract_shapes.extract_mesh(generator, z, voxel_resolution=voxel_resolution, cube_length=cube_length, level=level, colors=False)
+    return mesh_metrics(vertices, faces, cloud, n_samples=n_samples, tau=tau, u=u, return_samples=return_samples)

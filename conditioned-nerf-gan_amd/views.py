@@ -1,4 +1,5 @@
-"""Between rendered views and point clouds, on the device: depth maps fused into one coloured cloud, and the z-buffered picture of a cloud.
+"""Between rendered views and shapes, on the device: depth maps fused into one coloured cloud or into a truncated signed distance volume
+(tsdf_volume: cnerf_tsdf_integrate, whose zero level extract_shapes.extract_mesh_tsdf meshes), and the z-buffered picture of a cloud.
 
 The reference looks at a scene's geometry with Inferencer.render_pcl (inference.py:501-601): it renders n views, lifts every pixel whose
 depth lies strictly inside (ray_start, ray_end) into world space on the host -- nonzero, indexing, a 4x4 matmul per view in a Python
@@ -26,11 +27,10 @@ def fuse_depth_maps(pixels, depth, cam2worlds, fov, ray_start, ray_end, mask=Non
                            mask=mask, mask_min=1e-4)[0]
 
 
-def render_pcl(gen, z, cam2worlds, img_size, fov, ray_start, ray_end, num_steps, views_per_batch=None, **render_kwargs):
-    """The reference's render_pcl without the file: renders ONE scene z (batch 1, as the generator takes it: a feature volume, a
-    (volume, global feature) pair or a latent) from the cameras cam2worlds (V,4,4) under no_grad, views_per_batch at a time (None: all
-    at once), and fuses the views -> (n,6).  render_kwargs go to the generator's forward (hierarchical_sample, clamp_mode,
-    nerf_noise, ...).  Write it with write_obj_cloud; score it with shape_metrics; voxelise it with voxels.voxelize_cloud."""
+def render_views(gen, z, cam2worlds, img_size, fov, ray_start, ray_end, num_steps, views_per_batch=None, **render_kwargs):
+    """Renders ONE scene z (batch 1, as the generator takes it: a feature volume, a (volume, global feature) pair or a latent) from the
+    cameras cam2worlds (V,4,4) under no_grad, views_per_batch at a time (None: all at once).  render_kwargs go to the generator's
+    forward (hierarchical_sample, clamp_mode, nerf_noise, ...).  -> pixels (V,3,R,R), depth (V,R,R)."""
     V = int(cam2worlds.shape[0])
     step = V if views_per_batch is None else max(1, int(views_per_batch))
 
@@ -45,7 +45,36 @@ def render_pcl(gen, z, cam2worlds, img_size, fov, ray_start, ray_end, num_steps,
                            **render_kwargs)
             imgs.append(img)
             depths.append(dep)
-        return fuse_depth_maps(torch.cat(imgs, 0), torch.cat(depths, 0), cam2worlds, fov, ray_start, ray_end)
+        return torch.cat(imgs, 0), torch.cat(depths, 0)
+
+
+def render_pcl(gen, z, cam2worlds, img_size, fov, ray_start, ray_end, num_steps, views_per_batch=None, **render_kwargs):
+    """The reference's render_pcl without the file: render_views of ONE scene z from the cameras cam2worlds (V,4,4), and the views fused
+    -> (n,6).  Write it with write_obj_cloud; score it with shape_metrics; voxelise it with voxels.voxelize_cloud."""
+    pixels, depth = render_views(gen, z, cam2worlds, img_size, fov, ray_start, ray_end, num_steps, views_per_batch, **render_kwargs)
+    with torch.no_grad():
+        return fuse_depth_maps(pixels, depth, cam2worlds, fov, ray_start, ray_end)
+
+
+def tsdf_volume(pixels, depth, cam2worlds, fov, ray_start, ray_end, resolution=256, cube_length=1.2, origin=(0, 0, 0), trunc=None, carve=True,
+                hidden_min=1, unseen=-1.0, want_weight=False):
+    """Rendered views -> a truncated signed distance volume: pixels (V,3,R,R) in [-1,1] (or None) and depth (V,R,R) as render_views returns
+    them, cam2worlds (V,4,4).  The cube of edge cube_length about origin, resolution^3 lattice points: corner lo = origin - cube_length / 2,
+    pitch = cube_length / (resolution - 1), lattice axis c = world axis c.  trunc=None: three pitches.  Pixels with
+    ray_start < depth < ray_end are surface, all others but NaNs background (the renderer's depth of an empty ray is near 0); colours are
+    0.5 * pixels + 0.5, as in fuse_depth_maps.  ops.tsdf_integrate states the rule, include/cnerf.h the arithmetic.
+    -> tsdf (N,N,N), weight (int32, or None without want_weight), rgb (N,N,N,3) in [0,1] (None without pixels), lo (three floats), pitch:
+    ops.isosurface(tsdf, 0.0, lo, pitch, attrs=rgb) is the mesh."""
+    N = int(resolution)
+    if N < 2:
+        raise ValueError(f"tsdf_volume: resolution={resolution} must be at least 2")
+    lo = tuple(float(o) - 0.5 * float(cube_length) for o in origin)
+    pitch = float(cube_length) / (N - 1)
+    trunc = 3.0 * pitch if trunc is None else float(trunc)
+    tsdf, weight, rgb = ops.tsdf_integrate(depth, cam2worlds, focal_of(fov), ray_start, ray_end, (N, N, N), lo, pitch, trunc, colors=pixels,
+                                           color_layout="chw", color_scale=0.5, color_offset=0.5, carve=carve, hidden_min=hidden_min, unseen=unseen,
+                                           want_weight=want_weight)
+    return tsdf, weight, rgb, lo, pitch
 
 
 def splat_cloud(pcl, cam2worlds, img_size, fov, z_min, z_max, radius=1, lengths=None):
