@@ -3,6 +3,22 @@
 
 using namespace cnerf;
 
+// checks that more than one entry makes: the message of each is written here alone
+namespace {
+int check_finite3(const float* v, const char* name, const char* who) {
+    for (int c = 0; c < 3; ++c)
+        if (!(fabsf(v[c]) < INFINITY)) return fail(CNERF_EINVAL, "%s: %s[%d]=%g must be finite", who, name, c, (double)v[c]);
+    return CNERF_OK;
+}
+int check_pitch(float p, const char* who) { return p > 0.0f && p < INFINITY ? CNERF_OK : fail(CNERF_EINVAL, "%s: pitch=%g must be > 0 and finite", who, (double)p); }
+int check_color_layout(int l, const char* who) { return l == 0 || l == 1 ? CNERF_OK : fail(CNERF_EINVAL, "%s: color_layout=%d must be 0 (V,3,R,R) or 1 (V,R,R,3)", who, l); }
+int check_cloud_rows(long long n, int stride, int min_stride, const char* who) {
+    if (n < 1 || n >= (1LL << 28)) return fail(CNERF_EINVAL, "%s: n=%lld out of range [1,2^28)", who, n);
+    if (stride < min_stride) return fail(CNERF_EINVAL, "%s: stride=%d must be >= %d (%s)", who, stride, min_stride, min_stride == 3 ? "xyz" : "xyz rgb");
+    return CNERF_OK;
+}
+}  // namespace
+
 // ---------------------------------------------------------------------------------------------------------------------
 // isosurfaces: marching tetrahedra on a scalar lattice (csrc/isosurface.hip)
 // ---------------------------------------------------------------------------------------------------------------------
@@ -83,8 +99,7 @@ int check_voxel_cube(int G, const float* lo, float side, int layout, const char*
     if (!(side > 0.0f) || !(side < INFINITY)) return fail(CNERF_EINVAL, "%s: side=%g must be > 0 and finite", who, (double)side);
     if (!((float)G / side < INFINITY))       // a denormal side: every cell coordinate would be an infinity or a NaN
         return fail(CNERF_EINVAL, "%s: side=%g is too small: (float)G / side is not finite", who, (double)side);
-    for (int c = 0; c < 3; ++c)
-        if (!(fabsf(lo[c]) < INFINITY)) return fail(CNERF_EINVAL, "%s: lo[%d]=%g must be finite", who, c, (double)lo[c]);
+    if (int rc = check_finite3(lo, "lo", who)) return rc;
     if (layout != 0 && layout != 1) return fail(CNERF_EINVAL, "%s: layout=%d must be 0 (B,4,G,G,G) or 1 (B,G,G,G,4)", who, layout);
     return CNERF_OK;
 }
@@ -134,7 +149,7 @@ int cnerf_backproject(int32_t V, int32_t R, const float* depth, const float* col
     if (int rc = check_pinhole(focal, z_min, z_max, who)) return rc;
     if (mask_min != mask_min) return fail(CNERF_EINVAL, "%s: mask_min is NaN", who);
     if (color_scale != color_scale || color_offset != color_offset) return fail(CNERF_EINVAL, "%s: color_scale / color_offset is NaN", who);
-    if (color_layout != 0 && color_layout != 1) return fail(CNERF_EINVAL, "%s: color_layout=%d must be 0 (V,3,R,R) or 1 (V,R,R,3)", who, color_layout);
+    if (int rc = check_color_layout(color_layout, who)) return rc;
     if (!depth || !cam2world || !points || !workspace) return fail(CNERF_EINVAL, "%s: NULL argument (depth / cam2world / points / workspace)", who);
     BackprojectArgs a{};
     a.V = V, a.R = R, a.chunks = bp_chunks(R), a.depth = depth, a.colors = colors, a.color_layout = color_layout, a.mask = mask, a.cam2world = cam2world;
@@ -157,8 +172,7 @@ int cnerf_splat_points(int32_t B, int64_t n, int32_t stride, const float* points
     g_err[0] = 0;
     const char* who = "splat_points";
     if (int rc = check_view_grid(B, V, R, who)) return rc;
-    if (n < 1 || n >= (1LL << 28)) return fail(CNERF_EINVAL, "%s: n=%lld out of range [1,2^28)", who, (long long)n);
-    if (stride < 3) return fail(CNERF_EINVAL, "%s: stride=%d must be >= 3 (xyz)", who, stride);
+    if (int rc = check_cloud_rows((long long)n, stride, 3, who)) return rc;
     if (pixels && stride < 6) return fail(CNERF_EINVAL, "%s: pixels need stride >= 6 (xyz rgb), got stride=%d", who, stride);
     if (radius < 0 || radius > 8) return fail(CNERF_EINVAL, "%s: radius=%d out of range [0,8]", who, radius);
     if (int rc = check_pinhole(focal, z_min, z_max, who)) return rc;
@@ -182,15 +196,14 @@ int cnerf_tsdf_integrate(int32_t n0, int32_t n1, int32_t n2, const float lo[3], 
     if (int rc = check_iso_shape(n0, n1, n2, who)) return rc;
     if (int rc = check_view_grid(1, V, R, who)) return rc;
     if (!lo || !depth || !cam2world || !tsdf) return fail(CNERF_EINVAL, "%s: NULL argument (lo / depth / cam2world / tsdf)", who);
-    if (!(pitch > 0.0f) || !(pitch < INFINITY)) return fail(CNERF_EINVAL, "%s: pitch=%g must be > 0 and finite", who, (double)pitch);
-    for (int c = 0; c < 3; ++c)
-        if (!(fabsf(lo[c]) < INFINITY)) return fail(CNERF_EINVAL, "%s: lo[%d]=%g must be finite", who, c, (double)lo[c]);
+    if (int rc = check_pitch(pitch, who)) return rc;
+    if (int rc = check_finite3(lo, "lo", who)) return rc;
     if (!(trunc > 0.0f) || !(trunc < INFINITY)) return fail(CNERF_EINVAL, "%s: trunc=%g must be > 0 and finite", who, (double)trunc);
     if (int rc = check_pinhole(focal, z_min, z_max, who)) return rc;
     if (!(fabsf(unseen) < INFINITY)) return fail(CNERF_EINVAL, "%s: unseen=%g must be finite", who, (double)unseen);
     if (!(fabsf(color_scale) < INFINITY)) return fail(CNERF_EINVAL, "%s: color_scale=%g must be finite", who, (double)color_scale);
     if (!(fabsf(color_offset) < INFINITY)) return fail(CNERF_EINVAL, "%s: color_offset=%g must be finite", who, (double)color_offset);
-    if (color_layout != 0 && color_layout != 1) return fail(CNERF_EINVAL, "%s: color_layout=%d must be 0 (V,3,R,R) or 1 (V,R,R,3)", who, color_layout);
+    if (int rc = check_color_layout(color_layout, who)) return rc;
     if (carve != 0 && carve != 1) return fail(CNERF_EINVAL, "%s: carve=%d must be 0 or 1", who, carve);
     if (hidden_min < 0) return fail(CNERF_EINVAL, "%s: hidden_min=%d must be >= 0", who, hidden_min);
     if (rgb && !colors) return fail(CNERF_EINVAL, "%s: rgb is asked for and colors is NULL", who);
@@ -215,8 +228,7 @@ int cnerf_voxelize(int32_t B, int64_t n, int32_t stride, const float* points, co
     g_err[0] = 0;
     const char* who = "voxelize";
     if (int rc = check_voxel_grid(B, G, who)) return rc;
-    if (n < 1 || n >= (1LL << 28)) return fail(CNERF_EINVAL, "%s: n=%lld out of range [1,2^28)", who, (long long)n);
-    if (stride < 6) return fail(CNERF_EINVAL, "%s: stride=%d must be >= 6 (xyz rgb)", who, stride);
+    if (int rc = check_cloud_rows((long long)n, stride, 6, who)) return rc;
     if (int rc = check_voxel_cube(G, lo, side, layout, who)) return rc;
     if (clip_margin != clip_margin) return fail(CNERF_EINVAL, "%s: clip_margin is NaN (>= 0 clips, < 0 does not)", who);
     if (clip_margin >= 0.0f && !(2.0f * clip_margin < side))
@@ -291,9 +303,8 @@ int cnerf_isosurface_emit(int32_t n0, int32_t n1, int32_t n2, const float* value
     if (int rc = check_iso_shape(n0, n1, n2, who)) return rc;
     if (!values || !workspace || !vertices || !triangles || !lo) return fail(CNERF_EINVAL, "%s: NULL argument (values / lo / workspace / vertices / triangles)", who);
     if (!(fabsf(level) < INFINITY)) return fail(CNERF_EINVAL, "%s: level=%g must be finite", who, (double)level);
-    if (!(pitch > 0.0f) || !(pitch < INFINITY)) return fail(CNERF_EINVAL, "%s: pitch=%g must be > 0 and finite", who, (double)pitch);
-    for (int c = 0; c < 3; ++c)
-        if (!(fabsf(lo[c]) < INFINITY)) return fail(CNERF_EINVAL, "%s: lo[%d]=%g must be finite", who, c, (double)lo[c]);
+    if (int rc = check_pitch(pitch, who)) return rc;
+    if (int rc = check_finite3(lo, "lo", who)) return rc;
     if ((attrs == nullptr) != (vertex_attrs == nullptr)) return fail(CNERF_EINVAL, "%s: attrs and vertex_attrs must both be given, or neither", who);
     if (attrs && (n_attr < 1 || n_attr > 8)) return fail(CNERF_EINVAL, "%s: n_attr=%d out of range [1,8]", who, n_attr);
     if (max_vertices < 0 || max_triangles < 0)

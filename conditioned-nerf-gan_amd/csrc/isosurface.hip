@@ -13,8 +13,10 @@
 //   emit       vertices and attributes of the point's edges, triangles of its cell; the index of a vertex on an edge owned by point q is
 //              block offset + voff[q] + popc(edge mask of q below the edge's kind), read back from q's code -- no 7 n index table
 //
-// Bandwidth work: 8 L2-served loads of values per point in classify, 9 B per point of workspace written there and read in emit.
+// Bandwidth work: 8 L2-served loads of values per point in classify, 9 B per point of workspace written there and read in emit.  The
+// lattice rule (flat index split, position of a point) is geom_dev.hpp's, shared with tsdf.hip.
 #include "cnerf_dev.hpp"
+#include "geom_dev.hpp"
 #include "cnerf_kernels.hpp"
 
 namespace cnerf {
@@ -74,17 +76,7 @@ __constant__ const IsoCountTable ISO_TRIANGLES = iso_count_table();
 // the seven edge bits of a code: bit k = the edge of kind k + 1 crosses the level (its far end's INSIDE bit differs from the point's own)
 __device__ __forceinline__ unsigned iso_edge_mask(unsigned code) { return ((code >> 1) ^ ((code & 1u) ? 0x7Fu : 0u)) & 0x7Fu; }
 
-struct IsoIndex {
-    int i0, i1, i2;
-};
-__device__ __forceinline__ IsoIndex iso_index(const IsoDims& d, int p) {
-    IsoIndex I;
-    I.i2 = p % d.n2;
-    const int q = p / d.n2;
-    I.i1 = q % d.n1;
-    I.i0 = q / d.n1;
-    return I;
-}
+__device__ __forceinline__ Index3 iso_index(const IsoDims& d, int p) { return lattice_split(p, d.n1, d.n2); }
 // flat distance to the corner with offset number j
 __device__ __forceinline__ int iso_step(const IsoDims& d, int j) { return (j & 1) * d.n1 * d.n2 + ((j >> 1) & 1) * d.n2 + ((j >> 2) & 1); }
 
@@ -129,7 +121,7 @@ __global__ __launch_bounds__(ISO_BLOCK) void iso_classify_kernel(IsoCountArgs a)
     int nv = 0, nt = 0;
     unsigned code = 0;
     if (p < a.d.n) {
-        const IsoIndex I = iso_index(a.d, p);
+        const Index3 I = iso_index(a.d, p);
         const bool own = a.values[p] > a.level;
         const bool in0 = I.i0 + 1 < a.d.n0, in1 = I.i1 + 1 < a.d.n1, in2 = I.i2 + 1 < a.d.n2;
         code = own ? 1u : 0u;
@@ -159,7 +151,7 @@ __device__ __forceinline__ int iso_vertex_index(const IsoEmitArgs& a, int q, int
     return a.block_offsets[q / ISO_BLOCK] + a.voff[q] + __popc(iso_edge_mask(a.code[q]) & ((1u << k) - 1u));
 }
 
-// Pass 3.  Position of lattice point i on an axis: (float)i * pitch + lo, the product rounded, then the sum.  The vertex of an edge is
+// Pass 3.  Position of lattice point i on an axis: geom_dev.hpp's lattice_pos, as tsdf.hip forms it.  The vertex of an edge is
 // formed from its owner P0 toward the other end P1: t = (level - v0) / (v1 - v0), 0.5 if either value is not finite; P0 + t (P1 - P0)
 // per component, every operation rounded on its own.  Rows at or beyond the caller's capacities are not written.
 __global__ __launch_bounds__(ISO_BLOCK) void iso_emit_kernel(IsoEmitArgs a) {
@@ -167,11 +159,10 @@ __global__ __launch_bounds__(ISO_BLOCK) void iso_emit_kernel(IsoEmitArgs a) {
     if (p >= a.d.n) return;
     const unsigned code = a.code[p];
     const unsigned mask = iso_edge_mask(code);
-    const IsoIndex I = iso_index(a.d, p);
+    const Index3 I = iso_index(a.d, p);
     if (mask) {
         const float v0 = a.values[p];
-        const float p0[3] = {__fadd_rn(__fmul_rn((float)I.i0, a.pitch), a.lo[0]), __fadd_rn(__fmul_rn((float)I.i1, a.pitch), a.lo[1]),
-                             __fadd_rn(__fmul_rn((float)I.i2, a.pitch), a.lo[2])};
+        const float p0[3] = {lattice_pos(I.i0, a.pitch, a.lo[0]), lattice_pos(I.i1, a.pitch, a.lo[1]), lattice_pos(I.i2, a.pitch, a.lo[2])};
         long long row = (long long)a.block_offsets[blockIdx.x] + a.voff[p];
         for (int k = 0; k < 7; ++k) {
             if (!((mask >> k) & 1u)) continue;
@@ -183,7 +174,7 @@ __global__ __launch_bounds__(ISO_BLOCK) void iso_emit_kernel(IsoEmitArgs a) {
                 const float t = finite ? __fdiv_rn(__fsub_rn(a.level, v0), __fsub_rn(v1, v0)) : 0.5f;
                 const int i[3] = {I.i0 + (j & 1), I.i1 + ((j >> 1) & 1), I.i2 + ((j >> 2) & 1)};
                 for (int c = 0; c < 3; ++c) {
-                    const float p1 = __fadd_rn(__fmul_rn((float)i[c], a.pitch), a.lo[c]);
+                    const float p1 = lattice_pos(i[c], a.pitch, a.lo[c]);
                     a.vertices[row * 3 + c] = __fadd_rn(p0[c], __fmul_rn(t, __fsub_rn(p1, p0[c])));
                 }
                 for (int c = 0; c < a.n_attr; ++c) {

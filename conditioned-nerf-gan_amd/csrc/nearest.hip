@@ -11,9 +11,11 @@
 //          distance that is NaN or +inf never compares below the best, so it is never chosen.
 //          A work item is (image, range of targets, group of NN_QUERIES queries); blocks stride over the items, so no grid dimension
 //          grows with the problem beyond NN_MAX_GRID.  With one range the result goes to the outputs, otherwise to the workspace.
+//          The clamped lengths of an image (clamped_len) and the capped launch grid are geom_dev.hpp's.
 // reduce   (more than one range) one lane per query: the ranges' partial (d, j) in ascending range order under the same strict <.
 //          A range holds ascending indices and the ranges ascend, so this is the order of a single scan.
 #include "cnerf_dev.hpp"
+#include "geom_dev.hpp"
 #include "cnerf_kernels.hpp"
 
 namespace cnerf {
@@ -24,12 +26,6 @@ constexpr int NN_PAIRS = NN_QPT / 2;
 constexpr int NN_REDUCE_BLOCK = 256;
 constexpr long long NN_MAX_GRID = 1LL << 20;     // blocks of a launch; the kernels stride over what is beyond
 static_assert(NN_QPT % 2 == 0 && NN_QUERIES == NN_QPT * WAVE, "a lane owns whole pairs of queries, a block is one wave");
-
-__device__ __forceinline__ long long nn_clamp_len(const int32_t* __restrict__ lens, int b, long long full) {
-    if (!lens) return full;
-    const long long v = lens[b];
-    return v < 0 ? 0 : (v > full ? full : v);
-}
 
 // one target against the lane's queries; j ascends from call to call
 __device__ __forceinline__ void nn_step(const nn_f32x2 (&qx)[NN_PAIRS], const nn_f32x2 (&qy)[NN_PAIRS], const nn_f32x2 (&qz)[NN_PAIRS], float tx, float ty,
@@ -59,8 +55,8 @@ __global__ __launch_bounds__(WAVE) void nearest_search_kernel(int B, long long n
     for (long long w = blockIdx.x; w < items; w += gridDim.x) {
         const long long qg = w % qgroups, br = w / qgroups;
         const int r = (int)(br % splits), b = (int)(br / splits);
-        const long long nq = nn_clamp_len(n_queries, b, n);
-        const long long mt = nn_clamp_len(n_targets, b, m);
+        const long long nq = clamped_len(n_queries, b, n);
+        const long long mt = clamped_len(n_targets, b, m);
         const int lo = (int)((long long)r * mt / splits), hi = (int)((long long)(r + 1) * mt / splits);      // mt < 2^31, splits <= 1024
         const long long q0 = qg * NN_QUERIES;
         float best[NN_QPT];
@@ -136,12 +132,12 @@ hipError_t launch_nearest_points(const NearestArgs& a, hipStream_t stream) {
     const long long qgroups = (a.n + NN_QUERIES - 1) / NN_QUERIES;
     const long long items = (long long)a.B * a.splits * qgroups;
     const bool split = a.splits > 1;
-    hipLaunchKernelGGL(nearest_search_kernel, dim3((unsigned)(items < NN_MAX_GRID ? items : NN_MAX_GRID)), dim3(WAVE), 0, stream, a.B, a.n, a.m, a.splits,
+    hipLaunchKernelGGL(nearest_search_kernel, dim3(capped_grid(items, NN_MAX_GRID)), dim3(WAVE), 0, stream, a.B, a.n, a.m, a.splits,
                        a.queries, a.targets, a.n_queries, a.n_targets, split ? a.part_d : a.dist2, split ? a.part_j : a.idx);
     if (hipError_t e = hipGetLastError()) return e;
     if (!split) return hipSuccess;
     const long long blocks = ((long long)a.B * a.n + NN_REDUCE_BLOCK - 1) / NN_REDUCE_BLOCK;
-    hipLaunchKernelGGL(nearest_reduce_kernel, dim3((unsigned)(blocks < NN_MAX_GRID ? blocks : NN_MAX_GRID)), dim3(NN_REDUCE_BLOCK), 0, stream, a.B, a.n,
+    hipLaunchKernelGGL(nearest_reduce_kernel, dim3(capped_grid(blocks, NN_MAX_GRID)), dim3(NN_REDUCE_BLOCK), 0, stream, a.B, a.n,
                        a.splits, a.part_d, a.part_j, a.dist2, a.idx);
     return hipGetLastError();
 }

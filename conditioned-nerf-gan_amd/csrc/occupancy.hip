@@ -10,6 +10,7 @@
 // All four kernels are bandwidth work of 4 - 28 B per sample point against the field's 0.41 MFLOP; the bit words of an image (at most
 // 2 MiB) are re-read through L2, and 32 ray-consecutive points usually hit one or two of them.
 #include "cnerf_dev.hpp"
+#include "geom_dev.hpp"
 #include "cnerf_kernels.hpp"
 
 namespace cnerf {
@@ -51,15 +52,11 @@ __global__ __launch_bounds__(OCC_BLOCK) void occ_build_kernel(OccBuildArgs a) {
     }
 }
 
-// Is point p of image b given to the field?  t = (p - lo) * inv per axis, each operation rounded on its own; inside the box iff
-// 0 <= t < G on all three axes (a NaN is not inside); outside nothing is skipped, inside the cell's bit decides.
+// Is point p of image b given to the field?  geom_dev.hpp's cell rule per axis: outside the box nothing is skipped, inside the bit decides.
 __device__ __forceinline__ bool occ_live(const OccGrid& g, const uint32_t* bits, float x, float y, float z) {
     const float Gf = (float)g.G;
-    const float tx = __fmul_rn(__fsub_rn(x, g.lo[0]), g.inv);
-    const float ty = __fmul_rn(__fsub_rn(y, g.lo[1]), g.inv);
-    const float tz = __fmul_rn(__fsub_rn(z, g.lo[2]), g.inv);
-    const bool inside = tx >= 0.0f && tx < Gf && ty >= 0.0f && ty < Gf && tz >= 0.0f && tz < Gf;
-    if (!inside) return true;
+    const float tx = cell_coord(x, g.lo[0], g.inv), ty = cell_coord(y, g.lo[1], g.inv), tz = cell_coord(z, g.lo[2], g.inv);
+    if (!(cell_inside(tx, Gf) && cell_inside(ty, Gf) && cell_inside(tz, Gf))) return true;
     const int idx = ((int)floorf(tx) * g.G + (int)floorf(ty)) * g.G + (int)floorf(tz);
     return (bits[idx >> 5] >> (idx & 31)) & 1u;
 }
@@ -69,7 +66,7 @@ __device__ __forceinline__ const uint32_t* occ_image_bits(const OccGrid& g, int 
 }
 
 // Pass 1: live points of every chunk of OCC_CHUNK consecutive points of an image -- ballot + popcount per wave, summed over the block's
-// rounds in registers and over its four waves through LDS.  block_counts (B, chunks_per_image).
+// rounds in registers and over its four waves by block_wave_sums.  block_counts (B, chunks_per_image).
 __global__ __launch_bounds__(OCC_BLOCK) void occ_count_kernel(OccCompactArgs a) {
     __shared__ int wave_sum[OCC_WAVES];
     const int b = blockIdx.y;
@@ -82,13 +79,8 @@ __global__ __launch_bounds__(OCC_BLOCK) void occ_count_kernel(OccCompactArgs a) 
         const bool live = p < a.n && occ_live(a.grid, bits, pts[p * 3], pts[p * 3 + 1], pts[p * 3 + 2]);
         cnt += __popcll(__ballot(live));                    // the same number in every lane of the wave
     }
-    if ((threadIdx.x & (WAVE - 1)) == 0) wave_sum[threadIdx.x / WAVE] = cnt;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        int s = 0;
-        for (int w = 0; w < OCC_WAVES; ++w) s += wave_sum[w];
-        a.block_counts[(size_t)b * gridDim.x + blockIdx.x] = s;
-    }
+    const int total = block_wave_sums<OCC_WAVES>(cnt, wave_sum).total;
+    if (threadIdx.x == 0) a.block_counts[(size_t)b * gridDim.x + blockIdx.x] = total;
 }
 
 // Pass 2: one block per image turns its chunk counts into exclusive offsets, in place, and writes counts[b].  256 counts per round: a
@@ -121,12 +113,11 @@ __global__ __launch_bounds__(OCC_BLOCK) void occ_scan_kernel(int32_t* block_coun
 }
 
 // Pass 3: rank of every point -- its index among the image's live points in ascending order, -1 if skipped -- and the live positions
-// packed at the front of live_points.  The chunk's offset from pass 2, then per round of 256 points the waves' ballots: lanes below,
-// waves before (LDS), rounds before (a register).  No atomics: the order is the points' own.
+// packed at the front of live_points.  The chunk's offset from pass 2, then per round of 256 points block_rank: lanes below, waves
+// before (LDS), and rounds before (a register).  No atomics: the order is the points' own.
 __global__ __launch_bounds__(OCC_BLOCK) void occ_rank_kernel(OccCompactArgs a) {
     __shared__ int wave_cnt[2][OCC_WAVES];
     const int b = blockIdx.y;
-    const int lane = threadIdx.x & (WAVE - 1), wave = threadIdx.x / WAVE;
     const long long p0 = (long long)blockIdx.x * OCC_CHUNK;
     const uint32_t* bits = occ_image_bits(a.grid, b);
     const float* pts = a.points + (size_t)b * a.n * 3;
@@ -143,17 +134,9 @@ __global__ __launch_bounds__(OCC_BLOCK) void occ_rank_kernel(OccCompactArgs a) {
             z = pts[p * 3 + 2];
             live = occ_live(a.grid, bits, x, y, z);
         }
-        const unsigned long long mask = __ballot(live);
-        if (lane == 0) wave_cnt[r & 1][wave] = __popcll(mask);
-        __syncthreads();                                    // (two slots: round r + 1 writes the other one while a slow wave still reads this)
-        int before = 0, total = 0;
-        for (int w = 0; w < OCC_WAVES; ++w) {
-            const int c = wave_cnt[r & 1][w];
-            before += w < wave ? c : 0;
-            total += c;
-        }
+        const BlockRank br = block_rank<OCC_WAVES>(live, wave_cnt[r & 1]);      // (two slots: round r + 1 writes the other one while a slow wave still reads this)
         if (p < a.n) {
-            const int k = live ? base + before + __popcll(mask & ((1ull << lane) - 1ull)) : -1;
+            const int k = live ? base + br.before : -1;
             rank[p] = k;
             if (live) {
                 out[(size_t)k * 3] = x;
@@ -161,7 +144,7 @@ __global__ __launch_bounds__(OCC_BLOCK) void occ_rank_kernel(OccCompactArgs a) {
                 out[(size_t)k * 3 + 2] = z;
             }
         }
-        base += total;
+        base += br.total;
     }
 }
 
@@ -305,9 +288,8 @@ hipError_t launch_occ_compact(const OccCompactArgs& a, hipStream_t stream) {
 }
 
 hipError_t launch_occ_expand(const OccExpandArgs& a, hipStream_t stream) {
-    long long blocks = (a.n * a.B + OCC_BLOCK - 1) / OCC_BLOCK;
-    if (blocks > 65536) blocks = 65536;
-    hipLaunchKernelGGL(occ_expand_kernel, dim3((unsigned)blocks), dim3(OCC_BLOCK), 0, stream, a);
+    const long long blocks = (a.n * a.B + OCC_BLOCK - 1) / OCC_BLOCK;
+    hipLaunchKernelGGL(occ_expand_kernel, dim3(capped_grid(blocks, 65536)), dim3(OCC_BLOCK), 0, stream, a);      // the kernel strides over what is beyond
     return hipGetLastError();
 }
 

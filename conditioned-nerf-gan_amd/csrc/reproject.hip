@@ -6,12 +6,12 @@
 // in a Python loop over the views) and gives what its render_pcl_masked / loss_depth read from EXR files: a depth image of the cloud.
 //
 // back-projection   count, scan, emit over the flat pixel sequence (v, row, col), as occupancy.hip compacts sample points: a block owns
-//   count            BP_CHUNK = 256 consecutive pixels of one view (one round, one pixel per lane); ballot + popcount per wave, the four
-//                    waves through LDS.  chunk_counts (V, chunks per view): the flat pixel order.
+//   count            BP_CHUNK = 256 consecutive pixels of one view (one round, one pixel per lane); geom_dev.hpp's block_rank gives the
+//                    block's total.  chunk_counts (V, chunks per view): the flat pixel order.
 //   scan             occupancy.hip's occ_scan_kernel over the V * chunks counts as ONE row: exclusive offsets in place, the total behind
 //                    them.  No atomics anywhere: the order of the cloud is the pixels' own.
-//   emit             the validity again, the pixel's row from the chunk's offset, the waves before and the lanes below; the twelve
-//                    separately rounded operations of the position, the colour, rank, pixel; block 0 of a view writes counts[v] as a
+//   emit             the validity again, the pixel's row from the chunk's offset and block_rank's lanes before; the twelve separately
+//                    rounded operations of the position, the colour (view_color), rank, pixel; block 0 of a view writes counts[v] as a
 //                    difference of two offsets.
 // splat             the workspace is one 64-bit key per (b, view, row, col), set to all ones.
 //   splat            one lane per (point, view); a block handles one (b, view) and 256 points, so the camera and the scalars are
@@ -19,8 +19,9 @@
 //                    One no-return 64-bit unsigned atomic min at agent scope per covered pixel (behind a plain load iff radius > 0).
 //                    A minimum does not depend on the order of arrival: the result is the same bits for every launch geometry and run.
 //   resolve          one lane per pixel: the key back into depth, index and the winner's stored colour.
-// The two splat kernels stride over their work with a grid of at most SPLAT_MAX_GRID blocks.
+// The two splat kernels stride over their work with a grid of at most SPLAT_MAX_GRID blocks.  The projection is geom_dev.hpp's.
 #include "cnerf_dev.hpp"
+#include "geom_dev.hpp"
 #include "cnerf_kernels.hpp"
 
 namespace cnerf {
@@ -50,36 +51,25 @@ __global__ __launch_bounds__(RP_BLOCK) void bp_count_kernel(BackprojectArgs a) {
     const int p = c * BP_CHUNK + threadIdx.x;
     float z;
     const bool live = p < RR && bp_valid(a, (long long)v * RR + p, z);
-    const int cnt = __popcll(__ballot(live));
-    if ((threadIdx.x & (WAVE - 1)) == 0) wave_sum[threadIdx.x / WAVE] = cnt;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        int s = 0;
-        for (int w = 0; w < RP_WAVES; ++w) s += wave_sum[w];
-        a.chunk_counts[blockIdx.x] = s;
-    }
+    const int total = block_rank<RP_WAVES>(live, wave_sum).total;
+    if (threadIdx.x == 0) a.chunk_counts[blockIdx.x] = total;
 }
 
 __global__ __launch_bounds__(RP_BLOCK) void bp_emit_kernel(BackprojectArgs a) {
     __shared__ int wave_cnt[RP_WAVES];
     const int RR = a.R * a.R;
     const int v = blockIdx.x / a.chunks, c = blockIdx.x - v * a.chunks;
-    const int lane = threadIdx.x & (WAVE - 1), wave = threadIdx.x / WAVE;
     const int p = c * BP_CHUNK + threadIdx.x;
     const long long e = (long long)v * RR + p;
     const int total_chunks = a.V * a.chunks;
     float z = 0.0f;
     const bool live = p < RR && bp_valid(a, e, z);
-    const unsigned long long mask = __ballot(live);
-    if (lane == 0) wave_cnt[wave] = __popcll(mask);
-    __syncthreads();
-    int before = 0;
-    for (int w = 0; w < RP_WAVES; ++w) before += w < wave ? wave_cnt[w] : 0;
+    const int before = block_rank<RP_WAVES>(live, wave_cnt).before;
     const int base = a.chunk_counts[blockIdx.x];
     if (c == 0 && threadIdx.x == 0 && a.counts)          // offsets are flat over the views: a view's count is a difference of two
         a.counts[v] = a.chunk_counts[v + 1 < a.V ? (v + 1) * a.chunks : total_chunks] - base;
     if (p >= RR) return;
-    const int k = live ? base + before + __popcll(mask & ((1ull << lane) - 1ull)) : -1;
+    const int k = live ? base + before : -1;
     if (a.rank) a.rank[e] = k;
     if (!live) return;
     if (a.pixel) a.pixel[k] = (int32_t)e;
@@ -93,11 +83,9 @@ __global__ __launch_bounds__(RP_BLOCK) void bp_emit_kernel(BackprojectArgs a) {
     for (int i = 0; i < 3; ++i)
         out[i] = __fadd_rn(__fadd_rn(__fadd_rn(__fmul_rn(M[4 * i], xc), __fmul_rn(M[4 * i + 1], yc)), __fmul_rn(M[4 * i + 2], z)), M[4 * i + 3]);
     if (a.colors) {
+        const ViewColor cv = view_color_at(a.colors, a.color_layout, v, RR, p);
 #pragma unroll
-        for (int ch = 0; ch < 3; ++ch) {
-            const float cv = a.color_layout == 0 ? a.colors[((size_t)v * 3 + ch) * RR + p] : a.colors[(size_t)e * 3 + ch];
-            out[3 + ch] = __fadd_rn(__fmul_rn(cv, a.color_scale), a.color_offset);
-        }
+        for (int ch = 0; ch < 3; ++ch) out[3 + ch] = view_color(cv, ch, a.color_scale, a.color_offset);
     }
 }
 
@@ -132,22 +120,14 @@ __global__ __launch_bounds__(RP_BLOCK) void splat_kernel(SplatArgs a) {
         const long long bv = w / chunks;
         const long long i = (w - bv * chunks) * RP_BLOCK + threadIdx.x;
         const long long b = bv / a.V;
-        long long np = a.n;
-        if (a.n_points) {
-            const long long v = a.n_points[b];
-            np = v < 0 ? 0 : (v > a.n ? a.n : v);
-        }
-        if (i >= np) continue;
+        if (i >= clamped_len(a.n_points, b, a.n)) continue;
         const float* M = a.cam2world + (size_t)bv * 16;
         const float* p = a.points + ((size_t)b * a.n + i) * a.stride;
-        const float q0 = __fsub_rn(p[0], M[3]), q1 = __fsub_rn(p[1], M[7]), q2 = __fsub_rn(p[2], M[11]);
-        const float z = __fadd_rn(__fadd_rn(__fmul_rn(q0, M[2]), __fmul_rn(q1, M[6])), __fmul_rn(q2, M[10]));
+        float q[3], u, v;
+        const float z = cam_depth(M, p, q);
         if (!(a.z_min < z && z < a.z_max)) continue;                  // behind, beyond, a NaN
-        const float cx = __fadd_rn(__fadd_rn(__fmul_rn(q0, M[0]), __fmul_rn(q1, M[4])), __fmul_rn(q2, M[8]));
-        const float cy = __fadd_rn(__fadd_rn(__fmul_rn(q0, M[1]), __fmul_rn(q1, M[5])), __fmul_rn(q2, M[9]));
-        const float u = __fadd_rn(__fmul_rn(__fmul_rn(cx, a.focal) / z, half), half);
-        const float v = __fadd_rn(__fmul_rn(__fmul_rn(cy, a.focal) / z, half), half);
-        if (!(lo < u && u < hi && lo < v && v < hi)) continue;         // float compares: a NaN fails them; what passes converts safely
+        cam_pixel(q, z, M, a.focal, half, u, v);
+        if (!(lo < u && u < hi && lo < v && v < hi)) continue;
         const int col = (int)rintf(u), row = (int)rintf(v);
         const unsigned long long key = ((unsigned long long)__float_as_uint(z) << 32) | (uint32_t)i;
         unsigned long long* img = a.keys + (size_t)bv * R * R;
@@ -178,15 +158,13 @@ __global__ __launch_bounds__(RP_BLOCK) void splat_resolve_kernel(SplatArgs a) {
     }
 }
 
-static unsigned splat_grid(long long blocks) { return (unsigned)(blocks < 1 ? 1 : (blocks < SPLAT_MAX_GRID ? blocks : SPLAT_MAX_GRID)); }
-
 hipError_t launch_splat_points(const SplatArgs& a, hipStream_t stream) {
     const long long px = (long long)a.B * a.V * a.R * a.R;
     if (hipError_t e = hipMemsetAsync(a.keys, 0xff, (size_t)px * sizeof(unsigned long long), stream)) return e;
     const long long chunks = (a.n + RP_BLOCK - 1) / RP_BLOCK;
-    hipLaunchKernelGGL(splat_kernel, dim3(splat_grid((long long)a.B * a.V * chunks)), dim3(RP_BLOCK), 0, stream, a);
+    hipLaunchKernelGGL(splat_kernel, dim3(capped_grid((long long)a.B * a.V * chunks, SPLAT_MAX_GRID)), dim3(RP_BLOCK), 0, stream, a);
     if (hipError_t e = hipGetLastError()) return e;
-    hipLaunchKernelGGL(splat_resolve_kernel, dim3(splat_grid((px + RP_BLOCK - 1) / RP_BLOCK)), dim3(RP_BLOCK), 0, stream, a);
+    hipLaunchKernelGGL(splat_resolve_kernel, dim3(capped_grid((px + RP_BLOCK - 1) / RP_BLOCK, SPLAT_MAX_GRID)), dim3(RP_BLOCK), 0, stream, a);
     return hipGetLastError();
 }
 

@@ -9,8 +9,9 @@
 // scalar of the arguments are the same address for every lane: they arrive through the scalar data path (the pointers are __restrict__
 // and the view index is uniform), and the vector operations take them as scalar operands.
 //
-// Positions and camera coordinates are formed per voxel from its indices, never stepped: the contract fixes every rounding.
+// Positions and camera coordinates are formed per voxel from its indices, never stepped, by geom_dev.hpp's rules (isosurface.hip's lattice).
 #include "cnerf_dev.hpp"
+#include "geom_dev.hpp"
 #include "cnerf_kernels.hpp"
 
 namespace cnerf {
@@ -24,11 +25,8 @@ __global__ __launch_bounds__(TSDF_BLOCK) void tsdf_kernel(TsdfArgs a, const floa
     const int total = a.n0 * a.n1 * a.n2;                                   // <= 2^27
     const int e = (int)blockIdx.x * TSDF_BLOCK + (int)threadIdx.x;
     if (e >= total) return;
-    const int i01 = e / a.n2, i2 = e - i01 * a.n2;
-    const int i0 = i01 / a.n1, i1 = i01 - i0 * a.n1;
-    const float p0 = __fadd_rn(__fmul_rn((float)i0, a.pitch), a.lo[0]);
-    const float p1 = __fadd_rn(__fmul_rn((float)i1, a.pitch), a.lo[1]);
-    const float p2 = __fadd_rn(__fmul_rn((float)i2, a.pitch), a.lo[2]);
+    const Index3 I = lattice_split(e, a.n1, a.n2);
+    const float p[3] = {lattice_pos(I.i0, a.pitch, a.lo[0]), lattice_pos(I.i1, a.pitch, a.lo[1]), lattice_pos(I.i2, a.pitch, a.lo[2])};
     const int R = a.R;
     const size_t RR = (size_t)R * R;
     const float half = __fmul_rn(0.5f, (float)(R - 1));
@@ -37,14 +35,11 @@ __global__ __launch_bounds__(TSDF_BLOCK) void tsdf_kernel(TsdfArgs a, const floa
     int n = 0, hidden = 0, cn = 0;
     for (int w = 0; w < a.V; ++w) {                                          // w is uniform: M comes through scalar loads
         const float* M = cams + (size_t)w * 16;
-        const float q0 = __fsub_rn(p0, M[3]), q1 = __fsub_rn(p1, M[7]), q2 = __fsub_rn(p2, M[11]);
-        const float z = __fadd_rn(__fadd_rn(__fmul_rn(q0, M[2]), __fmul_rn(q1, M[6])), __fmul_rn(q2, M[10]));
+        float q[3], u, v;
+        const float z = cam_depth(M, p, q);
         if (!(z > 0.0f)) continue;                                           // behind the camera, or a NaN
-        const float cx = __fadd_rn(__fadd_rn(__fmul_rn(q0, M[0]), __fmul_rn(q1, M[4])), __fmul_rn(q2, M[8]));
-        const float cy = __fadd_rn(__fadd_rn(__fmul_rn(q0, M[1]), __fmul_rn(q1, M[5])), __fmul_rn(q2, M[9]));
-        const float u = __fadd_rn(__fmul_rn(__fmul_rn(cx, a.focal) / z, half), half);
-        const float v = __fadd_rn(__fmul_rn(__fmul_rn(cy, a.focal) / z, half), half);
-        if (!(-1.0f < u && u < fR && -1.0f < v && v < fR)) continue;         // float compares: a NaN fails them; what passes converts safely
+        cam_pixel(q, z, M, a.focal, half, u, v);
+        if (!(-1.0f < u && u < fR && -1.0f < v && v < fR)) continue;
         const int col = (int)rintf(u), row = (int)rintf(v);
         if (col < 0 || col >= R || row < 0 || row >= R) continue;            // (-1, -0.5] and [R - 0.5, R) round outside
         const size_t pix = (size_t)row * R + col;
@@ -55,11 +50,10 @@ __global__ __launch_bounds__(TSDF_BLOCK) void tsdf_kernel(TsdfArgs a, const floa
                 ++hidden;                                                    // occluded: no observation
             } else {
                 if (COLOR && s >= -1.0f) {
-                    const float* c = a.color_layout == 0 ? colors + (size_t)w * 3 * RR + pix : colors + ((size_t)w * RR + pix) * 3;
-                    const size_t step = a.color_layout == 0 ? RR : 1;
-                    c0 = __fadd_rn(c0, __fadd_rn(__fmul_rn(c[0], a.color_scale), a.color_offset));
-                    c1 = __fadd_rn(c1, __fadd_rn(__fmul_rn(c[step], a.color_scale), a.color_offset));
-                    c2 = __fadd_rn(c2, __fadd_rn(__fmul_rn(c[2 * step], a.color_scale), a.color_offset));
+                    const ViewColor cv = view_color_at(colors, a.color_layout, w, RR, pix);
+                    c0 = __fadd_rn(c0, view_color(cv, 0, a.color_scale, a.color_offset));
+                    c1 = __fadd_rn(c1, view_color(cv, 1, a.color_scale, a.color_offset));
+                    c2 = __fadd_rn(c2, view_color(cv, 2, a.color_scale, a.color_offset));
                     ++cn;
                 }
                 sum = __fadd_rn(sum, fmaxf(s, -1.0f));

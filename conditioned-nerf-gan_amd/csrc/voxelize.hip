@@ -16,8 +16,10 @@
 // first hit   one lane per ray walks the S depths in ascending order and leaves at the first occupied sample.  Per step one fma for the
 //             depth (linspace_at, as ATen), then twelve separately rounded operations for the position and the cell coordinate (never
 //             fused), one 4-byte load.  No atomics.
+// The cell rule and the clamped row count of an image are geom_dev.hpp's.
 // Every kernel strides over its work with a grid of at most VOX_MAX_GRID blocks; the tests cross that size in all three.
 #include "cnerf_dev.hpp"
+#include "geom_dev.hpp"
 #include "cnerf_kernels.hpp"
 
 namespace cnerf {
@@ -42,12 +44,11 @@ __device__ __forceinline__ int vox_axis(const VoxelizeArgs& a, int k, float p) {
     const float Gf = (float)a.G;
     if (a.clip) {
         p = fminf(fmaxf(p, a.clip_lo[k]), a.clip_hi[k]);
-        const float t = __fmul_rn(__fsub_rn(p, a.lo[k]), a.inv);
-        const int i = (int)floorf(t);
+        const int i = (int)floorf(cell_coord(p, a.lo[k], a.inv));
         return i < 0 ? 0 : (i > a.G - 1 ? a.G - 1 : i);
     }
-    const float t = __fmul_rn(__fsub_rn(p, a.lo[k]), a.inv);
-    if (!(t >= 0.0f && t < Gf)) return -1;          // outside, an infinity, an overflow
+    const float t = cell_coord(p, a.lo[k], a.inv);
+    if (!cell_inside(t, Gf)) return -1;             // outside, an infinity, an overflow
     return (int)floorf(t);
 }
 
@@ -60,11 +61,7 @@ __global__ __launch_bounds__(VOX_BLOCK) void voxelize_accumulate_kernel(Voxelize
     for (long long w = blockIdx.x; w < items; w += gridDim.x) {
         const long long b = w / chunks;
         const long long p0 = (w - b * chunks) * VOX_BLOCK;
-        long long np = a.n;
-        if (a.n_points) {
-            const long long v = a.n_points[b];
-            np = v < 0 ? 0 : (v > a.n ? a.n : v);
-        }
+        const long long np = clamped_len(a.n_points, b, a.n);
         if (p0 >= np) continue;                      // block-uniform
         const float* src = a.points + ((size_t)b * a.n + p0) * a.stride;
         const long long live = np - p0 < VOX_BLOCK ? np - p0 : VOX_BLOCK;
@@ -132,10 +129,10 @@ __global__ __launch_bounds__(VOX_BLOCK) void voxel_first_hit_kernel(VoxelHitArgs
         int hc = -1;
         for (int s = 0; s < a.S; ++s) {
             const float t = linspace_at(a.t_min, a.t_max, a.S, s);
-            const float tx = __fmul_rn(__fsub_rn(__fadd_rn(ox, __fmul_rn(dx, t)), a.lo[0]), a.inv);
-            const float ty = __fmul_rn(__fsub_rn(__fadd_rn(oy, __fmul_rn(dy, t)), a.lo[1]), a.inv);
-            const float tz = __fmul_rn(__fsub_rn(__fadd_rn(oz, __fmul_rn(dz, t)), a.lo[2]), a.inv);
-            if (!(tx >= 0.0f && tx < Gf && ty >= 0.0f && ty < Gf && tz >= 0.0f && tz < Gf)) continue;
+            const float tx = cell_coord(__fadd_rn(ox, __fmul_rn(dx, t)), a.lo[0], a.inv);
+            const float ty = cell_coord(__fadd_rn(oy, __fmul_rn(dy, t)), a.lo[1], a.inv);
+            const float tz = cell_coord(__fadd_rn(oz, __fmul_rn(dz, t)), a.lo[2], a.inv);
+            if (!(tx >= 0.0f && tx < Gf && ty >= 0.0f && ty < Gf && tz >= 0.0f && tz < Gf)) continue;      // cell_inside on the three axes, as one chain
             const int ix = (int)floorf(tx), iy = (int)floorf(ty), iz = (int)floorf(tz);
             const long long at = a.layout == 0 ? ((long long)iz * a.G + iy) * a.G + ix : (((long long)ix * a.G + iy) * a.G + iz) * 4;
             const long long ch = a.layout == 0 ? cells : 1;
@@ -152,20 +149,18 @@ __global__ __launch_bounds__(VOX_BLOCK) void voxel_first_hit_kernel(VoxelHitArgs
     }
 }
 
-static unsigned vox_grid(long long blocks) { return (unsigned)(blocks < 1 ? 1 : (blocks < VOX_MAX_GRID ? blocks : VOX_MAX_GRID)); }
-
 hipError_t launch_voxelize(const VoxelizeArgs& a, hipStream_t stream) {
     const long long cells = (long long)a.G * a.G * a.G;
     if (hipError_t e = hipMemsetAsync(a.acc, 0, (size_t)a.B * cells * 4 * sizeof(unsigned long long), stream)) return e;
     const long long chunks = (a.n + VOX_BLOCK - 1) / VOX_BLOCK;
-    hipLaunchKernelGGL(voxelize_accumulate_kernel, dim3(vox_grid((long long)a.B * chunks)), dim3(VOX_BLOCK), 0, stream, a);
+    hipLaunchKernelGGL(voxelize_accumulate_kernel, dim3(capped_grid((long long)a.B * chunks, VOX_MAX_GRID)), dim3(VOX_BLOCK), 0, stream, a);
     if (hipError_t e = hipGetLastError()) return e;
-    hipLaunchKernelGGL(voxelize_finish_kernel, dim3(vox_grid(((long long)a.B * cells + VOX_BLOCK - 1) / VOX_BLOCK)), dim3(VOX_BLOCK), 0, stream, a);
+    hipLaunchKernelGGL(voxelize_finish_kernel, dim3(capped_grid(((long long)a.B * cells + VOX_BLOCK - 1) / VOX_BLOCK, VOX_MAX_GRID)), dim3(VOX_BLOCK), 0, stream, a);
     return hipGetLastError();
 }
 
 hipError_t launch_voxel_first_hit(const VoxelHitArgs& a, hipStream_t stream) {
-    hipLaunchKernelGGL(voxel_first_hit_kernel, dim3(vox_grid(((long long)a.B * a.P + VOX_BLOCK - 1) / VOX_BLOCK)), dim3(VOX_BLOCK), 0, stream, a);
+    hipLaunchKernelGGL(voxel_first_hit_kernel, dim3(capped_grid(((long long)a.B * a.P + VOX_BLOCK - 1) / VOX_BLOCK, VOX_MAX_GRID)), dim3(VOX_BLOCK), 0, stream, a);
     return hipGetLastError();
 }
 

@@ -114,6 +114,19 @@ def drop_of(rng):
     return (rng or {}).get("drop")
 
 
+def _float3(v):
+    """Three floats for a `const float[3]` argument; a number stands for all three."""
+    v = (v, v, v) if isinstance(v, (int, float)) else tuple(v)
+    return (C.c_float * 3)(*(float(x) for x in v))
+
+
+def _workspace(entry_name, dev, *dims):
+    """The workspace that the size query `entry_name` asks for at `dims`: uint8 on `dev`, or None where it asks for nothing."""
+    nb = C.c_size_t(0)
+    L.check(getattr(L.lib(), entry_name)(*dims, C.byref(nb)), entry_name)
+    return torch.empty(nb.value, dtype=torch.uint8, device=dev) if nb.value else None
+
+
 def _u8(t):
     return None if t is None else t.to(torch.uint8).contiguous()
 
@@ -699,7 +712,7 @@ def _occ_struct(grid, B):
         raise L.CnerfError(f"occupancy bits must be int32 (B={B}, G^3/32={G ** 3 // 32}), got {bits.dtype} {tuple(bits.shape)}")
     oc = L.Occupancy()
     oc.bits, oc.G, oc.side = L.ptr(bits).value, G, float(grid.side)
-    oc.lo[0], oc.lo[1], oc.lo[2] = (float(v) for v in grid.lo)
+    oc.lo = _float3(grid.lo)
     return oc
 
 
@@ -725,9 +738,7 @@ def occupancy_compact(grid, points, rank=None, live_points=None):
     B, n = points.shape[0], points.shape[1]
     dev = points.device
     oc = _occ_struct(grid, B)
-    nb = C.c_size_t(0)
-    L.check(L.lib().cnerf_occupancy_compact_bytes(B, n, C.byref(nb)), "cnerf_occupancy_compact_bytes")
-    ws = torch.empty(nb.value, dtype=torch.uint8, device=dev)
+    ws = _workspace("cnerf_occupancy_compact_bytes", dev, B, n)
     rank = torch.empty((B, n), dtype=torch.int32, device=dev) if rank is None else rank
     live_points = torch.empty((B, n, 3), dtype=torch.float32, device=dev) if live_points is None else live_points
     counts = torch.empty((B,), dtype=torch.int32, device=dev)
@@ -793,9 +804,7 @@ def isosurface(values, level, lo=(0.0, 0.0, 0.0), pitch=1.0, attrs=None):
             raise L.CnerfError(f"isosurface: attrs must be ({n0},{n1},{n2},C), got {tuple(attrs.shape)}")
     n_attr = 0 if attrs is None else int(attrs.shape[3])
     lib = L.lib()
-    nb = C.c_size_t(0)
-    L.check(lib.cnerf_isosurface_bytes(n0, n1, n2, C.byref(nb)), "cnerf_isosurface_bytes")
-    ws = torch.empty(nb.value, dtype=torch.uint8, device=dev)
+    ws = _workspace("cnerf_isosurface_bytes", dev, n0, n1, n2)
     counts = torch.empty((2,), dtype=torch.int32, device=dev)
     L.check(lib.cnerf_isosurface_count(n0, n1, n2, L.ptr(values), float(level), L.ptr(counts), L.ptr(ws), _stream()), "cnerf_isosurface_count")
     nv, nt = (int(c) for c in counts.tolist())
@@ -804,8 +813,7 @@ def isosurface(values, level, lo=(0.0, 0.0, 0.0), pitch=1.0, attrs=None):
     vertex_attrs = None if attrs is None else torch.empty((nv, n_attr), dtype=torch.float32, device=dev)
     if nv == 0:
         return vertices, faces, vertex_attrs
-    lo3 = (C.c_float * 3)(*(float(v) for v in lo))
-    L.check(lib.cnerf_isosurface_emit(n0, n1, n2, L.ptr(values), float(level), lo3, float(pitch), L.ptr(attrs), n_attr, nv, nt, L.ptr(vertices),
+    L.check(lib.cnerf_isosurface_emit(n0, n1, n2, L.ptr(values), float(level), _float3(lo), float(pitch), L.ptr(attrs), n_attr, nv, nt, L.ptr(vertices),
                                       L.ptr(vertex_attrs), L.ptr(faces), L.ptr(ws), _stream()), "cnerf_isosurface_emit")
     return vertices, faces, vertex_attrs
 
@@ -840,14 +848,11 @@ def nearest_points(queries, targets, query_lengths=None, target_lengths=None, ta
     dev = queries.device
     nq = _cloud_lengths(query_lengths, B, dev, "query_lengths")
     mt = _cloud_lengths(target_lengths, B, dev, "target_lengths")
-    lib = L.lib()
-    nb = C.c_size_t(0)
-    L.check(lib.cnerf_nearest_points_bytes(B, n, m, int(target_splits), C.byref(nb)), "cnerf_nearest_points_bytes")
-    ws = torch.empty(nb.value, dtype=torch.uint8, device=dev) if nb.value else None
+    ws = _workspace("cnerf_nearest_points_bytes", dev, B, n, m, int(target_splits))
     dist2 = torch.empty((B, n), dtype=torch.float32, device=dev)
     idx = torch.empty((B, n), dtype=torch.int32, device=dev)
-    L.check(lib.cnerf_nearest_points(B, n, m, L.ptr(queries), L.ptr(targets), L.ptr(nq), L.ptr(mt), int(target_splits), L.ptr(dist2), L.ptr(idx),
-                                     L.ptr(ws), _stream()), "cnerf_nearest_points")
+    L.check(L.lib().cnerf_nearest_points(B, n, m, L.ptr(queries), L.ptr(targets), L.ptr(nq), L.ptr(mt), int(target_splits), L.ptr(dist2), L.ptr(idx),
+                                         L.ptr(ws), _stream()), "cnerf_nearest_points")
     return (dist2[0], idx[0]) if single else (dist2, idx)
 
 
@@ -858,11 +863,6 @@ def _voxel_layout(layout, who):
     if layout not in VOXEL_LAYOUTS:
         raise L.CnerfError(f"{who}: layout must be 'encoder' (B,4,G,G,G) or 'npz' (B,G,G,G,4), got {layout!r}")
     return VOXEL_LAYOUTS[layout]
-
-
-def _cube_lo(lo):
-    lo = (lo, lo, lo) if isinstance(lo, (int, float)) else tuple(lo)
-    return (C.c_float * 3)(*(float(v) for v in lo))
 
 
 def voxelize(points, G, lo, side, lengths=None, clip_margin=1e-4, layout="encoder", want_counts=False):
@@ -888,15 +888,12 @@ def voxelize(points, G, lo, side, lengths=None, clip_margin=1e-4, layout="encode
     G = int(G)
     dev = points.device
     np_ = _cloud_lengths(lengths, B, dev, "lengths", "voxelize")
-    lib = L.lib()
-    nb = C.c_size_t(0)
-    L.check(lib.cnerf_voxelize_bytes(B, G, C.byref(nb)), "cnerf_voxelize_bytes")
-    ws = torch.empty(nb.value, dtype=torch.uint8, device=dev)
+    ws = _workspace("cnerf_voxelize_bytes", dev, B, G)
     voxels = torch.empty((B, 4, G, G, G) if code == 0 else (B, G, G, G, 4), dtype=torch.float32, device=dev)
     counts = torch.empty((B, G, G, G), dtype=torch.int32, device=dev) if want_counts else None
     margin = -1.0 if clip_margin is None else float(clip_margin)
-    L.check(lib.cnerf_voxelize(B, n, stride, L.ptr(points), L.ptr(np_), G, _cube_lo(lo), float(side), margin, code, L.ptr(voxels), L.ptr(counts),
-                               L.ptr(ws), _stream()), "cnerf_voxelize")
+    L.check(L.lib().cnerf_voxelize(B, n, stride, L.ptr(points), L.ptr(np_), G, _float3(lo), float(side), margin, code, L.ptr(voxels), L.ptr(counts),
+                                   L.ptr(ws), _stream()), "cnerf_voxelize")
     if single:
         voxels, counts = voxels[0], (counts[0] if want_counts else None)
     return (voxels, counts) if want_counts else voxels
@@ -930,9 +927,8 @@ def voxel_first_hit(voxels, origins, dirs, lo, side, t_min, t_max, num_steps, ba
     hit_t = torch.empty((B, P), dtype=torch.float32, device=dev)
     hit_cell = torch.empty((B, P), dtype=torch.int32, device=dev)
     rs = _rays_struct(origins, dirs)
-    bg = (C.c_float * 3)(*(float(v) for v in background))
-    L.check(L.lib().cnerf_voxel_first_hit(B, P, C.byref(rs), L.ptr(voxels), G, _cube_lo(lo), float(side), code, float(t_min), float(t_max),
-                                          int(num_steps), bg, L.ptr(pixels), L.ptr(hit_t), L.ptr(hit_cell), _stream()), "cnerf_voxel_first_hit")
+    L.check(L.lib().cnerf_voxel_first_hit(B, P, C.byref(rs), L.ptr(voxels), G, _float3(lo), float(side), code, float(t_min), float(t_max),
+                                          int(num_steps), _float3(background), L.ptr(pixels), L.ptr(hit_t), L.ptr(hit_cell), _stream()), "cnerf_voxel_first_hit")
     return (pixels[0], hit_t[0], hit_cell[0]) if single else (pixels, hit_t, hit_cell)
 
 
@@ -949,6 +945,33 @@ def _cams16(cam2worlds, lead, who):
     return c.contiguous()
 
 
+def _view_inputs(who, depth, cam2worlds, colors, color_layout, mask=None):
+    """What backproject and tsdf_integrate take alike: depth maps (V,R,R), their cameras, colours in `color_layout` or None, a mask or None
+    -> (depth, cams, colors, mask) detached, float32 and on one device, and (V, R, the layout's code, the device)."""
+    if not (depth.is_cuda and cam2worlds.is_cuda):
+        raise L.CnerfError(f"{who}: depth and cam2worlds must be on the GPU (there is no CPU fallback)")
+    depth = _f32(depth.detach())
+    if depth.dim() != 3 or depth.shape[1] != depth.shape[2]:
+        raise L.CnerfError(f"{who}: depth must be (V,R,R), got {tuple(depth.shape)}")
+    if color_layout not in COLOR_LAYOUTS:
+        raise L.CnerfError(f"{who}: color_layout must be 'chw' (V,3,R,R) or 'hwc' (V,R,R,3), got {color_layout!r}")
+    code = COLOR_LAYOUTS[color_layout]
+    V, R = int(depth.shape[0]), int(depth.shape[1])
+    dev = depth.device
+    cams = _cams16(cam2worlds, (V,), who)
+    if colors is not None:
+        colors = _f32(colors.detach())
+        if tuple(colors.shape) != ((V, 3, R, R) if code == 0 else (V, R, R, 3)):
+            raise L.CnerfError(f"{who}: colors must be {(V, 3, R, R) if code == 0 else (V, R, R, 3)} as {color_layout!r}, got {tuple(colors.shape)}")
+    if mask is not None:
+        mask = _f32(mask.detach())
+        if mask.shape != depth.shape:
+            raise L.CnerfError(f"{who}: mask must be {tuple(depth.shape)}, got {tuple(mask.shape)}")
+    if any(t is not None and t.device != dev for t in (cams, colors, mask)):
+        raise L.CnerfError(f"{who}: all tensors must be on the same device")
+    return (depth, cams, colors, mask), (V, R, code, dev)
+
+
 def backproject(depth, cam2worlds, focal, z_min, z_max, colors=None, color_layout="chw", color_scale=1.0, color_offset=0.0, mask=None, mask_min=0.0,
                 want_pixel=False, want_rank=False):
     """cnerf_backproject: V depth maps (V,R,R) with their cameras (V,4,4) -> ONE cloud in world space.  A pixel is valid iff
@@ -959,38 +982,15 @@ def backproject(depth, cam2worlds, focal, z_min, z_max, colors=None, color_layou
     -> points (n, 6 or 3) float32, counts (V,) int32 on the device (valid pixels per view, summing to n), then with want_pixel
     pixel (n,) int32 = (v R + row) R + col of every row, and with want_rank rank (V,R,R) int32 = the pixel's row in the cloud or -1.
     Reading n back is the one synchronisation.  Forward only: the inputs are detached, the outputs carry no gradient."""
-    if not (depth.is_cuda and cam2worlds.is_cuda):
-        raise L.CnerfError("backproject: depth and cam2worlds must be on the GPU (there is no CPU fallback)")
-    depth = _f32(depth.detach())
-    if depth.dim() != 3 or depth.shape[1] != depth.shape[2]:
-        raise L.CnerfError(f"backproject: depth must be (V,R,R), got {tuple(depth.shape)}")
-    if color_layout not in COLOR_LAYOUTS:
-        raise L.CnerfError(f"backproject: color_layout must be 'chw' (V,3,R,R) or 'hwc' (V,R,R,3), got {color_layout!r}")
-    code = COLOR_LAYOUTS[color_layout]
-    V, R = int(depth.shape[0]), int(depth.shape[1])
-    dev = depth.device
-    cams = _cams16(cam2worlds, (V,), "backproject")
-    if colors is not None:
-        colors = _f32(colors.detach())
-        if tuple(colors.shape) != ((V, 3, R, R) if code == 0 else (V, R, R, 3)):
-            raise L.CnerfError(f"backproject: colors must be {(V, 3, R, R) if code == 0 else (V, R, R, 3)} as {color_layout!r}, got {tuple(colors.shape)}")
-    if mask is not None:
-        mask = _f32(mask.detach())
-        if mask.shape != depth.shape:
-            raise L.CnerfError(f"backproject: mask must be {tuple(depth.shape)}, got {tuple(mask.shape)}")
-    if any(t is not None and t.device != dev for t in (cams, colors, mask)):
-        raise L.CnerfError("backproject: all tensors must be on the same device")
-    lib = L.lib()
-    nb = C.c_size_t(0)
-    L.check(lib.cnerf_backproject_bytes(V, R, C.byref(nb)), "cnerf_backproject_bytes")
-    ws = torch.empty(nb.value, dtype=torch.uint8, device=dev)
+    (depth, cams, colors, mask), (V, R, code, dev) = _view_inputs("backproject", depth, cam2worlds, colors, color_layout, mask)
+    ws = _workspace("cnerf_backproject_bytes", dev, V, R)
     points = torch.empty((V * R * R, 6 if colors is not None else 3), dtype=torch.float32, device=dev)
     counts = torch.empty((V,), dtype=torch.int32, device=dev)
     pixel = torch.empty((V * R * R,), dtype=torch.int32, device=dev) if want_pixel else None
     rank = torch.empty((V, R, R), dtype=torch.int32, device=dev) if want_rank else None
-    L.check(lib.cnerf_backproject(V, R, L.ptr(depth), L.ptr(colors), code, L.ptr(mask), float(mask_min), L.ptr(cams), float(focal), float(z_min),
-                                  float(z_max), float(color_scale), float(color_offset), L.ptr(points), L.ptr(counts), L.ptr(pixel), L.ptr(rank),
-                                  L.ptr(ws), _stream()), "cnerf_backproject")
+    L.check(L.lib().cnerf_backproject(V, R, L.ptr(depth), L.ptr(colors), code, L.ptr(mask), float(mask_min), L.ptr(cams), float(focal), float(z_min),
+                                      float(z_max), float(color_scale), float(color_offset), L.ptr(points), L.ptr(counts), L.ptr(pixel), L.ptr(rank),
+                                      L.ptr(ws), _stream()), "cnerf_backproject")
     n = int(counts.sum().item())
     out = (points[:n], counts)
     if want_pixel:
@@ -1022,16 +1022,12 @@ def splat_points(points, cam2worlds, R, focal, z_min, z_max, radius=0, lengths=N
     if cams.device != dev:
         raise L.CnerfError("splat_points: points and cam2worlds must be on the same device")
     np_ = _cloud_lengths(lengths, B, dev, "lengths", "splat_points")
-    lib = L.lib()
-    nb = C.c_size_t(0)
-    L.check(lib.cnerf_splat_points_bytes(B, V, R, C.byref(nb)), "cnerf_splat_points_bytes")
-    ws = torch.empty(nb.value, dtype=torch.uint8, device=dev)
+    ws = _workspace("cnerf_splat_points_bytes", dev, B, V, R)
     depth = torch.empty((B, V, R, R), dtype=torch.float32, device=dev)
     index = torch.empty((B, V, R, R), dtype=torch.int32, device=dev)
     pixels = torch.empty((B, V, R, R, 3), dtype=torch.float32, device=dev) if want_pixels else None
-    bg = (C.c_float * 3)(*(float(v) for v in background))
-    L.check(lib.cnerf_splat_points(B, n, stride, L.ptr(points), L.ptr(np_), V, L.ptr(cams), R, float(focal), float(z_min), float(z_max), int(radius), bg,
-                                   L.ptr(depth), L.ptr(index), L.ptr(pixels), L.ptr(ws), _stream()), "cnerf_splat_points")
+    L.check(L.lib().cnerf_splat_points(B, n, stride, L.ptr(points), L.ptr(np_), V, L.ptr(cams), R, float(focal), float(z_min), float(z_max), int(radius),
+                                       _float3(background), L.ptr(depth), L.ptr(index), L.ptr(pixels), L.ptr(ws), _stream()), "cnerf_splat_points")
     return depth, index, pixels
 
 
@@ -1048,23 +1044,7 @@ def tsdf_integrate(depth, cam2worlds, focal, z_min, z_max, shape, lo, pitch, tru
     no view says anything; rgb (n0,n1,n2,3) float32 with colors, else None: the mean colour of the observations within the band, 0
     where there is none.  ops.isosurface(tsdf, 0.0, lo, pitch, attrs=rgb) meshes it, normals outward.  The same bits on every run; no
     synchronisation.  Forward only: the inputs are detached, the outputs carry no gradient."""
-    if not (depth.is_cuda and cam2worlds.is_cuda):
-        raise L.CnerfError("tsdf_integrate: depth and cam2worlds must be on the GPU (there is no CPU fallback)")
-    depth = _f32(depth.detach())
-    if depth.dim() != 3 or depth.shape[1] != depth.shape[2]:
-        raise L.CnerfError(f"tsdf_integrate: depth must be (V,R,R), got {tuple(depth.shape)}")
-    if color_layout not in COLOR_LAYOUTS:
-        raise L.CnerfError(f"tsdf_integrate: color_layout must be 'chw' (V,3,R,R) or 'hwc' (V,R,R,3), got {color_layout!r}")
-    code = COLOR_LAYOUTS[color_layout]
-    V, R = int(depth.shape[0]), int(depth.shape[1])
-    dev = depth.device
-    cams = _cams16(cam2worlds, (V,), "tsdf_integrate")
-    if colors is not None:
-        colors = _f32(colors.detach())
-        if tuple(colors.shape) != ((V, 3, R, R) if code == 0 else (V, R, R, 3)):
-            raise L.CnerfError(f"tsdf_integrate: colors must be {(V, 3, R, R) if code == 0 else (V, R, R, 3)} as {color_layout!r}, got {tuple(colors.shape)}")
-    if any(t is not None and t.device != dev for t in (cams, colors)):
-        raise L.CnerfError("tsdf_integrate: all tensors must be on the same device")
+    (depth, cams, colors, _), (V, R, code, dev) = _view_inputs("tsdf_integrate", depth, cam2worlds, colors, color_layout)
     shape = tuple(int(s) for s in shape)
     if len(shape) != 3:
         raise L.CnerfError(f"tsdf_integrate: shape must be (n0,n1,n2), got {shape}")
@@ -1074,7 +1054,7 @@ def tsdf_integrate(depth, cam2worlds, focal, z_min, z_max, shape, lo, pitch, tru
     tsdf = torch.empty(shape, dtype=torch.float32, device=dev)
     weight = torch.empty(shape, dtype=torch.int32, device=dev) if want_weight else None
     rgb = torch.empty(shape + (3,), dtype=torch.float32, device=dev) if colors is not None else None
-    L.check(L.lib().cnerf_tsdf_integrate(*shape, _cube_lo(lo), float(pitch), V, R, L.ptr(depth), L.ptr(colors), code, float(color_scale),
+    L.check(L.lib().cnerf_tsdf_integrate(*shape, _float3(lo), float(pitch), V, R, L.ptr(depth), L.ptr(colors), code, float(color_scale),
                                          float(color_offset), L.ptr(cams), float(focal), float(z_min), float(z_max), float(trunc), int(bool(carve)),
                                          int(hidden_min), float(unseen), L.ptr(tsdf), L.ptr(weight), L.ptr(rgb), _stream()), "cnerf_tsdf_integrate")
     return tsdf, weight, rgb
@@ -1100,10 +1080,7 @@ def render_rays_forward(net, levels, freq, phase, origins, dirs, o, rng=None, wa
     dev = origins.device
     cfg = _rays_cfg(net, o, levels, rng=rng)
     packed = pack_field(net, cfg)
-    nb = C.c_size_t(0)
-    ws_entry = "cnerf_render_rays_workspace_bytes" if occupancy is None else "cnerf_render_rays_masked_workspace_bytes"
-    L.check(getattr(L.lib(), ws_entry)(C.byref(cfg), P, C.byref(nb)), ws_entry)
-    ws = torch.empty(nb.value, dtype=torch.uint8, device=dev)
+    ws = _workspace("cnerf_render_rays_workspace_bytes" if occupancy is None else "cnerf_render_rays_masked_workspace_bytes", dev, C.byref(cfg), P)
     pixels = torch.empty((B, P, 3), dtype=torch.float32, device=dev)
     dist = torch.empty((B, P), dtype=torch.float32, device=dev)
     r, keep = _rng_struct(rng or {}, RAY_RNG_KEYS)

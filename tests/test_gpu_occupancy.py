@@ -4,8 +4,10 @@ cnerf_render_rays_masked_forward against the unmasked cnerf_render_rays_forward,
 
 Shapes: B = 2 with a different bit set per image; G in {4, 8, 12} for the build, 8 for the compaction and the renders, 32 for the
 truthful mask; point counts on both sides of a wave (32 / 64 would be the same path: 31, 32, 33), of a 256-thread round (255, 256, 257),
-several 2048-point chunks (5000) and more chunks than one round of the chunk scan holds (257 chunks: 2048 * 256 + 5); renders of 2 x 37
-rays with 12 (+ 12) or 10 samples, so that no count is a multiple of the 32-point tile.
+several 2048-point chunks (5000), a second chunk of a full wave and a wave of one lane whose first chunk has a round without a live
+point before a round of nothing else (2048 + 65: what the two LDS slots of the rank kernel are for) and more chunks than one round of
+the chunk scan holds (257 chunks: 2048 * 256 + 5); renders of 2 x 37 rays with 12 (+ 12) or 10 samples, so that no count is a multiple
+of the 32-point tile.
 
 Gates: every stage and every rgb_sigma bit for bit.  pixels / dist of a masked render against the oracle's merge + composite in float64 on
 the device's own masked rgb_sigma and depths: COMPOSITE_TOL = 1e-5, the gate of tests/test_gpu_ray_stages.py::test_composite_vs_float64
@@ -49,7 +51,10 @@ def mask_words(kind, G, seed):
         return np.full(G ** 3 // 32, 0xFFFFFFFF, np.uint32)
     if kind == "clear":
         return np.zeros(G ** 3 // 32, np.uint32)
-    return OC.pack_bits(np.random.default_rng(seed).random(G ** 3) < 0.5)
+    cells = np.random.default_rng(seed).random(G ** 3) < 0.5
+    if kind == "rounds":                                                      # the first cell clear, the last one set
+        cells[0], cells[-1] = False, True
+    return OC.pack_bits(cells)
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -86,26 +91,35 @@ def test_build_equals_numpy_word_for_word(dev, G, dilate):
 # ---------------------------------------------------------------------------------------------------------------------
 # 2. compaction and expansion
 # ---------------------------------------------------------------------------------------------------------------------
+ROUNDS_N = 2048 + 65
+
+
 def compaction_points(B, n, G, seed):
-    """Uniform over 1.3 x the box; the hand-made edge points replace the first rows (as many as fit)."""
+    """Uniform over 1.3 x the box; the hand-made edge points replace the first rows (as many as fit).  n = ROUNDS_N: the first 256
+    rows of image 1 (round 0 of its first chunk) sit in the first cell, the next 256 (round 1) in the last."""
     rng = np.random.default_rng(seed)
     pts = rng.uniform(1.3 * LO, 1.3 * (LO + SIDE), (B, n, 3)).astype(np.float32)
     edge = OC.edge_points(LO, SIDE, G)
     k = min(n, len(edge))
     pts[0, :k] = edge[:k]
     pts[1, n - k:] = edge[len(edge) - k:]
+    if n == ROUNDS_N:
+        pts[1, :256] = LO + 0.5 * SIDE / G
+        pts[1, 256:512] = LO + SIDE - 0.5 * SIDE / G
     return pts
 
 
-@pytest.mark.parametrize("n", [1, 31, 32, 33, 255, 256, 257, 5000, 2048 * 256 + 5])
+@pytest.mark.parametrize("n", [1, 31, 32, 33, 255, 256, 257, ROUNDS_N, 5000, 2048 * 256 + 5])
 def test_compaction_equals_numpy(dev, n):
     from cnerf_amd import ops
     B, G = 2, 8
     pts = compaction_points(B, n, G, n)
     d_pts = torch.from_numpy(pts).to(dev)
-    for kinds in (("set", "random"), ("clear", "random"), ("random", "clear")):
+    for kinds in (("set", "random"), ("clear", "random"), ("random", "clear")) + ((("random", "rounds"),) if n == ROUNDS_N else ()):
         words = np.stack([mask_words(k, G, 7 * n + i) for i, k in enumerate(kinds)])
         rank, counts, lv = OC.compact(pts, words, *BOX, G)
+        if "rounds" in kinds:
+            assert not lv[1, :256].any() and lv[1, 256:512].all()              # a round of 256 without a live point, then one of nothing else
         if n >= 5000:
             assert 0.3 < lv[kinds.index("random")].mean() < 0.9                # inside and skipped, inside and kept, outside
         pad = 64
