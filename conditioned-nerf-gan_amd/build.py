@@ -6,7 +6,7 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libcnerf_hip.so")
-SOURCES = ["abi_common.hip", "abi_forward.hip", "abi_backward.hip", "abi_rays.hip", "abi_shapes.hip", "field_kernel.hip", "field_h3.hip", "field_pw16.hip", "ray_kernels.hip", "ray_batch.hip", "grad_kernels.hip", "bwd16.hip", "chain_pw16.hip", "scatter_patch.hip", "points_grad.hip", "pfilm_finish.hip", "occupancy.hip", "isosurface.hip", "nearest.hip", "voxelize.hip", "reproject.hip", "tsdf.hip"]
+SOURCES = ["abi_common.hip", "abi_forward.hip", "abi_backward.hip", "abi_rays.hip", "abi_shapes.hip", "field_kernel.hip", "field_h3.hip", "field_pw16.hip", "ray_kernels.hip", "ray_batch.hip", "grad_kernels.hip", "bwd16.hip", "chain_pw16.hip", "scatter_patch.hip", "points_grad.hip", "pfilm_finish.hip", "occupancy.hip", "isosurface.hip", "components.hip", "nearest.hip", "voxelize.hip", "reproject.hip", "tsdf.hip"]
 HEADERS = ["abi_common.hpp", "cnerf_dev.hpp", "geom_dev.hpp", "cnerf_kernels.hpp", "field_common.hpp", "bwd16.hpp", "h3_dev.hpp", os.path.join("..", "..", "include", "cnerf.h")]
 # -ffp-contract=off: a*b+c is two roundings unless fmaf() is written (see csrc/cnerf_dev.hpp)
 FLAGS = ["--offload-arch=gfx950", "-O3", "-fPIC", "-std=c++17", "-ffp-contract=off", "-Wall", "-Wno-unused-function"]

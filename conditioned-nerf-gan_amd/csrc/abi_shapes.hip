@@ -1,4 +1,4 @@
-// C ABI (include/cnerf.h), shapes: isosurface meshes, nearest points, voxel grids of point clouds, depth maps <-> clouds, depth maps -> a TSDF lattice.
+// C ABI (include/cnerf.h), shapes: isosurface meshes, lattice components, nearest points, voxel grids of point clouds, depth maps <-> clouds, depth maps -> a TSDF lattice.
 #include "abi_common.hpp"
 
 using namespace cnerf;
@@ -316,6 +316,44 @@ int cnerf_isosurface_emit(int32_t n0, int32_t n1, int32_t n2, const float* value
                         vertices, vertex_attrs, triangles, (const uint8_t*)(ws + W.code), (const int32_t*)(ws + W.voff), (const int32_t*)(ws + W.toff),
                         (const int32_t*)(ws + W.sums)};
     if (hipError_t e = launch_iso_emit(a, (hipStream_t)stream)) return hip_fail(e, "iso_emit");
+    return CNERF_OK;
+}
+
+// connected components of a lattice (csrc/components.hip).  The refusals come in one order: shape, NULLs, level, connectivity, the
+// switches, min_size, fill.  Workspace: the 64-bit key of the largest component.
+int cnerf_components_bytes(int32_t n0, int32_t n1, int32_t n2, size_t* workspace) {
+    g_err[0] = 0;
+    if (int rc = check_iso_shape(n0, n1, n2, "components_bytes")) return rc;
+    if (workspace) *workspace = align256(sizeof(unsigned long long));
+    return CNERF_OK;
+}
+
+int cnerf_components_label(int32_t n0, int32_t n1, int32_t n2, const float* values, float level, int32_t invert, int32_t connectivity, int32_t* labels,
+                           int32_t* sizes, int32_t* stats, void* workspace, void* stream) {
+    g_err[0] = 0;
+    const char* who = "components_label";
+    if (int rc = check_iso_shape(n0, n1, n2, who)) return rc;
+    if (!values || !labels || !sizes || !stats || !workspace) return fail(CNERF_EINVAL, "%s: NULL argument (values / labels / sizes / stats / workspace)", who);
+    if (!(fabsf(level) < INFINITY)) return fail(CNERF_EINVAL, "%s: level=%g must be finite", who, (double)level);
+    if (connectivity != 6 && connectivity != 14) return fail(CNERF_EINVAL, "%s: connectivity=%d must be 6 or 14", who, connectivity);
+    if (invert != 0 && invert != 1) return fail(CNERF_EINVAL, "%s: invert=%d must be 0 or 1", who, invert);
+    if ((uintptr_t)workspace & 7) return fail(CNERF_EINVAL, "%s: workspace must be 8-byte aligned", who);
+    const CompLabelArgs a{iso_dims(n0, n1, n2), values, level, invert, connectivity == 6 ? 3 : 7, labels, sizes, stats, (unsigned long long*)workspace};
+    if (hipError_t e = launch_components_label(a, (hipStream_t)stream)) return hip_fail(e, "components_label");
+    return CNERF_OK;
+}
+
+int cnerf_components_filter(int32_t n0, int32_t n1, int32_t n2, const float* values, const int32_t* labels, const int32_t* sizes, const int32_t* stats,
+                            int32_t largest_only, int32_t min_size, float fill, float* out_values, void* stream) {
+    g_err[0] = 0;
+    const char* who = "components_filter";
+    if (int rc = check_iso_shape(n0, n1, n2, who)) return rc;
+    if (!values || !labels || !sizes || !stats || !out_values) return fail(CNERF_EINVAL, "%s: NULL argument (values / labels / sizes / stats / out_values)", who);
+    if (largest_only != 0 && largest_only != 1) return fail(CNERF_EINVAL, "%s: largest_only=%d must be 0 or 1", who, largest_only);
+    if (min_size < 0) return fail(CNERF_EINVAL, "%s: min_size=%d must be >= 0", who, min_size);
+    if (fill != fill) return fail(CNERF_EINVAL, "%s: fill is NaN", who);
+    const CompFilterArgs a{iso_dims(n0, n1, n2), values, labels, sizes, stats, largest_only, min_size, fill, out_values};
+    if (hipError_t e = launch_components_filter(a, (hipStream_t)stream)) return hip_fail(e, "components_filter");
     return CNERF_OK;
 }
 

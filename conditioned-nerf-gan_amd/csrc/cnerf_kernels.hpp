@@ -336,6 +336,32 @@ struct IsoEmitArgs {
 hipError_t launch_iso_count(const IsoCountArgs& a, hipStream_t stream);
 hipError_t launch_iso_emit(const IsoEmitArgs& a, hipStream_t stream);
 
+// components.hip: connected components of a scalar lattice by a union-find in `labels` (include/cnerf.h states the contract, DESIGN.md 3.25 the protocol)
+constexpr int COMP_BLOCK = ISO_BLOCK;        // lattice points of a block, one per lane: IsoDims.blocks counts these
+struct CompLabelArgs {
+    IsoDims d;
+    const float* values;         // (n0,n1,n2)
+    float level;
+    int invert;                  // 0: the INSIDE points (v > level) are selected, 1: all the others
+    int kinds;                   // forward neighbour kinds: 3 (axes: connectivity 6) or 7 (the Kuhn edges: connectivity 14)
+    int32_t* labels;             // (n) the parent array, in the end the root (smallest flat index of the component) or -1
+    int32_t* sizes;              // (n) points of the component at its root, 0 elsewhere
+    int32_t* stats;              // (4) components, root and size of the largest, status
+    unsigned long long* best;    // workspace: size << 32 | (0xFFFFFFFF - root) of the largest
+};
+struct CompFilterArgs {
+    IsoDims d;
+    const float* values;
+    const int32_t* labels;
+    const int32_t* sizes;
+    const int32_t* stats;
+    int largest_only, min_size;
+    float fill;
+    float* out;                  // (n), may be values
+};
+hipError_t launch_components_label(const CompLabelArgs& a, hipStream_t stream);
+hipError_t launch_components_filter(const CompFilterArgs& a, hipStream_t stream);
+
 // nearest.hip: exact nearest target of every query, brute force (include/cnerf.h states the contract, DESIGN.md 3.20 the tiling)
 constexpr int NN_QPT = 4;                    // queries a lane owns in registers
 constexpr int NN_QUERIES = NN_QPT * 64;      // queries of a block (one wave): cnerf_nearest_points_tiling's queries_per_block

@@ -54,14 +54,19 @@ def sample_generator(generator, z, voxel_resolution=256, voxel_origin=(0, 0, 0),
     return sig.reshape(N, N, N).cpu().numpy()
 
 
-def extract_mesh(generator, z, voxel_resolution=256, voxel_origin=(0, 0, 0), cube_length=1.2, level=0.0, colors=True, max_points=1 << 22):
+def extract_mesh(generator, z, voxel_resolution=256, voxel_origin=(0, 0, 0), cube_length=1.2, level=0.0, colors=True, max_points=1 << 22,
+                 keep_largest=False, min_component=0):
     """The level set sigma = level of one conditioned scene as an indexed triangle mesh on the device: vertices (Nv,3) float32, faces
     (Nt,3) int32, colors (Nv,3) float32 (the field's channels 0..2 interpolated along the crossed edges) or None.
 
     The grid is sample_generator's (same coordinates, same chunking).  Lattice point (i0,i1,i2) is given the position
     i_c * pitch + (corner[2], corner[1], corner[0])[c] -- create_samples' column convention; its columns 0 and 1 are not floored, so off
     the i2 = 0 face the field is sampled up to one pitch beyond that position on those axes, as in every grid the reference extracts.
-    The normals point toward falling sigma: out of the shape."""
+    The normals point toward falling sigma: out of the shape.
+
+    keep_largest / min_component: every blob of density above the level is a closed sheet of its own (a floater).  With keep_largest only
+    the largest connected solid is meshed, with min_component = k only solids of at least k lattice points (ops.keep_components on the very
+    lattice the isosurface reads, so its axes are the split's): what is left is, bit for bit, part of the unfiltered mesh."""
     N = int(voxel_resolution)
     pts, corner, pitch = create_samples(N, voxel_origin, cube_length)
     pts = pts.to(generator.device)
@@ -74,6 +79,8 @@ def extract_mesh(generator, z, voxel_resolution=256, voxel_origin=(0, 0, 0), cub
     sigma = field[..., 3].contiguous()
     attrs = field[..., :3].contiguous() if colors else None
     lo = (float(corner[2]), float(corner[1]), float(corner[0]))
+    if keep_largest or min_component > 0:
+        sigma = ops.keep_components(sigma, level, largest=keep_largest, min_size=min_component)
     return ops.isosurface(sigma, level, lo=lo, pitch=pitch, attrs=attrs)
 
 
@@ -89,11 +96,26 @@ def extract_mesh_tsdf(generator, z, cam2worlds, img_size, fov, ray_start, ray_en
     depth.  A cube no larger than the views cover: a voxel that only a view or two see, behind the object, counts as solid (the hidden
     rule, include/cnerf.h) and shows as a blob in a corner of the cube.  trunc (None: three pitches) of at least two or three pitches:
     with less, the inside end of a crossed edge may lie beyond the band in every view and have no colour (it then pulls the vertex's
-    colour toward black), and the surface follows single pixels.  render_kwargs go to the generator's forward."""
+    colour toward black), and the surface follows single pixels.
+
+    render_kwargs go to the generator's forward, but for four keywords that are taken out of them first (this function's parameter
+    list is fixed): hidden_min=1, keep_largest=False, min_component=0, fill_cavities=False.  hidden_min is views.tsdf_volume's.  The
+    others are for what more cameras or a smaller cube do not cure.  keep_largest meshes only the largest connected solid, and
+    min_component = k only solids of at least k lattice points: the blobs in the cube's corners go.  fill_cavities keeps the largest
+    connected free region, the one around the object, and makes every other one solid: the second, inner surface of a volume without
+    the hidden rule goes.  The solids are filtered first, then the cavities, by ops.keep_components on the volume the isosurface reads;
+    the fills are -1 and +1, the volume's own free and solid values, and what is left of the mesh is bit for bit part of the unfiltered
+    one."""
     from . import views
+    hidden_min, keep_largest = render_kwargs.pop("hidden_min", 1), render_kwargs.pop("keep_largest", False)
+    min_component, fill_cavities = render_kwargs.pop("min_component", 0), render_kwargs.pop("fill_cavities", False)
     pixels, depth = views.render_views(generator, z, cam2worlds, img_size, fov, ray_start, ray_end, num_steps, views_per_batch, **render_kwargs)
     tsdf, _, rgb, lo, pitch = views.tsdf_volume(pixels if colors else None, depth, cam2worlds, fov, ray_start, ray_end, resolution=voxel_resolution,
-                                                cube_length=cube_length, origin=voxel_origin, trunc=trunc)
+                                                cube_length=cube_length, origin=voxel_origin, trunc=trunc, hidden_min=hidden_min)
+    if keep_largest or min_component > 0:
+        tsdf = ops.keep_components(tsdf, 0.0, largest=keep_largest, min_size=min_component, fill=-1.0)
+    if fill_cavities:
+        tsdf = ops.keep_components(tsdf, 0.0, largest=True, fill=1.0, invert=True)
     return ops.isosurface(tsdf, 0.0, lo=lo, pitch=pitch, attrs=rgb)
 
 

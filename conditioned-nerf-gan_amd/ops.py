@@ -818,6 +818,52 @@ def isosurface(values, level, lo=(0.0, 0.0, 0.0), pitch=1.0, attrs=None):
     return vertices, faces, vertex_attrs
 
 
+def _lattice(values, who):
+    """values as a components call takes them -> detached contiguous float32 (N0,N1,N2) and its three sizes."""
+    values = _f32(values.detach())
+    if values.dim() != 3:
+        raise L.CnerfError(f"{who}: values must be (N0,N1,N2), got {tuple(values.shape)}")
+    return values, tuple(int(s) for s in values.shape)
+
+
+def connected_components(values, level, invert=False, connectivity=14):
+    """cnerf_components_label: the connected components of the points of a scalar lattice values (N0,N1,N2) that are INSIDE (v > level,
+    the rule of isosurface; invert=True: of all the others).  connectivity=14 joins points that differ by +-(d0,d1,d2), d in {0,1}^3 \\ 0:
+    the edges isosurface puts vertices on, so the components are the pieces its mesh separates; 6 is the axis neighbourhood.
+    -> labels (N0,N1,N2) int32 (-1 where not selected, else the smallest flat index of the component), sizes (N0,N1,N2) int32 (the point
+    count at each root, 0 elsewhere), stats int32[4] (components, root and size of the largest, status) -- all on the device, nothing is
+    read back here: stats[3] != 0 says that a loop cap was hit and the rest is not to be used.  include/cnerf.h states the contract."""
+    values, (n0, n1, n2) = _lattice(values, "connected_components")
+    dev = values.device
+    ws = _workspace("cnerf_components_bytes", dev, n0, n1, n2)
+    labels = torch.empty((n0, n1, n2), dtype=torch.int32, device=dev)
+    sizes = torch.empty_like(labels)
+    stats = torch.empty((4,), dtype=torch.int32, device=dev)
+    L.check(L.lib().cnerf_components_label(n0, n1, n2, L.ptr(values), float(level), int(bool(invert)), int(connectivity), L.ptr(labels), L.ptr(sizes),
+                                           L.ptr(stats), L.ptr(ws), _stream()), "cnerf_components_label")
+    return labels, sizes, stats
+
+
+def keep_components(values, level, largest=True, min_size=0, fill=None, invert=False, connectivity=14, return_labels=False):
+    """connected_components, then cnerf_components_filter: the lattice with every selected component that is not the largest (largest=True)
+    or has fewer than min_size points overwritten by `fill`, which puts it on the other side of the level: None stands for -inf (+inf with
+    invert); a fill on the selected side (> level without invert, not > level with it) is a ValueError.  All else is copied; with
+    connectivity 14, isosurface of the result is the mesh of `values` less the sheets of those components, bit for bit.
+    -> the filtered (N0,N1,N2) float32 lattice, a new tensor; with return_labels also labels, sizes, stats of connected_components.
+    Nothing is read back from the device."""
+    values, (n0, n1, n2) = _lattice(values, "keep_components")
+    if fill is None:
+        fill = float("inf") if invert else float("-inf")
+    fill = C.c_float(fill).value                                  # as the C call rounds it, and the level beside it
+    if fill != fill or (fill > C.c_float(level).value) != bool(invert):
+        raise ValueError(f"keep_components: fill={fill} must{'' if invert else ' not'} be > level={level} with invert={bool(invert)}")
+    labels, sizes, stats = connected_components(values, level, invert=invert, connectivity=connectivity)
+    out = torch.empty_like(values)
+    L.check(L.lib().cnerf_components_filter(n0, n1, n2, L.ptr(values), L.ptr(labels), L.ptr(sizes), L.ptr(stats), int(bool(largest)), int(min_size), fill,
+                                            L.ptr(out), _stream()), "cnerf_components_filter")
+    return (out, labels, sizes, stats) if return_labels else out
+
+
 def _cloud_lengths(lengths, B, dev, what, who="nearest_points"):
     """Per-image lengths of a padded cloud -> contiguous int32 (B,) on `dev`, or None."""
     if lengths is None:

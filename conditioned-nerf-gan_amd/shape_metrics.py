@@ -212,6 +212,8 @@ def mesh_metrics(vertices, faces, cloud, n_samples=100_000, tau=0.01, u=None, re
 def reconstruction_metrics(generator, z, cloud, voxel_resolution=128, cube_length=1.2, level=10.0, n_samples=100_000, tau=0.01, u=None,
                            return_samples=False):
     """How far the surface of one conditioned scene lies from a point cloud (the one it was conditioned on): extract_mesh at `level`,
-    then mesh_metrics of that mesh against the cloud, which states the samples, the scores and what is returned."""
+    then mesh_metrics of that mesh against the cloud, which states the samples, the scores and what is returned.  Floaters are
+    sampled by area like the object and count against both scores: to score the object alone, mesh_metrics of
+    extract_mesh(..., keep_largest=True)."""
     vertices, faces, _ = extract_shapes.extract_mesh(generator, z, voxel_resolution=voxel_resolution, cube_length=cube_length, level=level, colors=False)
     return mesh_metrics(vertices, faces, cloud, n_samples=n_samples, tau=tau, u=u, return_samples=return_samples)

@@ -758,6 +758,50 @@ int cnerf_isosurface_emit(int32_t n0, int32_t n1, int32_t n2, const float* value
                           float* vertices /* (max_vertices,3) */, float* vertex_attrs /* (max_vertices,C) or NULL */,
                           int32_t* triangles /* (max_triangles,3) */, const void* workspace /* as count left it */, void* stream);
 
+/* ---- connected components of a scalar lattice (added in ABI v10 without a version change: additive symbols only) -----------------------
+ * What a mesh of a raw density or of a fused volume needs next: which lattice points hang together, so that floaters can be dropped
+ * and enclosed free space filled before cnerf_isosurface_* runs, without the lattice leaving the device.  Everything here is an integer
+ * and fixed by the lattice alone, so it can be checked exactly.
+ *
+ * Lattice.  values v[i0,i1,i2], (n0,n1,n2) row-major fp32, the limits of cnerf_isosurface_*: each n_c in [2,1024], n0 n1 n2 <= 2^27.
+ *   The flat index of a point is (i0 n1 + i1) n2 + i2.
+ * Selection.  A point is INSIDE iff v > level, the isosurface's rule: a value equal to the level is outside, a NaN is outside.
+ *   invert = 0 selects the INSIDE points, invert = 1 all the others.
+ * Neighbours.  connectivity = 14: two selected points are joined iff they differ by +-(d0,d1,d2), (d0,d1,d2) in {0,1}^3 \ 0 -- the
+ *   seven edge kinds of the isosurface's Kuhn split, in both directions ((1,-1,0) is not among them).  These are exactly the lattice
+ *   edges on which cnerf_isosurface_* places a vertex when the ends differ in INSIDE, so the components are the pieces that the mesh
+ *   separates: moving a whole component to the other side of the level removes its sheets and nothing else, and every vertex and
+ *   triangle that is left is bit for bit one of the unfiltered mesh.  Marching tetrahedra treats inside and outside alike, so the same
+ *   neighbourhood serves invert = 1.  connectivity = 6: the three axis kinds only (the customary neighbourhood; the property above does
+ *   not hold for it).
+ * Results.
+ *   labels (n0,n1,n2) int32   -1 for a point that is not selected, else the smallest flat index among the points of its component
+ *                             (the component's root: labels[root] == root)
+ *   sizes  (n0,n1,n2) int32   the point count of a component at the position of its root, 0 everywhere else
+ *   stats  DEVICE int32[4]    n_components; largest_root (the root of the component with the most points, at equal size the lowest
+ *                             root, -1 if there is no component); largest_size; status (0, or non-zero if a loop cap was hit: the
+ *                             other results are then not to be used.  A chain of parents cannot be longer than the lattice has points,
+ *                             which is the cap of every loop that follows one, so correct code never reaches it.)
+ *   All of them are independent of launch geometry and arrival order: two runs agree bit for bit.
+ *
+ *   cnerf_components_bytes    workspace of cnerf_components_label (the 64-bit key of the largest component; 8-byte aligned).
+ *   cnerf_components_label    fills labels, sizes and stats.  labels doubles as the parent array of a union-find in global memory.
+ *   cnerf_components_filter   out_values = values, but `fill` where a labelled point's component fails  size >= min_size  or, with
+ *                             largest_only = 1,  root == largest_root.  Points with label -1 are copied; with no component at all
+ *                             out_values = values.  It reads stats on the device; out_values may be values itself.  The filter does
+ *                             not know the level: a caller that wants the failed components on the other side passes such a fill.
+ * All are asynchronous on `stream`, allocate nothing, do not synchronise with the host and need no host readback.
+ * CNERF_EINVAL before any launch, checked in this order: an n_c outside [2,1024] or n0 n1 n2 > 2^27; values / labels / sizes / stats /
+ * workspace / out_values NULL; level not finite; connectivity other than 6 or 14; invert or largest_only outside {0,1}; min_size < 0;
+ * fill NaN; (last) a workspace that is not 8-byte aligned. */
+int cnerf_components_bytes(int32_t n0, int32_t n1, int32_t n2, size_t* workspace);
+int cnerf_components_label(int32_t n0, int32_t n1, int32_t n2, const float* values, float level, int32_t invert, int32_t connectivity,
+                           int32_t* labels /* (n0,n1,n2) */, int32_t* sizes /* (n0,n1,n2) */, int32_t* stats /* DEVICE int32[4] */,
+                           void* workspace, void* stream);
+int cnerf_components_filter(int32_t n0, int32_t n1, int32_t n2, const float* values, const int32_t* labels, const int32_t* sizes,
+                            const int32_t* stats, int32_t largest_only, int32_t min_size, float fill,
+                            float* out_values /* (n0,n1,n2), may be values */, void* stream);
+
 /* ---- nearest points: the nearest target of every query, between two batched clouds (added in ABI v10 without a version change:
  * additive symbols only) --------------------------------------------------------------------------------------------------------------
  * The primitive under the Chamfer distance and the F-score of a reconstruction (shape_metrics.py).  The search is exact and brute force:
