@@ -63,6 +63,16 @@ FieldArgs storing_args(const FieldArgs& a, long long n_points, void* feat, void*
     return s;
 }
 
+// The storing re-run of a half-precision chunk, FiLM / plain-sine / residual networks (field_h3.hip, STORE_TB16 on the shared weights):
+// the chunk's pass `fa` again, leaving its gradient volumes alone.  ONE launch for chunk16 and for the stage entry cnerf_field_store16.
+int store16_forward(FieldArgs fa, int H, long long n_points, void* feat, void* h, void* c, void* scratch, hipStream_t stream) {
+    for (float*& g : fa.lvl_grad) g = nullptr;
+    fa.gin = nullptr;
+    if (hipError_t e = launch_field_h3(storing_args(fa, n_points, feat, h, c, nullptr, scratch), H, stream))
+        return hip_fail(e, "field kernel (fp16 activation store)");
+    return CNERF_OK;
+}
+
 // The exact fp32 backward of one field pass `fa` (n_points rows, gradient volumes and dropout set): the activation-storing re-run
 // in cfg->precision (`packed` is in that precision's layout), then the fp32 gradient chain on the transposed fp32 weights, which
 // scatters d(feature volume) itself.  grad_out / saved_out: the rows of this launch.
@@ -628,14 +638,8 @@ int chunk16(const cnerf_cfg* cfg, const MatrixSet& ms, const BackwardLayout& L, 
     float* scales = (float*)(ws + L.scales);
     char* a_g = ws + L.a_g;
     char* a_go = ws + L.a_go;
-    auto store_forward = [&]() -> int {      // the storing re-run leaves the gradient volumes alone
-        if (!store) return CNERF_OK;
-        FieldArgs fa = fc;
-        for (float*& g : fa.lvl_grad) g = nullptr;
-        fa.gin = nullptr;
-        if (hipError_t e = launch_field_h3(storing_args(fa, (long long)k.cnt * k.npi, a_feat, a_h, a_c, nullptr, a_g), H, stream))
-            return hip_fail(e, "field kernel (fp16 activation store)");
-        return CNERF_OK;
+    auto store_forward = [&]() -> int {
+        return store ? store16_forward(fc, H, (long long)k.cnt * k.npi, a_feat, a_h, a_c, a_g, stream) : (int)CNERF_OK;
     };
     if (int rc = chain16_sequence(cfg, packed_bwd, fc, k.cnt, k.npi, k.tpi, g_out, s_out, a_c, a_g, a_go, (uint32_t*)(ws + L.gmax), scales, 0, saturated,
                                   stream, store_forward))
@@ -819,6 +823,30 @@ int cnerf_field_chain16(const cnerf_cfg* cfg, int32_t pass, int32_t image0, int3
     if (hipError_t e = hipMemsetAsync(go16, 0, (size_t)n_images * tpi * 2048, stream)) return hip_fail(e, "memset");
     return chain16_sequence(cfg, packed16, fc, n_images, npi, tpi, grad_rgb_sigma + (size_t)image0 * npi * 4, saved_rgb_sigma + (size_t)image0 * npi * 4,
                             cos16, g16, go16, gmax, scales, group_step, saturated, stream, [] { return (int)CNERF_OK; });
+}
+
+int cnerf_field_store16(const cnerf_cfg* cfg, int32_t pass, int32_t image0, int32_t n_images, const cnerf_volumes* vols, const float* packed,
+                        const float* freq, const float* phase, const float* cam2world, const float* u_strat, const float* fine_z, void* feat,
+                        void* h, void* c, float* rgb_sigma, void* stream) {
+    g_err[0] = 0;
+    if (int rc = check_cfg(cfg, true)) return rc;        // (drop_p != 0 with a half-precision cfg is refused here)
+    if (cfg->layer_kind[0] == CNERF_LAYER_PFILM)
+        return fail(CNERF_EINVAL, "field_store16: FiLM / plain-sine / residual layers only (the per-point FiLM family has a storing forward of its own)");
+    if (cfg->precision != CNERF_PREC_FP16X3) return fail(CNERF_EINVAL, "field_store16: a stage of the fp16 backward: cfg->precision must be CNERF_PREC_FP16X3");
+    if (pass < 0 || pass > 2) return fail(CNERF_EINVAL, "field_store16: pass must be 0 (coarse), 1 (fine) or 2 (explicit points)");
+    if (image0 < 0 || n_images < 1 || image0 + n_images > cfg->B) return fail(CNERF_EINVAL, "field_store16: image range out of [0,B)");
+    if ((!vols && !no_volume(cfg)) || !packed || !feat || !h || !c || !rgb_sigma)
+        return fail(CNERF_EINVAL, "field_store16: NULL argument (vols, packed, feat, h, c, rgb_sigma)");
+    if (counts_of(cfg).n_film && (!freq || !phase)) return fail(CNERF_EINVAL, "field_store16: FiLM layers need freq and phase");
+    if (pass != 2 && !cam2world) return fail(CNERF_EINVAL, "field_store16: NULL argument (cam2world of a ray pass)");
+    if (pass == 1 && !fine_z) return fail(CNERF_EINVAL, "field_store16: the fine pass needs fine_z");
+    if (pass == 2 && !u_strat) return fail(CNERF_EINVAL, "field_store16: pass 2 takes the points (B,R*R*S,3) in the u_strat argument");
+    // explicit points need no camera: packed stands in for the address pass_args offsets (it dereferences nothing)
+    FieldArgs fa;
+    if (int rc = pass_args(fa, cfg, pass, image0, n_images, vols, nullptr, packed, freq, phase, pass == 2 ? packed : cam2world, u_strat, fine_z)) return rc;
+    if (pass == 2) fa.cam2world = nullptr;
+    const long long npi = (long long)cfg->R * cfg->R * cfg->S;
+    return store16_forward(fa, cfg->H, (long long)n_images * npi, feat, h, c, rgb_sigma, (hipStream_t)stream);
 }
 
 int cnerf_field_chain_pw16(const cnerf_cfg* cfg, int32_t pass, int32_t image0, int32_t n_images, const void* packed16, const float* cam2world,

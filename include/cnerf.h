@@ -445,6 +445,32 @@ int cnerf_field_chain16(const cnerf_cfg* cfg, int32_t pass, int32_t image0, int3
                         const float* saved_rgb_sigma, const void* cos16, int32_t group_step, void* g16, void* go16, float* scales, uint32_t* gmax,
                         float* gin, const cnerf_grad_volumes* grad_vols, uint32_t* saturated, void* stream);
 
+/* Stage entry of the activation-storing re-run in front of that chain (csrc/field_h3.hip, field_h3_kernel<NT, STORE_TB16, HAS_RES, WF = 0>;
+ * FiLM / plain-sine / residual networks), for hosts that sequence the stages themselves and what tests/test_gpu_store16.py holds to
+ * float64 row by row (added in ABI v10 without a version change: no struct changed).  On the caller's buffers it runs the ONE launch
+ * cnerf_render_backward runs per pass and chunk when the forward kept no activations: the field pass over images [image0, image0 +
+ * n_images) of `pass` (0 / 1 / 2 as cnerf_field_backward; pass 2: u_strat carries the points (B, R*R*S, 3)) again on the fp16x3 kernel,
+ * storing what the chain and the weight reductions read.  vols, freq, phase, cam2world, u_strat, fine_z are the FULL tensors of the call
+ * described by cfg (the function offsets them); packed: cnerf_pack_field in CNERF_PREC_FP16X3.  tiles = n_images * ceil(R*R*S / 32),
+ * NT = H / 32, n_in = layer 0's 32-wide input tiles (per level its channel tiles, then the xyz tile), n_mats as for cnerf_field_chain16.
+ * Outputs, fp16, 16-byte aligned, the chunk's first image first (tile T = image of the chunk * ceil(R*R*S / 32) + tile of the image):
+ *   feat            TB16 (tiles, n_in, 32, 32): layer 0's input rows, fp16(clamp(x, +-65504)); an xyz tile holds the position in columns
+ *                   0..2 and zeros in 3..31.
+ *   h               TB16 (n_mats, tiles, NT, 32, 32): sin(arg) of every slab; channel 32 t + k of point j of tile T ->
+ *                   (((m * tiles + T) * NT + t) * 32 + j) * 32 + k.
+ *   c               COS16 (n_mats, tiles, NT, 4, 64, 4): cos(arg), the layout of cnerf_field_chain16's cos16.
+ *   rgb_sigma       (n_images * R*R*S, 4) fp32: the head's output (cnerf_render_backward discards it into a scratch buffer).
+ * Rows past an image's end (the padded lanes of an image's last tile) hold the rows of the image's LAST point, in feat, h and c alike:
+ * cnerf_weight_grad16 multiplies them by the chain's zero gradient rows, so they must be finite whatever the buffer held before.  A wave
+ * without a tile (the tiles of an image are worked on in groups of four) stores nothing: the buffers have no block for it, and nothing
+ * outside the chunk's tiles is written.
+ * CNERF_EINVAL and no launch: per-point FiLM networks, cfg->precision != CNERF_PREC_FP16X3, drop_p != 0 (dropout exists in fp32 only),
+ * pass outside 0..2, an image range outside [0, B), a NULL required argument (vols of a network with a volume or one of its levels, packed,
+ * freq / phase of a FiLM network, cam2world of a ray pass, fine_z of the fine pass, the points of pass 2, an output). */
+int cnerf_field_store16(const cnerf_cfg* cfg, int32_t pass, int32_t image0, int32_t n_images, const cnerf_volumes* vols, const float* packed,
+                        const float* freq, const float* phase, const float* cam2world, const float* u_strat, const float* fine_z, void* feat,
+                        void* h, void* c, float* rgb_sigma, void* stream);
+
 /* Stage entry of the half-precision gradient chain of the per-point FiLM family (csrc/chain_pw16.hip: chain_pre_kernel, pw_gm_kernel),
  * the counterpart of cnerf_field_chain16 and what tests/test_gpu_chain_pw16.py holds to float64 row by row (added in ABI v10 without a
  * version change: no struct changed).  On the caller's buffers it runs the launches cnerf_render_backward runs per pass and chunk between
