@@ -115,6 +115,7 @@ PROTOTYPES = {
     "cnerf_field_chain16": (C.c_int, [C.POINTER(Cfg), C.c_int32, C.c_int32, C.c_int32] + [C.c_void_p] * 8 + [C.c_int32] + [C.c_void_p] * 5 +
                             [C.POINTER(Volumes), C.c_void_p, C.c_void_p]),
     "cnerf_field_store16": (C.c_int, [C.POINTER(Cfg), C.c_int32, C.c_int32, C.c_int32, C.POINTER(Volumes)] + [C.c_void_p] * 11),
+    "cnerf_field_store_pw16": (C.c_int, [C.POINTER(Cfg), C.c_int32, C.c_int32, C.c_int32, C.POINTER(Volumes)] + [C.c_void_p] * 10),
     "cnerf_field_chain_pw16": (C.c_int, [C.POINTER(Cfg), C.c_int32, C.c_int32, C.c_int32] + [C.c_void_p] * 9 + [C.c_int32] + [C.c_void_p] * 5 +
                                [C.POINTER(Volumes), C.c_void_p, C.c_void_p]),
     "cnerf_field_query_backward_workspace_bytes": (C.c_int, [C.POINTER(Cfg), C.c_int32, C.c_int64, C.POINTER(C.c_size_t)]),

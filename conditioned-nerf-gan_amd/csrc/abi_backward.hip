@@ -50,10 +50,11 @@ PointsGradArgs points_grad_args(const cnerf_cfg* c, const cnerf_volumes* vols, i
 }
 
 // the activation-storing re-run of a half-precision backward: the pass `a` again, storing fp16 TB16 activations (amax: per-point FiLM
-// family only); its head output goes to `scratch`, (n,4) floats nobody reads -- the chain overwrites that buffer entirely
-FieldArgs storing_args(const FieldArgs& a, long long n_points, void* feat, void* h, void* c, float* amax, void* scratch) {
+// family only); its head output goes to `rgb_sigma`, (n,4) floats: the stage entries hand it to the caller (it equals the non-storing
+// kernel's), the chunk drivers point it at a workspace buffer nobody reads -- the chain overwrites that buffer entirely
+FieldArgs storing_args(const FieldArgs& a, long long n_points, void* feat, void* h, void* c, float* amax, void* rgb_sigma) {
     FieldArgs s = a;
-    s.rgb_sigma = (float*)scratch;
+    s.rgb_sigma = (float*)rgb_sigma;
     s.act_points = n_points;
     s.act_feat = (float*)feat;
     s.act_h = (float*)h;
@@ -65,10 +66,19 @@ FieldArgs storing_args(const FieldArgs& a, long long n_points, void* feat, void*
 
 // The storing re-run of a half-precision chunk, FiLM / plain-sine / residual networks (field_h3.hip, STORE_TB16 on the shared weights):
 // the chunk's pass `fa` again, leaving its gradient volumes alone.  ONE launch for chunk16 and for the stage entry cnerf_field_store16.
-int store16_forward(FieldArgs fa, int H, long long n_points, void* feat, void* h, void* c, void* scratch, hipStream_t stream) {
+int store16_forward(FieldArgs fa, int H, long long n_points, void* feat, void* h, void* c, void* rgb_sigma, hipStream_t stream) {
     for (float*& g : fa.lvl_grad) g = nullptr;
     fa.gin = nullptr;
-    if (hipError_t e = launch_field_h3(storing_args(fa, n_points, feat, h, c, nullptr, scratch), H, stream))
+    if (hipError_t e = launch_field_h3(storing_args(fa, n_points, feat, h, c, nullptr, rgb_sigma), H, stream))
+        return hip_fail(e, "field kernel (fp16 activation store)");
+    return CNERF_OK;
+}
+
+// The storing forward of a half-precision per-point FiLM chunk (field_pw16.hip: field_pw16_kernel<NT, STORE> for y, cos, m and the input
+// tiles, then pw_deriv_kernel for cos f, cos 15 pre and amax): the chunk's pass `fa` again; the kernels read no gradient volume.  ONE
+// launch for chunk_pw16 and for the stage entry cnerf_field_store_pw16.
+int store_pw16_forward(const FieldArgs& fa, int H, long long n_points, void* feat, void* h, void* c, float* amax, void* rgb_sigma, hipStream_t stream) {
+    if (hipError_t e = launch_field_pw3(storing_args(fa, n_points, feat, h, c, amax, rgb_sigma), H, stream))
         return hip_fail(e, "field kernel (fp16 activation store)");
     return CNERF_OK;
 }
@@ -717,8 +727,7 @@ int chunk_pw16(const cnerf_cfg* cfg, const BackwardLayout& L, char* ws, const vo
     float* dwarg = (float*)(ws + L.dwarg);
     float* cs = (float*)(ws + L.cs);
     if (store)
-        if (hipError_t e = launch_field_pw3(storing_args(fa, (long long)k.cnt * k.npi, a_feat, a_h, a_c, a_amax, a_g), H, stream))
-            return hip_fail(e, "field kernel (fp16 activation store)");
+        if (int rc = store_pw16_forward(fa, H, (long long)k.cnt * k.npi, a_feat, a_h, a_c, a_amax, a_g, stream)) return rc;
     const size_t slabH = (size_t)T * NT * 2048;            // bytes per (tiles, NT, 32, 32) slab
     if (int rc = chain_pw16_sequence(cfg, packed_bwd, fa, k.cnt, k.npi, k.tpi, g_out, s_out, a_c, a_amax, a_h + (size_t)Lc * slabH, ws + L.a_gy, a_g, a_go,
                                      (uint32_t*)(ws + L.gmax), scales, 0, saturated, stream))
@@ -847,6 +856,30 @@ int cnerf_field_store16(const cnerf_cfg* cfg, int32_t pass, int32_t image0, int3
     if (pass == 2) fa.cam2world = nullptr;
     const long long npi = (long long)cfg->R * cfg->R * cfg->S;
     return store16_forward(fa, cfg->H, (long long)n_images * npi, feat, h, c, rgb_sigma, (hipStream_t)stream);
+}
+
+int cnerf_field_store_pw16(const cnerf_cfg* cfg, int32_t pass, int32_t image0, int32_t n_images, const cnerf_volumes* vols, const float* packed,
+                           const float* cam2world, const float* u_strat, const float* fine_z, void* feat, void* h, void* c, float* amax,
+                           float* rgb_sigma, void* stream) {
+    g_err[0] = 0;
+    if (int rc = check_cfg(cfg, true)) return rc;        // (drop_p != 0 with a half-precision cfg is refused here)
+    if (cfg->layer_kind[0] != CNERF_LAYER_PFILM)
+        return fail(CNERF_EINVAL, "field_store_pw16: per-point FiLM networks only (FiLM / plain-sine / residual layers: cnerf_field_store16)");
+    if (cfg->C != 32 || cfg->n_levels > 1) return fail(CNERF_EINVAL, "field_store_pw16: single 32-channel volume only");
+    if (cfg->precision != CNERF_PREC_FP16X3) return fail(CNERF_EINVAL, "field_store_pw16: a stage of the fp16 backward: cfg->precision must be CNERF_PREC_FP16X3");
+    if (pass < 0 || pass > 2) return fail(CNERF_EINVAL, "field_store_pw16: pass must be 0 (coarse), 1 (fine) or 2 (explicit points)");
+    if (image0 < 0 || n_images < 1 || image0 + n_images > cfg->B) return fail(CNERF_EINVAL, "field_store_pw16: image range out of [0,B)");
+    if (!vols || !packed || !feat || !h || !c || !amax || !rgb_sigma)
+        return fail(CNERF_EINVAL, "field_store_pw16: NULL argument (vols, packed, feat, h, c, amax, rgb_sigma)");
+    if (pass != 2 && !cam2world) return fail(CNERF_EINVAL, "field_store_pw16: NULL argument (cam2world of a ray pass)");
+    if (pass == 1 && !fine_z) return fail(CNERF_EINVAL, "field_store_pw16: the fine pass needs fine_z");
+    if (pass == 2 && !u_strat) return fail(CNERF_EINVAL, "field_store_pw16: pass 2 takes the points (B,R*R*S,3) in the u_strat argument");
+    // explicit points need no camera: packed stands in for the address pass_args offsets (it dereferences nothing)
+    FieldArgs fa;
+    if (int rc = pass_args(fa, cfg, pass, image0, n_images, vols, nullptr, packed, nullptr, nullptr, pass == 2 ? packed : cam2world, u_strat, fine_z)) return rc;
+    if (pass == 2) fa.cam2world = nullptr;
+    const long long npi = (long long)cfg->R * cfg->R * cfg->S;
+    return store_pw16_forward(fa, cfg->H, (long long)n_images * npi, feat, h, c, amax, rgb_sigma, (hipStream_t)stream);
 }
 
 int cnerf_field_chain_pw16(const cnerf_cfg* cfg, int32_t pass, int32_t image0, int32_t n_images, const void* packed16, const float* cam2world,

@@ -343,7 +343,8 @@ __global__ __launch_bounds__(256) void field_pw16_kernel(FieldArgs a) {
 // rows, loaded straight into MFMA B fragments: a lane's eight channels of a k-chunk are two 8-byte pieces of its point's row) and cos(arg).
 // One MFMA per 16 k-values on the LEADING fp16 part of the forward's own two-part weight stream (the hi pieces of a unit are every other
 // KiB; same scales, same starting values): f and 15 pre are derivative factors about to be rounded to fp16, and the operands they come
-// from are fp16 here (relative 6e-4 on 15 pre, 1e-4 on f).  Units used per tile: W_0 | layer 0: fr_t | layers >= 1: fr_t, pre_t; the
+// from are fp16 here (f: relative 1e-4; 15 pre: 2e-4 of the row's largest value, up to 3e-3 of an element >= 1 whose sum cancels --
+// tests/store_pw16_common.py (e) holds both rows to the bound of this arithmetic).  Units used per tile: W_0 | layer 0: fr_t | layers >= 1: fr_t, pre_t; the
 // epilogue of tile t-1 rides under fr_t.  HBM-bound: 8.5 KiB read + 8 KiB written per point and 8 layers.
 // ---------------------------------------------------------------------------------------------------------------
 template <int KC, typename PerChunk>

@@ -471,6 +471,34 @@ int cnerf_field_store16(const cnerf_cfg* cfg, int32_t pass, int32_t image0, int3
                         const float* freq, const float* phase, const float* cam2world, const float* u_strat, const float* fine_z, void* feat,
                         void* h, void* c, float* rgb_sigma, void* stream);
 
+/* Stage entry of the storing forward of the per-point FiLM family (csrc/field_pw16.hip: field_pw16_kernel<NT, STORE = true>, then
+ * pw_deriv_kernel<NT>), the counterpart of cnerf_field_store16 and what tests/test_gpu_store_pw16.py holds to float64 row by row (added
+ * in ABI v10 without a version change: no struct changed).  On the caller's buffers it runs the ONE launch pair cnerf_render_backward
+ * runs per pass and chunk when the forward kept no activations.  pass / image0 / n_images / vols / cam2world / u_strat / fine_z as for
+ * cnerf_field_store16 (the FULL tensors of the call; pass 2: u_strat carries the points); packed: cnerf_pack_field in
+ * CNERF_PREC_FP16X3.  tiles = n_images * ceil(R*R*S / 32), L = cfg->L, NT = H / 32.  Outputs, 16-byte aligned, the chunk's first image
+ * first (tile T = image of the chunk * ceil(R*R*S / 32) + tile of the image):
+ *   feat            TB16 (tiles, 2, 32, 32) fp16: tile 0 the looked-up feature, fp16(clamp(x, +-65504)); tile 1 the position, rounded to
+ *                   nearest, in columns 0..2 and zeros in 3..31.
+ *   h               L TB16 slabs (tiles, NT, 32, 32) fp16: y_l = sin(arg_l); then TB16 (tiles, 8, 32, 32): m = LeakyReLU_0.2(Wm1 feat +
+ *                   bm1), clamped to +-65504.
+ *   c               3 L COS16 slabs (tiles, NT, 4, 64, 4) fp16, the layout of cnerf_field_chain_pw16's cos16: per layer cos(arg_l),
+ *                   cos(arg_l) f_l, cos(arg_l) 15 pre_l (f_l = 15 fr_l + 30), the latter two clamped to +-65504.  They are formed by
+ *                   pw_deriv_kernel from the STORED cos, m and y_{l-1} (layer 0: the fp16 position) with the leading fp16 part of each
+ *                   scaled weight (rounded to nearest: relative 2^-11 per weight).
+ *   amax            (L, tiles * 32) fp32: max(1, largest |stored cos f|, |stored cos 15 pre| of the point and layer before their fp16
+ *                   rounding): 1 <= amax, every stored derivative d of the point has |d| <= amax (1 + 2^-11).
+ *   rgb_sigma       (n_images * R*R*S, 4) fp32: the head's output, equal to cnerf_field_forward's in CNERF_PREC_FP16X3.
+ * Rows past an image's end (the padded lanes of an image's last tile) hold the rows of the image's LAST point in feat, y, m, all 3 L
+ * slabs of c and amax: the weight reductions multiply them by zero gradient rows (they must be finite whatever the buffer held), and
+ * those of amax enter the layer maximum r_l comes from.  A wave without a tile stores nothing; nothing outside the chunk's tiles is written.
+ * CNERF_EINVAL and no launch: another layer family, cfg->precision != CNERF_PREC_FP16X3, drop_p != 0, a volume other than one 32-channel
+ * level, pass outside 0..2, an image range outside [0, B), a NULL required argument (vols or its level, packed, cam2world of a ray
+ * pass, fine_z of the fine pass, the points of pass 2, an output). */
+int cnerf_field_store_pw16(const cnerf_cfg* cfg, int32_t pass, int32_t image0, int32_t n_images, const cnerf_volumes* vols, const float* packed,
+                           const float* cam2world, const float* u_strat, const float* fine_z, void* feat, void* h, void* c, float* amax,
+                           float* rgb_sigma, void* stream);
+
 /* Stage entry of the half-precision gradient chain of the per-point FiLM family (csrc/chain_pw16.hip: chain_pre_kernel, pw_gm_kernel),
  * the counterpart of cnerf_field_chain16 and what tests/test_gpu_chain_pw16.py holds to float64 row by row (added in ABI v10 without a
  * version change: no struct changed).  On the caller's buffers it runs the launches cnerf_render_backward runs per pass and chunk between

@@ -12,7 +12,9 @@ an honest float32 emulation passes them and that each named hazard fails one.
 Shapes: H = 64 / 128 / 256 (NT 2 / 4 / 8; the KCH < 16 tail exists at 64 / 128); every family at H = 64, three of them at 128 and 256;
 B = 3 images with distinct volumes, latents and FiLM vectors; 5 x 5 rays x 14 samples = 350 points per image (10 full tiles, a 30-row
 tile, one idle wave), both passes, forced fine_z; the stage on images 1..2 and on image 2 alone; pass 2 with 33 points per image (a 1-row
-last tile, three idle waves) and with 128 (no idle wave).  Every buffer lies between guards and starts as an fp16 NaN canary.
+last tile, three idle waves) and with 128 (no idle wave).  Every buffer lies between guards and starts as an fp16 NaN canary.  One more
+stage call, SHORTSIREN_FG at H = 64 on pass 2: images 0..1 with so many points that the tile groups are about 2.5 x the CU count and no
+multiple of 8 -- every block takes its second and third trip through the tile loop, and every element is checked as above.
 
 Measured on an MI355X (each launch prints its own line).  Every equality holds on every launch, the input tiles of all levels included.
 Worst |err| / bound over a network's eight launches, and for (d) the launch and slab with the kernel's largest share beyond one fp16 ulp
@@ -172,6 +174,19 @@ class Net:
         g = torch.Generator().manual_seed(17)
         self.u_strat, self.u_fine = (torch.rand((B, P, S_), generator=g).to(self.dev) for _ in range(2))
         self.fine_z = (0.25 + 1.7 * torch.rand((B, P, S_), generator=g)).to(self.dev).contiguous()
+
+
+@pytest.mark.parametrize("variant,H", [("SHORTSIREN_FG", 64)])
+def test_stored_rows_when_every_block_takes_a_second_and_third_trip(dev, variant, H):
+    """The stage alone, pass 2, images 0..1, on the long shape of tests/test_gpu_store_pw16.py (store_pw16_common.long_shape: 2 ceil(tiles
+    per image / 4) tile groups are about 2.5 x the CU count and no multiple of 8, the last tile ragged), through stage() and with it
+    every check of the test below, (d) included.  About 41 k points per image on 256 CUs: the test takes 2.6 s there, the float64 and
+    float32 reference networks of eight 64-wide layers included."""
+    import store_pw16_common
+    nt = Net(dev, variant, H)
+    R, S_ = store_pw16_common.long_shape(torch.cuda.get_device_properties(dev).multi_processor_count)
+    points = K.random_points(nt.cs, R * R * S_, 23)
+    nt.stage(nt.cfg(R, S_), 2, 0, 2, points, nt.gather(points), f"stage points {R * R * S_}")
 
 
 @pytest.mark.parametrize("variant,H", K.NETS)
